@@ -22,9 +22,15 @@ one fixed-size RCCL all-gather of the survivors per level; the leaf blocks are b
 `--config c5` is BASELINE config 5: sponge(5) at 1/2048 (2048^3 effective), grid 16: subdivision + grid_eval
 of its 1.34 M leaf blocks (5.5 G samples) -- the multi-GPU workload that is not launch-latency-sized.
 
-The JSON line carries `roofline` for the dominant kernel (timed with HIP events on its own stream),
+The JSON line carries `roofline` for the dominant kernel (timed with HIP events on its own stream).  A plain run
+does only what that line needs: set up, warm up, time the --steps steps, print.  `--full` adds the legs beside
+the headline, each with a run of its own: the interpreter on the dense launch, the comparison of what the timed
+steps wrote with the CPU oracle (`verified`), the same steps replayed from a hipGraph (`graph_replay`),
 `roofline_hbm` (the HBM-bound regime: the same dense kernel on tapes whose arithmetic fits under the store
 stream) and, at N = 1, `cpu_baseline` (the CPU oracle on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (dump_step / dump_c4), so that
+two builds can be compared output for output: the inputs are the same from run to run.
 """
 import argparse
 import ctypes
@@ -84,7 +90,16 @@ def main():
     ap.add_argument("--n", type=int, default=None, help="grid edge (default: the config's)")
     ap.add_argument("--evaluator", choices=["auto", "specialised", "interpreter"], default="auto",
                     help="auto = per-tape hipRTC specialisation when it builds, else the tape interpreter")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: interpreter, oracle check, hipGraph replay, HBM regime, CPU baseline "
+                         "(each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1 (a rank holds only its share of the outputs)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Called directly with --gpus N (the driver launches torch.distributed.run itself): start the ranks as a
@@ -336,7 +351,7 @@ def main():
 
     # the interpreter on the same dense launch, timed the same way (reported, not part of `value`)
     interp_ms = []
-    if dense_leg:
+    if dense_leg and args.full:
         ev0, ev1 = warm_events[0], warm_events[1]
         for i in range(3):
             check(lib.hu_event_record(ev0, stream), "record")
@@ -346,6 +361,11 @@ def main():
             check(lib.hu_event_synchronize(ev1), "sync")
             if i:
                 interp_ms.append(elapsed(ev0, ev1))
+    # the warm-up above waits for the host after every step, and the device clocks down while it idles (the dense kernel
+    # measured 0.41 ms after it against 0.40 after back-to-back launches): steps of the timed path enqueued back to back
+    # bring it to the clocks of the free-running loop before the timed region
+    for k in range(32):
+        one_step(None, k)
     barrier()
     t0 = time.perf_counter()
     last_mine = None
@@ -362,9 +382,11 @@ def main():
     # the timed traversals were not looked at while they ran: validate now (identical work every step)
     for used in pipes[:min(args.steps, n_pipes)]:
         assert used.check() == totals, "the timed steps did not reproduce the warm-up traversal"
+    if args.dump_outputs:      # (before the hipGraph leg, whose replays rewrite the outputs)
+        dump_step(np, torch, args.dump_outputs, dense_out if dense_leg else None, last_mine, leaf_out[0], totals)
     # what the timed steps WROTE, against the CPU oracle, bit for bit (outside the timing; a checker, nothing measured)
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verified = verify_outputs(np, torch, host_tape, dense_out if dense_leg else None, corner, step_f, x0, n, last_mine,
                                   leaf_out[0], resolution, (box.a.x, box.a.y, box.a.z), leaf_step_f, leaf_dims)
         if world > 1:
@@ -376,7 +398,7 @@ def main():
     # up to eight steps per graph + one graph for the remainder, EXACTLY --steps steps in all; what it shows is the
     # host's share of a step -- ~25 ctypes / torch calls enqueued directly, one graph launch per eight steps replayed
     graph_leg = None
-    if not args.no_graph and (world == 1 or args.graph):
+    if args.full and not args.no_graph and (world == 1 or args.graph):
         try:
             barrier()
             unit = min(8, args.steps)
@@ -425,7 +447,7 @@ def main():
 
     b_avg, c_avg, dense_avg_ms = allmax(avg(b_ms)), allmax(avg(c_ms)), avg(dense_ms)
     hbm_leg = None
-    if rank == 0 and world == 1 and not args.no_hbm_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_hbm_leg:
         hbm_leg = hbm_regime(lib, check, hip_util, cc, torch, np, dev, stream, n if dense_leg else 512, evaluator)
 
     if rank == 0:
@@ -518,7 +540,7 @@ def main():
             line["interpreter_dense_kernel_ms"] = round(avg(interp_ms), 4)
         if hbm_leg is not None:
             line["roofline_hbm"] = hbm_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(host_tape, n if dense_leg else 512)
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()
@@ -609,12 +631,15 @@ def run_c4(args, real_stdout, rank, world, dev):
         wall = float(dist.allreduce_max(torch.tensor([wall], dtype=torch.float64, device=dev)).item())
     partial, totals_timed = pipe.finish()
     assert totals_timed == totals, "the timed steps did not reproduce the warm-up traversal"
-    mp = finish(dict(zip(_KEYS, dist.allreduce_sum(partial.clone()).tolist())))
+    integrals = dist.allreduce_sum(partial.clone()).tolist()
+    mp = finish(dict(zip(_KEYS, integrals)))
+    if args.dump_outputs:
+        dump_c4(np, args.dump_outputs, integrals, mp, totals)
     parents = [1] + [int(t) for t in totals]
     samples = sum(p * c for p, c in zip(parents, cells))
     leaf_parents_here = int(pipe.pipe.lists[-2][0, 0].item())       # this rank's share of the leaf level's parents
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verified = verify_c4(np, torch, host_tape, pipe, levels, leaf_parents_here)
         if world > 1:
             bad = torch.tensor([0.0 if verified["ok"] else 1.0], dtype=torch.float64, device=dev)
@@ -659,7 +684,7 @@ def run_c4(args, real_stdout, rank, world, dev):
                 "roofline": roofline}
         if verified is not None:
             line["verified"] = verified
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_c4(host_tape, levels, box)
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()
@@ -757,6 +782,49 @@ def verify_outputs(np, torch, host_tape, dense_out, corner, step, x0, n, mine, l
         out["leaf_blocks"] = {"checked": int(len(pick)), "of": count, "samples_checked": int(len(pick)) * cells, "ok": bool(ok)}
         out["ok"] = out["ok"] and bool(ok)
     return out
+
+
+DUMP_SEED = 20261016
+
+
+def dump_step(np, torch, out_dir, dense_out, mine, leaf_out, totals, dense_samples=1 << 20, leaf_blocks=1024, corners_max=1 << 18):
+    """What the last timed step computed, as a caller of the step receives it, to `out_dir`/<name>.npy (< 64 MB in all;
+    the samples are drawn with a fixed seed, so two runs with the same arguments write comparable files):
+      survivors_per_level  (levels,)      float64  cells that survived each level of B
+      dense_sample         (S, 4)         float32  A: S voxels of the float4 grid, flat indices drawn with the seed
+      leaf_corners         (L, 3)         float64  B's leaf list: integer corners, sorted (a seeded sample of corners_max if longer)
+      leaf_blocks          (K, 16^3)      float32  C: K leaf blocks drawn with the seed from the sorted list
+      leaf_block_corners   (K, 3)         float64  their corners
+    The compaction lists the leaf blocks in no fixed order, so the list is sorted by corner before anything is drawn."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"survivors_per_level": np.asarray(totals, dtype=np.float64)}
+    if dense_out is not None:
+        flat = dense_out.view(-1, 4)
+        idx = rng.integers(0, flat.shape[0], min(dense_samples, flat.shape[0]))
+        out["dense_sample"] = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float32)
+    count = int(mine[0, 0].item())
+    rows = mine[1:1 + count].cpu().numpy()
+    order = np.lexsort(rows.T[::-1])          # by column 0, then 1, 2, 3
+    corners = rows[order, :3].astype(np.float64)
+    out["leaf_corners"] = corners if count <= corners_max else corners[np.sort(rng.choice(count, corners_max, replace=False))]
+    pick = np.sort(rng.choice(count, min(leaf_blocks, count), replace=False)) if count else np.zeros(0, np.int64)
+    out["leaf_block_corners"] = corners[pick]
+    rows_picked = torch.from_numpy(order[pick].astype(np.int64)).to(leaf_out.device)
+    out["leaf_blocks"] = leaf_out[rows_picked].cpu().numpy().astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def dump_c4(np, out_dir, integrals, mp, totals):
+    """--config c4: the mass properties the last timed step integrated, to `out_dir`/<name>.npy (float64):
+    integrals (the ten reduced integrals, mass_properties._KEYS order), volume, centroid, inertia_tensor, and
+    ambiguous_cells_per_level."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"integrals": integrals, "volume": [mp.volume], "centroid": [mp.centroid.x, mp.centroid.y, mp.centroid.z],
+           "inertia_tensor": mp.inertia_tensor, "ambiguous_cells_per_level": totals}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def hbm_regime(lib, check, hip_util, cc, torch, np, dev, stream, n, evaluator, tapes=None):

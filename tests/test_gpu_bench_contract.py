@@ -1,5 +1,6 @@
 """bench.py prints ONE JSON line with the fields the driver and the judge read (reduced grid so that it
-takes seconds; the numbers themselves are not checked, only that they are there and consistent)."""
+takes seconds; the numbers themselves are not checked, only that they are there and consistent).  The legs beside the
+headline run with --full; a plain run times the steps alone, and --dump-outputs writes what its last step computed."""
 import json
 import os
 import subprocess
@@ -12,9 +13,9 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def run_bench(*extra):
+def run_bench(*extra, full=True):
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--n", "128"]
-                          + list(extra), capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          + (["--full"] if full else []) + list(extra), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, proc.stdout
@@ -80,7 +81,7 @@ def test_bench_config_c5_reduced(hip):
 
 
 def run_bench_env(env, *extra):
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--n", "128",
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--n", "128", "--full",
                            "--no-hbm-leg", "--no-cpu-baseline"] + list(extra), capture_output=True, text=True, timeout=600, cwd=ROOT,
                           env=dict(os.environ, **env))
     assert proc.returncode == 0, proc.stderr[-3000:]
@@ -120,3 +121,70 @@ def test_step_counts_are_replayed_exactly(hip):
         line = run_bench_env({}, "--steps", str(steps))
         g = line["graph_replay"]
         assert line["steps"] == steps and g["captured"] and g["steps"] == steps and g["steps_per_graph"] == per_graph
+
+
+def load_dump(d):
+    import numpy as np
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_plain_run_times_the_steps_alone_and_dumps_its_outputs(hip, tmp_path):
+    """Without --full: the headline fields, none of the legs beside them, exactly --steps timed steps.  --dump-outputs
+    writes what the last step computed (float32 / float64, under 64 MB), the same bytes from run to run, and the bytes
+    are what the CPU oracle computes at the dumped voxels and leaf blocks."""
+    import numpy as np
+    import bench
+    import codecad_amd as cc
+    import oracle
+    from conftest import same_bits
+    dumps = []
+    for i, steps in enumerate((2, 5)):
+        d = str(tmp_path / ("run%d" % i))
+        line = run_bench("--steps", str(steps), "--dump-outputs", d, full=False)      # (the last --steps given is the one taken)
+        assert line["steps"] == steps and line["warmup"] == 1 and line["n_gpus"] == 1
+        for key, kind in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str),
+                          ("ms_per_step", float)):
+            assert isinstance(line[key], kind), key
+        for key in ("interpreter_dense_kernel_ms", "verified", "graph_replay", "roofline_hbm", "cpu_baseline"):
+            assert key not in line, key
+        s = line["samples_per_step"]
+        assert line["value"] == pytest.approx((s["dense"] + s["subdivision"] + s["leaf_blocks"]) / (line["ms_per_step"] * 1e-3) / 1e6, rel=2e-2)
+        dumps.append(load_dump(d))
+    a, b = dumps
+    assert sorted(a) == ["dense_sample", "leaf_block_corners", "leaf_blocks", "leaf_corners", "survivors_per_level"]
+    assert sum(v.nbytes for v in a.values()) < 64 * 2 ** 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert a[name].shape == b[name].shape and a[name].tobytes() == b[name].tobytes(), name
+    n = 128
+    count = int(a["survivors_per_level"][-1])
+    assert list(a["survivors_per_level"]) == s["survivors_per_level_global"] and count > 0
+    assert a["leaf_corners"].shape == (count, 3) and np.array_equal(np.unique(a["leaf_corners"], axis=0), a["leaf_corners"])
+    assert a["leaf_blocks"].shape == (min(1024, count), 16 ** 3) and a["leaf_block_corners"].shape == (min(1024, count), 3)
+    assert a["dense_sample"].shape == (min(1 << 20, n ** 3), 4)
+
+    tape = cc.nodes.make_program(cc.examples.sponge(4))
+    # dense voxels: flat indices of the (n, n, n, 4) grid drawn with bench.DUMP_SEED; sample position corner + step * index
+    idx = np.random.default_rng(bench.DUMP_SEED).integers(0, n ** 3, min(1 << 20, n ** 3))[:4096]
+    xyz = np.stack(np.unravel_index(idx, (n, n, n)), axis=1).astype(np.float32)
+    pts = np.float32(-0.5 + 0.5 / n) + np.float32(1.0 / n) * xyz
+    assert same_bits(a["dense_sample"][:4096], oracle.evaluate_points(tape, pts))
+    # leaf blocks: corner = integer corner * resolution + origin of the hierarchy, in float64, cast once
+    res = 1.0 / n
+    box = cc.examples.sponge(4).bounding_box().expanded_additive(res / 2)
+    leaf_int_step, leaf_dims = cc.subdivision.calculate_block_sizes(box, 3, res, 16, True)[-1]
+    for c_int, got in list(zip(a["leaf_block_corners"], a["leaf_blocks"]))[:4]:
+        c = (c_int * res + np.array([box.a.x, box.a.y, box.a.z])).astype(np.float32)
+        want = oracle.grid_eval_pymcubes(tape, c, np.float32(leaf_int_step * res), tuple(int(v) for v in leaf_dims))
+        assert same_bits(got, np.asarray(want).reshape(-1))
+
+
+def test_plain_run_c4_dumps_the_mass_properties(hip, tmp_path):
+    import numpy as np
+    line = run_bench("--config", "c4", "--dump-outputs", str(tmp_path), full=False)
+    d = load_dump(str(tmp_path))
+    assert sorted(d) == ["ambiguous_cells_per_level", "centroid", "inertia_tensor", "integrals", "volume"]
+    assert all(v.dtype == np.float64 for v in d.values())
+    assert d["volume"][0] == line["result"]["volume"] > 0 and list(d["centroid"]) == line["result"]["centroid"]
+    assert list(d["ambiguous_cells_per_level"]) == line["samples_per_step"]["ambiguous_cells_per_level"]
+    assert d["inertia_tensor"].shape == (3, 3) and "verified" not in line and "cpu_baseline" not in line

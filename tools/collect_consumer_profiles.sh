@@ -1,13 +1,13 @@
 #!/bin/bash
 # Run ON THE GPU BOX (through gpurun): rocprofv3 kernel stats of the consumers of the path -- the mesh pipeline
 # (subdivision, leaf-block evaluation, marching cubes, STL records) and the renderers -- per-tape code.
-# Outputs land in gpurun_out/prof_<tag>/; tools/publish_profiles.py does not handle these: copy the two
+# Outputs land in $COLLECT_DIR/prof_<tag>/ (default collected/); tools/publish_profiles.py does not handle these: copy the two
 # *_kernel_stats.csv into profiles/ by hand (see profiles/README.md).
 set -u
 TAG=${1:-r01_consumers}
 export CODECAD_AMD_SPECIALIZE=1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-OUT=gpurun_out/prof_$TAG
+OUT=${COLLECT_DIR:-collected}/prof_$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/mesh" -- python3 tools/prof_mesh.py > "$OUT/mesh.log" 2>&1
 echo "mesh rc=$?"

@@ -4,10 +4,11 @@
     s = codecad.shapes.sphere(130) & codecad.shapes.box(100)
     codecad.mass_properties(s, 1.0)
 
-Public layout mirrors the reference package (reference codecad/__init__.py:1-11) for the
-hot path only: `shapes`, `util`, `nodes`, `hip_util` (in place of `cl_util`), `grid_eval`,
-`subdivision`, `mass_properties`.  Renderers, assemblies and the CLI are out of scope
-(DESIGN.md).  Importing the package does not touch the GPU; the first kernel launch does,
+Public layout mirrors the reference package (reference codecad/__init__.py:1-11): `shapes`,
+`util`, `nodes`, `hip_util` (in place of `cl_util`), `grid_eval`, `subdivision`,
+`mass_properties`, `assembly` (assemblies.py) and the renderers the package has (`rendering`);
+`interference(asm, resolution)` finds the overlapping instances of an assembly on the device.
+The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
 from . import util  # noqa: F401
@@ -19,6 +20,9 @@ from . import subdivision  # noqa: F401
 from .mass_properties import mass_properties, MassProperties  # noqa: F401
 from . import examples  # noqa: F401
 from . import rendering  # noqa: F401
+from . import assemblies  # noqa: F401
+from .assemblies import assembly  # noqa: F401
+from .interference import interference, InterferenceReport  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
-           "MassProperties", "examples"]
+           "MassProperties", "examples", "assembly", "interference", "InterferenceReport"]

@@ -193,6 +193,7 @@ int ensure_attrs()
     if ((rc = ensure_attrs_n<1>())) return rc;
     if ((rc = ensure_attrs_n<2>())) return rc;
     HU_HIP(hu_render::allow_big_lds(kMaxLds));   // the ray caster and the bitmap kernels (render.hip)
+    HU_HIP(hu_interference::allow_big_lds(kMaxLds));   // (interference.hip)
     done_for_device = dev;
     return HU_OK;
 }
@@ -1078,6 +1079,113 @@ int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_d
     if (rows == 0 || rows > 65535u) return fail(HU_ERR_BAD_ARG, "rows must be in 1..65535");
     HU_HIP(hu_render::mass_integrals((const double4*)parents_dev, sums_dev, max_parents, 0u, n_parents_dev, s, out_dev, rows, (hipStream_t)stream));
     return HU_OK;
+}
+
+int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, size_t bytes, int* distance_only_out,
+                          uint32_t* lane_bytes)
+{
+    if (!tapes || !table_host || !distance_only_out || !lane_bytes) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "an interference table holds 1..64 instances");
+    if (bytes < (size_t)n * sizeof(hu_interference::InstanceRec)) return fail(HU_ERR_BAD_ARG, "table buffer too small");
+    bool all_do = true;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!tapes[i]) return fail(HU_ERR_BAD_ARG, "NULL tape");
+        all_do = all_do && distance_only(tapes[i]);
+    }
+    // one interpreter instantiation per kernel: the distance-only programs when every instance has one, else the full ones.
+    // The wavefronts of a workgroup run different instances at once, and the register file interleaves every lane of the
+    // workgroup (float4 slot r of lane l at r * block + l, the scalar slots after n4 * block of them): so every instance
+    // gets the same n4, the largest, and no instance's float4 slots reach into another one's scalar slots.
+    uint32_t n4 = 0, n_res = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        n4 = std::max(n4, (uint32_t)(all_do ? tapes[i]->n_point_slots : tapes[i]->n_slots));
+        n_res = std::max(n_res, all_do ? (uint32_t)tapes[i]->n_result_slots : 0u);
+    }
+    auto* recs = static_cast<hu_interference::InstanceRec*>(table_host);
+    for (uint32_t i = 0; i < n; ++i)
+        recs[i] = hu_interference::InstanceRec{all_do ? tapes[i]->recs_do_dev : tapes[i]->recs_dev, tapes[i]->extra_dev, n4, 0u};
+    *distance_only_out = all_do ? 1 : 0;
+    *lane_bytes = n4 * 16u + n_res * 4u;
+    return HU_OK;
+}
+
+namespace {
+
+// workgroup size for an interference launch: four wavefronts (four cells) while their register file fits 48 KiB, as
+// launch_shape() sizes the one-voxel interpreter kernels; the LDS holds the largest instance's file
+int interference_launch(bool leaf, int distance_only_kernel, uint32_t lane_bytes, hu_interference::Args& a, void* stream)
+{
+    uint32_t block = 256;
+    while (block > 64u && (size_t)lane_bytes * block > 48 * 1024) block >>= 1;
+    const size_t regfile = (size_t)lane_bytes * block;
+    if (regfile + kScratchBytes > kMaxLds)
+        return fail(HU_ERR_UNSUPPORTED, "an instance keeps more values live than fit the 160 KiB LDS register file");
+    int rc;
+    if ((rc = ensure_attrs())) return rc;
+    a.scratch_offset = (uint32_t)regfile;
+    const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
+    if (blocks == 0) return HU_OK;
+    if (blocks > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
+    HU_HIP(hu_interference::level(leaf, distance_only_kernel != 0, a, (uint32_t)blocks, block, regfile + kScratchBytes, (hipStream_t)stream));
+    return HU_OK;
+}
+
+int interference_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                      const uint32_t dims[3], const float corner[3], float step, uint64_t* evaluations_dev, hu_interference::Args& a)
+{
+    if (!table_dev || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
+        return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "1..64 instances");
+    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0 || dims[0] > 65536u || dims[1] > 65536u)
+        return fail(HU_ERR_BAD_ARG, "lattice dims must be positive, x and y at most 65536");
+    std::memset(&a, 0, sizeof(a));
+    a.table = static_cast<const hu_interference::InstanceRec*>(table_dev);
+    a.n_instances = n;
+    a.parents = static_cast<const uint4*>(parents_dev);
+    a.n_parents_dev = n_parents_dev;
+    a.max_parents = max_parents;
+    for (int i = 0; i < 3; ++i) {
+        a.dims[i] = dims[i];
+        a.corner[i] = corner[i];
+    }
+    a.step = step;
+    a.evaluations = reinterpret_cast<unsigned long long*>(evaluations_dev);
+    return HU_OK;
+}
+
+}  // namespace
+
+int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
+                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                   uint64_t* evaluations_dev, void* stream)
+{
+    hu_interference::Args a;
+    int rc;
+    if ((rc = interference_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a))) return rc;
+    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (child_side < 4u || child_side > 16384u) return fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
+    a.child_side = child_side;
+    a.thr = thr;
+    a.counter = counter_dev;
+    a.children = static_cast<uint4*>(children_dev);
+    a.capacity = capacity;
+    return interference_launch(false, distance_only_kernel, lane_bytes, a, stream);
+}
+
+int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
+                                  uint64_t* evaluations_dev, void* stream)
+{
+    hu_interference::Args a;
+    int rc;
+    if ((rc = interference_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a))) return rc;
+    if (!pairs_dev) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    a.child_side = 1u;
+    a.pairs = static_cast<hu_interference::PairAcc*>(pairs_dev);
+    return interference_launch(true, distance_only_kernel, lane_bytes, a, stream);
 }
 
 int hu_ray_caster(hu_tape t, const float origin[4], const float forward[4], const float up[4], const float right[4],

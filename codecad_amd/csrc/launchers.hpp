@@ -1,12 +1,13 @@
-// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip.
+// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip and interference.hip.
 //
-// Two translation units hold kernels (hip_util/builder.py lists the flags of each):
+// Translation units that hold kernels (hip_util/builder.py lists the flags of each):
 //   hip_util.hip  the dense / leaf-block / classification kernels over the tape interpreter, built with
 //                 -mllvm -structurizecfg-skip-uniform-regions (the interpreter's dispatch loop needs it);
 //   render.hip    every other kernel -- ray caster, bitmap, 2D contouring, the mass-integral reduction, the
 //                 arithmetic self-test -- built WITHOUT it: that option once let a scalar branch choose a per-lane
 //                 value in a divergent loop (csrc/exchange.hip), so it stays confined to the kernels that are
-//                 nothing but the interpreter's wave-uniform loop around branch-free ops.
+//                 nothing but the interpreter's wave-uniform loop around branch-free ops;
+//   interference.hip  the interference check between the instances of an assembly, built without it as well;
 // Each function enqueues one launch and returns hipGetLastError().
 #pragma once
 
@@ -29,3 +30,45 @@ hipError_t selftest_math(unsigned long long* counts_dev);
 hipError_t selftest_minmax3(unsigned long long* counts_dev);
 
 }  // namespace hu_render
+
+namespace hu_interference {
+
+// one instance of the device table: the program the kernels interpret for it (distance-only or full, the same kind for
+// every instance of a launch), its constants and the float4 slots of the register file (the same for every instance)
+struct InstanceRec {
+    const sdf::Rec* prog;
+    const float* extra;
+    uint32_t n4, pad;
+};
+static_assert(sizeof(InstanceRec) == 24, "hu_interference_table writes 24-byte records");
+
+// the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j]: samples inside both, the sums of their x, y, z
+// indices, and the box of those indices (lo starts at 0xffffffff, hi at 0)
+struct PairAcc {
+    unsigned long long sums[4];   // count, sum x, sum y, sum z
+    uint32_t lo[3], hi[3];
+    uint32_t pad[2];
+};
+static_assert(sizeof(PairAcc) == 64, "interference.py reads 64-byte accumulators");
+
+struct Args {
+    const InstanceRec* table;
+    uint32_t n_instances;
+    const uint4* parents;            // rows {x0 | y0 << 16, z0, mask lo, mask hi} after the list's header row
+    const uint32_t* n_parents_dev;   // word 0 of the parents' header
+    uint32_t max_parents;            // the parents' capacity (the launch is sized for it)
+    uint32_t child_side;             // cells: side of a child cell in samples (leaf: 1)
+    uint32_t dims[3];
+    float corner[3], step, thr;
+    uint32_t* counter;               // cells: word 0 of the children's header
+    uint4* children;                 // cells: the children's rows
+    uint32_t capacity;
+    PairAcc* pairs;                  // leaf
+    unsigned long long* evaluations; // per-instance sample evaluations, added up per wavefront
+    uint32_t scratch_offset;         // bytes of LDS taken by the register file (the compaction's scratch follows)
+};
+
+hipError_t allow_big_lds(size_t bytes);
+hipError_t level(bool leaf, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
+
+}  // namespace hu_interference

@@ -130,6 +130,11 @@ class Shape2D(ShapeBase):
         solid = simple3d.Extrusion(self, height)
         return solid if symmetrical else solid.translated(0, 0, height / 2)
 
+    def make_part(self, name, attributes=None):
+        """This shape as a named part instance for assemblies (codecad_amd.assemblies)."""
+        from .. import assemblies
+        return assemblies.make_part(self, name, attributes)
+
     def revolved(self, r=0, twist=0):
         """Revolve the x > 0 half around the y axis, optionally twisting (degrees)."""
         from . import simple3d
@@ -199,6 +204,11 @@ class Shape3D(ShapeBase):
 
     def symmetrical_z(self):
         return self.rotated_y(90).symmetrical_x().rotated_y(-90)
+
+    def make_part(self, name, attributes=None):
+        """This shape as a named part instance for assemblies (codecad_amd.assemblies)."""
+        from .. import assemblies
+        return assemblies.make_part(self, name, attributes)
 
 
 class TapeShape(Shape3D):

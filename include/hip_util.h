@@ -194,6 +194,35 @@ int hu_mass_properties_level_owned(hu_tape t, const double* parents_dev, const u
 int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev,
                                uint32_t max_parents, double s, double* out_dev, uint32_t rows, void* stream);
 
+/* ---- interference between the instances of an assembly (codecad_amd/interference.py) --------------
+ * The instances' tapes are evaluated one at a time by the interpreter; the kernels reach them through a device
+ * table of 24-byte records, n <= 64 (one bit each in a cell's candidate mask).  A cell list is a [header row |
+ * rows...] buffer of 16-byte rows {x0 | y0 << 16, z0, mask lo, mask hi}, header word 0 its length; a cell is a cube
+ * of lattice samples (corner + step * index, per axis) whose first sample is (x0, y0, z0).
+ * hu_interference_table: no device work.  Writes the table of `tapes` into table_host (host memory of at least
+ *   n * 24 bytes; the caller uploads it): every instance's distance-only program when all have one (*distance_only
+ *   = 1), else every instance's full program, and *lane_bytes, the LDS bytes per lane of a register file that holds
+ *   every instance's (one layout for all: the wavefronts of a workgroup run different instances at once).
+ * hu_interference_cells_indirect: a cell of side 4 * child_side per parent row; each of its 4^3 children keeps the
+ *   candidates whose distance at the child's centre is below thr, and is appended to children_dev (counted into
+ *   *counter_dev; rows past `capacity` are dropped and counted) when two or more remain.
+ * hu_interference_leaf_indirect: a cell of 4^3 samples per parent row; every pair (i < j) of candidates with
+ *   samples inside both (w < 0) adds to pairs_dev[i * n + j] (64 bytes: uint64 count, x, y, z index sums; uint32
+ *   min x, y, z; uint32 max x, y, z; 8 bytes unused).
+ * Both read the number of parents from *n_parents_dev (at most max_parents are there) and add the sample
+ * evaluations they perform to *evaluations_dev. */
+int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, size_t bytes, int* distance_only,
+                          uint32_t* lane_bytes);
+int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
+                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                   uint64_t* evaluations_dev, void* stream);
+int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
+                                  uint64_t* evaluations_dev, void* stream);
+
 /* ---- renderers on the same evaluate() -------------------- */
 /* rendering/ray_caster.cl:146-159, launched by rendering/ray_caster.py:93-110 with global size
  * (width, height).  origin/forward/up/right: float4 as the reference passes them (forward already

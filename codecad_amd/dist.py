@@ -328,6 +328,13 @@ class LevelPipeline:
             self.mine = [torch.zeros((c + 1, k), dtype=torch.int32, device=device) for c in self.capacities]
             self.stats = torch.zeros((len(self.capacities), 2), dtype=torch.int32, device=device)
 
+    def sums_level(self, level):
+        """Does this rank add what it summed at `level` (mass properties: the inside cells' integrals) into its partial result?
+        Every level must count exactly once over the ranks: a replicated level before the last one is classified IN FULL by
+        every rank, so only rank 0 counts it; the last replicated level is owned and the exchanged ones (the leaf level too)
+        are sliced, so there every rank counts its own part."""
+        return level + 1 >= self.replicate or self.rank == 0
+
     def enqueue(self):
         """Enqueue the whole traversal on the current stream.  Returns the buffer [header | rows] holding this
         rank's share of the last level's survivors (no exchange: all of them)."""
@@ -500,7 +507,7 @@ class MassPipeline:
     reducing its inside cells' ten integrals on the device (hu_mass_integrals_indirect) into its own small buffer.
     `enqueue()` puts the whole integration on the stream; `finish()` waits once, validates the lists (Overflow ->
     rebuild with larger ones, every rank alike) and returns this rank's ten partial integrals, a (10,) float64 tensor
-    on the device, for ONE all-reduce.  `levels` = [(cell size, dims)], the last one being the leaf level."""
+    on the device, for ONE all-reduce: the sum of the levels that `LevelPipeline.sums_level` gives this rank.  `levels` = [(cell size, dims)], the last one being the leaf level."""
 
     def __init__(self, tape, levels, box_a, capacities, device, stream):
         import ctypes
@@ -549,10 +556,15 @@ class MassPipeline:
             check(lib.hu_mass_integrals_indirect(parents.data_ptr(), sums.data_ptr(), n_parents.data_ptr(), int(max_parents), float(s),
                                                  pieces.data_ptr(), int(pieces.shape[0]), stream), "hu_mass_integrals_indirect")
 
-        # (the leaf level lists nothing: it is never worth replicating -- its parents are the work -- and needs no exchange)
-        cells = [int(d[0]) * int(d[1]) * int(d[2]) for _, d in levels]
         self.pipe = LevelPipeline(top.view(torch.int32).reshape(1, 8), capacities, classify, _hip_slice_rows(lib, check, stream),
-                                  device, stream, replicate=min(replicated_levels(1, capacities, cells), len(levels) - 1))
+                                  device, stream, replicate=self.replicated(levels, capacities[:-1]))
+
+    @staticmethod
+    def replicated(levels, capacities, limit=None):
+        """How many leading levels a MassPipeline with these list capacities (one per non-leaf level) replicates.
+        (The leaf level lists nothing: it is never worth replicating -- its parents are the work -- and needs no exchange.)"""
+        cells = [int(d[0]) * int(d[1]) * int(d[2]) for _, d in levels]
+        return min(replicated_levels(1, list(capacities) + [0], cells, limit), len(levels) - 1)
 
     def enqueue(self):
         self.pipe.enqueue()
@@ -564,9 +576,34 @@ class MassPipeline:
         except Overflow as e:
             raise Overflow(e.needed[:-1])       # (the leaf level's "list" has no capacity to speak of)
         partial = torch.zeros(10, dtype=torch.float64, device=self.device)
-        for pieces in self.pieces:
-            partial = partial + pieces.sum(dim=0)     # a fixed reduction over <= 64 rows per level
+        for level, pieces in enumerate(self.pieces):
+            if self.pipe.sums_level(level):           # (a fully replicated level: rank 0's alone)
+                partial = partial + pieces.sum(dim=0)     # a fixed reduction over <= 64 rows per level
         return partial, totals[:-1]
+
+
+def grown_capacities(needed, capacities):
+    """The capacities a traversal that overflowed is repeated with: what it needed (Overflow.needed, the same on every
+    rank) + 12.5 % + 16, never less than before."""
+    from .subdivision import checked_capacity
+    return [checked_capacity(max(int(v * 1.125) + 16, c)) for v, c in zip(needed, capacities)]
+
+
+def mass_partial(tape, levels, box_a, capacities, device, stream, tries=None):
+    """A MassPipeline enqueued and finished, and built afresh with grown capacities while a list overflows (every rank
+    alike).  Each try is a new pipeline, its `replicate` worked out from ITS capacities, so nothing of an overflowed try --
+    buffers, sums, the levels it replicated -- reaches the result.  -> this rank's (10,) partial integrals, for ONE
+    all-reduce.  `tries`, a list, receives (replicate, capacities) of every try."""
+    while True:
+        pipe = MassPipeline(tape, levels, box_a, capacities, device, stream)
+        if tries is not None:
+            tries.append((pipe.pipe.replicate, list(capacities)))
+        pipe.enqueue()
+        try:
+            partial, _ = pipe.finish()
+            return partial
+        except Overflow as e:
+            capacities = grown_capacities(e.needed, capacities)
 
 
 def integrate_levels(top_parents, n_levels, level_fn):
@@ -593,13 +630,25 @@ def integrate_levels(top_parents, n_levels, level_fn):
     return allreduce_sum(totals)
 
 
+def mass_hierarchy(box, resolution, grid_size):
+    """The hierarchy of mass_properties: (levels = [(cell size, dims)], the last one the leaf level; the first guess of
+    every non-leaf level's list capacity).  Host knowledge only: MassPipeline works out `replicate` from them."""
+    from . import subdivision
+    levels = [(resolution * cell, tuple(int(v) for v in dims)) for cell, dims in
+              subdivision.calculate_block_sizes(box, 3, resolution, grid_size, overlap=False)]
+    cells = [d[0] * d[1] * d[2] for _, d in levels]
+    return levels, subdivision.first_capacities(cells[:-1], row_bytes=32 + 40)
+
+
 def mass_properties(shape, resolution, grid_size=None):
     """`codecad_amd.mass_properties` sharded over the ranks of the process group (one GPU each): every level's parent
     list is cut into balanced slices, `hu_mass_properties_level_indirect` + `hu_mass_integrals_indirect` run on the
     slice, the ambiguous cells go through ONE fixed-size all-gather per level and `hu_slice_rows`, the ten integrals are
-    all-reduced once -- the whole integration enqueued without a host round trip (MassPipeline).  Same volume, centroid
-    and inertia as the single-GPU driver up to the order of the fp64 sums (~1e-15 relative)."""
-    from . import nodes, subdivision
+    all-reduced once -- the whole integration enqueued without a host round trip (MassPipeline).  Every level's integrals
+    count once over the ranks (LevelPipeline.sums_level: a replicated level before the last one on rank 0 only, every other
+    level on every rank, each its own slice or owned cells), so volume, centroid and inertia are the single-GPU driver's up
+    to the order of the fp64 sums (~1e-15 relative)."""
+    from . import nodes
     from .mass_properties import finish, _KEYS   # (the package attribute of that name is the function)
     from .hip_util import manager as hip_manager
 
@@ -611,18 +660,8 @@ def mass_properties(shape, resolution, grid_size=None):
     stream = torch.cuda.current_stream(device).cuda_stream
     tape = nodes.make_program_buffer(shape)
     box = shape.bounding_box()
-    levels = [(resolution * cell, tuple(int(v) for v in dims)) for cell, dims in
-              subdivision.calculate_block_sizes(box, 3, resolution, grid_size, overlap=False)]
-    cells = [d[0] * d[1] * d[2] for _, d in levels]
-    capacities = subdivision.first_capacities(cells[:-1], row_bytes=32 + 40)
-    while True:
-        pipe = MassPipeline(tape, levels, (box.a.x, box.a.y, box.a.z), capacities, device, stream)
-        pipe.enqueue()
-        try:
-            partial, _ = pipe.finish()
-            break
-        except Overflow as e:     # every rank sees the same sizes: all rebuild together
-            capacities = [subdivision.checked_capacity(max(int(v * 1.125) + 16, c)) for v, c in zip(e.needed, capacities)]
+    levels, capacities = mass_hierarchy(box, resolution, grid_size)
+    partial = mass_partial(tape, levels, (box.a.x, box.a.y, box.a.z), capacities, device, stream)
     totals = allreduce_sum(partial)
     return finish(dict(zip(_KEYS, totals.tolist())))
 
@@ -633,7 +672,8 @@ def subdivision(shape, resolution, overlap_edge_samples=True, grid_size=None):
     slice, the survivors go through one fixed-size all-gather and `hu_slice_rows` (LevelPipeline).  Returns (leaves, info): `leaves` an (n, 4) int32 device tensor of
     integer leaf corners, identical (as a set; ordered by rank slice) on every rank, and `info` with
     `dims`, `int_step`, `step`, `resolution`, `origin`, `level_counts` like LeafBlocks, plus `share`: this rank's
-    balanced share of the leaves (what a sharded consumer evaluates, e.g. hu_grid_eval_blocks: bench.py step C)."""
+    balanced share of the leaves (what a sharded consumer evaluates, e.g. hu_grid_eval_blocks: bench.py step C), and
+    `replicate`: how many leading levels every rank classified in full (the last of them by ownership)."""
     from . import nodes
     from . import subdivision as sub
     from .hip_util import manager as hip_manager
@@ -661,7 +701,7 @@ def subdivision(shape, resolution, overlap_edge_samples=True, grid_size=None):
             counts = pipe.check()
             break
         except Overflow as e:
-            capacities = [sub.checked_capacity(max(int(v * 1.125) + 16, c)) for v, c in zip(e.needed, capacities)]
+            capacities = grown_capacities(e.needed, capacities)
     if len(levels) > 1:
         # (a copy: the pipeline's buffers are sized for their capacities -- a first guess may be tens of MB -- and go with it)
         share = mine[1:1 + int(mine[0, 0])].clone()
@@ -670,7 +710,9 @@ def subdivision(shape, resolution, overlap_edge_samples=True, grid_size=None):
         # the whole shape is one leaf block: it is rank 0's, the other ranks' shares are empty
         leaves = torch.zeros((1, 4), dtype=torch.int32, device=device)
         share = leaves if pipe.rank == 0 else leaves[:0]
+    if 0 in counts:     # like LeafBlocks: no level after the first one that lists nothing
+        counts = counts[:counts.index(0) + 1]
     leaf_int_step, leaf_dims = levels[-1]
     info = {"tape": tape, "dims": leaf_dims, "int_step": leaf_int_step, "step": leaf_int_step * resolution,
-            "resolution": resolution, "origin": box.a, "level_counts": counts, "share": share}
+            "resolution": resolution, "origin": box.a, "level_counts": counts, "share": share, "replicate": pipe.replicate}
     return leaves, info

@@ -114,16 +114,19 @@ def _integrate(tape, box_a, levels):
     return dist.integrate_levels(top, len(levels), level_fn)
 
 
-def _integrate_pipeline(tape, box_a, levels, capacities, replicate=0):
+def _integrate_pipeline(tape, box_a, levels, capacities, replicate=0, details=None):
     """The same integration through dist.LevelPipeline as dist.MassPipeline drives it on the GPU: 32-byte rows of four
     doubles seen as eight int32 words, the count in the header's first word, every level (the leaf level too) a
-    classify call, nothing looked at by the host until check().  -> the ten integrals, all-reduced."""
+    classify call, nothing looked at by the host until check().  Each level's integrals are kept apart and added up by the
+    product's rule, LevelPipeline.sums_level (what MassPipeline.finish does).  -> (the ten integrals, all-reduced, global
+    ambiguous cells per level); `details`, a dict, receives this rank's per-level integrals ("levels") and the pipeline's
+    `replicate`."""
     import math
     import oracle
     from codecad_amd import dist
     from codecad_amd.mass_properties import integrals_host, _KEYS
 
-    partial = torch.zeros(10, dtype=torch.float64)
+    per_level = [torch.zeros(10, dtype=torch.float64) for _ in levels]
 
     def owned_kernel(row_words, shifted, s, thr, dims, own):
         """hu_mass_properties_level_owned restated over the oracle's distances: the kernel of mass_properties.cl:7-56 with
@@ -160,7 +163,7 @@ def _integrate_pipeline(tape, box_a, levels, capacities, replicate=0):
                 children += [[i * s + cx, j * s + cy, k_ * s + cz, tag] for i, j, k_, _ in cells.tolist()]
         if corners:
             d = integrals_host(np.array(sums, dtype=np.uint32), np.array(corners, dtype=np.float64), s)
-            partial.add_(torch.tensor([d[key] for key in _KEYS], dtype=torch.float64))
+            per_level[level].add_(torch.tensor([d[key] for key in _KEYS], dtype=torch.float64))
         capacity = out.shape[0] - 1
         out[0, 0] = len(children)
         children = children[:capacity]
@@ -171,6 +174,12 @@ def _integrate_pipeline(tape, box_a, levels, capacities, replicate=0):
     pipe = dist.LevelPipeline(top, list(capacities) + [0], classify, replicate=replicate)
     pipe.enqueue()
     totals = pipe.check()
+    partial = torch.zeros(10, dtype=torch.float64)
+    for level, piece in enumerate(per_level):
+        if pipe.sums_level(level):
+            partial = partial + piece
+    if details is not None:
+        details.update(levels=[t.clone() for t in per_level], replicate=pipe.replicate)
     return dist.allreduce_sum(partial), totals[:-1]
 
 
@@ -183,6 +192,19 @@ def _setup_mass():
     box = shape.bounding_box()
     levels = [(res * c, tuple(int(v) for v in d)) for c, d in subdivision.calculate_block_sizes(box, 3, res, 3, False)]
     return nodes.make_program(shape), tuple(box.a), levels
+
+
+def _setup_solid():
+    """A SOLID shape for mass properties (sphere_plus_box, res = extent / 27, grid 3): three levels, the coarse ones with
+    inside cells -- where a level counted on more than one rank shows in the volume."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from codecad_amd import examples, nodes
+    from codecad_amd.dist import mass_hierarchy
+    shape = examples.sphere_plus_box()
+    box = shape.bounding_box()
+    levels, _ = mass_hierarchy(box, max(box.size()) / 27, 3)
+    return nodes.make_program(shape), tuple(box.a), levels, max(box.size())
 
 
 def _setup():
@@ -297,6 +319,113 @@ def test_two_rank_traversal_equals_single_rank():
     single = _integrate(mtape, box_a, mlevels).tolist()
     assert np.allclose(got_integrals, single, rtol=1e-13, atol=1e-15)   # first moments are 0 up to rounding noise
     assert got_integrals[0] == pytest.approx((20 / 27) ** 2, rel=1e-12)   # the sponge's exact volume at this resolution
+
+
+def _same_integrals(got, want, extent, rtol=1e-13):
+    """The ten integrals (1, x, y, z, xx, yy, zz, xy, xz, yz) equal to `rtol`, each measured against its own scale:
+    volume x extent^degree (a moment that is zero by symmetry is rounding noise of that size)."""
+    scale = [abs(want[0]) * extent ** len(key) if key != "1" else abs(want[0]) for key in ("1", "x", "y", "z", "xx", "yy", "zz", "xy", "xz", "yz")]
+    return all(abs(g - w) <= rtol * max(abs(w), s) for g, w, s in zip(got, want, scale))
+
+
+def _worker_guard(target, rank, world, port, queue):
+    """A failing rank reports its traceback at once (the others would wait in a collective)."""
+    try:
+        target(rank, world, port, queue)
+    except BaseException:
+        import traceback
+        queue.put((rank, "error", traceback.format_exc()))
+        raise
+
+
+def _solid_worker(rank, world, port, queue):
+    """The solid shape's integration at every `replicate`, and an Overflow retry loop like dist.mass_partial's whose first
+    try replicates more levels than the repeat: this rank's results go to the parent, which compares."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    mtape, box_a, mlevels, _ = _setup_solid()
+    from codecad_amd import dist
+    assert dist.init(backend="gloo") == (rank, world)
+    capacities = [800] * (len(mlevels) - 1)
+    sweep = {}
+    for k in range(len(mlevels)):
+        details = {}
+        got, ambiguous = _integrate_pipeline(mtape, box_a, mlevels, capacities, replicate=k, details=details)
+        sweep[k] = (got.tolist(), ambiguous, details["replicate"])
+    # the retry: first capacities of one row overflow; the limit is such that they replicate every non-leaf level and the
+    # grown ones (+16 rows at least) fewer -- nothing of the first try may reach the result
+    limit, capacities, tries = 27 * 8, [1] * (len(mlevels) - 1), []
+    while True:
+        tries.append(dist.MassPipeline.replicated(mlevels, capacities, limit))
+        try:
+            retried, _ = _integrate_pipeline(mtape, box_a, mlevels, capacities, replicate=tries[-1])
+            break
+        except dist.Overflow as err:
+            capacities = dist.grown_capacities(err.needed, capacities)
+    queue.put((rank, sweep, retried.tolist(), tries))
+    torch.distributed.barrier()
+    torch.distributed.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_replicated_levels_of_a_solid_count_once(world):
+    """World 2 and 3 (uneven slices, owners mod 3) on a shape whose coarse levels hold inside cells: at every `replicate`
+    the integrals are the single-rank ones -- a replicated level summed on every rank would add its inside volume once per
+    extra rank -- and so are the per-level ambiguous counts; a first try that overflows leaves nothing behind."""
+    mtape, box_a, mlevels, extent = _setup_solid()
+    for k in ("RANK", "WORLD_SIZE"):
+        os.environ.pop(k, None)
+    assert len(mlevels) >= 3
+    single = _integrate(mtape, box_a, mlevels).tolist()
+    details = {}
+    piped, ambiguous = _integrate_pipeline(mtape, box_a, mlevels, [800] * (len(mlevels) - 1), details=details)
+    assert _same_integrals(piped.tolist(), single, extent)
+    # what makes the test mean something: level 0 (and level 1) contain solid material
+    assert details["levels"][0][0] > 0 and details["levels"][1][0] > 0, details["levels"]
+
+    ctx = mp.get_context("spawn")
+    queue = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_guard, args=(_solid_worker, r, world, port, queue)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        got = {}
+        for _ in range(world):
+            item = queue.get(timeout=180)
+            assert item[1] != "error", "rank %d failed:\n%s" % (item[0], item[2])
+            got[item[0]] = item[1:]
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.kill()
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    for rank, (sweep, retried, tries) in sorted(got.items()):
+        assert sorted(sweep) == list(range(len(mlevels)))
+        for k, (integrals, ambiguous_k, replicate) in sweep.items():
+            assert replicate == k, (rank, k, replicate)
+            assert _same_integrals(integrals, single, extent), (world, rank, k, integrals, single)
+            assert ambiguous_k == ambiguous, (world, rank, k)
+        assert len(tries) >= 2 and tries[0] == len(mlevels) - 1 and tries[-1] < tries[0], tries
+        assert _same_integrals(retried, single, extent), (world, rank, tries, retried, single)
+
+
+def test_public_mass_hierarchy_replicates_solid_levels():
+    """The path the solid-shape tests are about is live: with the capacities dist.mass_properties starts from, grid 8
+    replicates two levels of sphere_plus_box (the level before the owned one is summed by rank 0 alone) -- and at 0.5,
+    the device test's case, that level holds inside cells (the oracle's classification of level 0)."""
+    import math
+    import oracle
+    from codecad_amd import dist, examples, nodes
+    shape = examples.sphere_plus_box()
+    box = shape.bounding_box()
+    for resolution in (1.0, 0.5):
+        levels, capacities = dist.mass_hierarchy(box, resolution, 8)
+        assert len(levels) == 3 and dist.MassPipeline.replicated(levels, capacities) >= 2, (resolution, capacities)
+    s, dims = levels[0]
+    shifted = np.array([box.a.x + s / 2, box.a.y + s / 2, box.a.z + s / 2], dtype=np.float32)
+    sums, _, _ = oracle.mass_properties(nodes.make_program(shape), shifted, np.float32(s), np.float32(s * math.sqrt(3) / 2), dims)
+    assert int(sums[9]) > 0, sums
 
 
 def test_pipeline_single_rank_and_slice_rule():

@@ -2,7 +2,8 @@
 """Rehearsal of the multi-GPU library paths with several ranks sharing ONE GPU (gloo host staging):
     CODECAD_AMD_DIST_BACKEND=gloo python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 \
         --master-port 29512 tools/rehearse_dist.py
-Each rank runs dist.mass_properties on its slices; rank 0 compares with the single-GPU driver."""
+Each rank runs dist.mass_properties on its slices; rank 0 compares with the single-GPU driver.  The solid sphere_plus_box
+at 0.5, grid 8 replicates two levels with inside cells at level 0: a level counted on more than one rank shows in its volume."""
 import os
 import sys
 
@@ -12,6 +13,15 @@ import codecad_amd as cc  # noqa: E402
 from codecad_amd import dist  # noqa: E402
 
 rank, world = dist.init()
+solid = cc.examples.sphere_plus_box()
+got = dist.mass_properties(solid, 0.5, grid_size=8)
+dist.barrier()
+if rank == 0:
+    want = cc.mass_properties(solid, 0.5, grid_size=8)
+    print("ranks %d: sphere_plus_box volume %.6f (single GPU %.6f)" % (world, got.volume, want.volume))
+    assert abs(got.volume - want.volume) <= 1e-13 * want.volume
+    assert np.allclose(got.inertia_tensor, want.inertia_tensor, rtol=1e-11, atol=1e-11 * np.abs(want.inertia_tensor).max())
+    assert abs(got.centroid - want.centroid) < 1e-14 * 130
 shape = cc.examples.sponge(3)
 got = dist.mass_properties(shape, 1.0 / 243, grid_size=9)
 dist.barrier()

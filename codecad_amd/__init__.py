@@ -7,7 +7,8 @@
 Public layout mirrors the reference package (reference codecad/__init__.py:1-11): `shapes`,
 `util`, `nodes`, `hip_util` (in place of `cl_util`), `grid_eval`, `subdivision`,
 `mass_properties`, `assembly` (assemblies.py) and the renderers the package has (`rendering`);
-`interference(asm, resolution)` finds the overlapping instances of an assembly on the device.
+`interference(asm, resolution)` finds the overlapping instances of an assembly on the device, and
+`clearance(asm, resolution, min_gap)` the pairs closer than a gap, with how close and where (clearance.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -23,6 +24,8 @@ from . import rendering  # noqa: F401
 from . import assemblies  # noqa: F401
 from .assemblies import assembly  # noqa: F401
 from .interference import interference, InterferenceReport  # noqa: F401
+from .clearance import clearance, ClearanceReport, NearMiss  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
-           "MassProperties", "examples", "assembly", "interference", "InterferenceReport"]
+           "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
+           "ClearanceReport", "NearMiss"]

@@ -194,6 +194,7 @@ int ensure_attrs()
     if ((rc = ensure_attrs_n<2>())) return rc;
     HU_HIP(hu_render::allow_big_lds(kMaxLds));   // the ray caster and the bitmap kernels (render.hip)
     HU_HIP(hu_interference::allow_big_lds(kMaxLds));   // (interference.hip)
+    HU_HIP(hu_clearance::allow_big_lds(kMaxLds));      // (clearance.hip)
     done_for_device = dev;
     return HU_OK;
 }
@@ -1186,6 +1187,112 @@ int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distanc
     a.child_side = 1u;
     a.pairs = static_cast<hu_interference::PairAcc*>(pairs_dev);
     return interference_launch(true, distance_only_kernel, lane_bytes, a, stream);
+}
+
+namespace {
+
+// workgroup size for a clearance launch, as interference_launch sizes it, but with the leaf's and the witness's w area
+// (4 bytes per instance and lane, clearance.hip) counted with the register file against the same 48 KiB
+int clearance_launch(hu_clearance::Kernel kernel, int distance_only_kernel, uint32_t lane_bytes, hu_clearance::Args& a, void* stream)
+{
+    const size_t per_lane = (size_t)lane_bytes + (kernel == hu_clearance::kCells ? 0u : 4u * a.n_instances);
+    uint32_t block = 256;
+    while (block > 64u && per_lane * block > 48 * 1024) block >>= 1;
+    const size_t regfile = (size_t)lane_bytes * block, lds = per_lane * block + kScratchBytes;
+    if (lds > kMaxLds)
+        return fail(HU_ERR_UNSUPPORTED, "an instance keeps more values live than fit the 160 KiB LDS register file");
+    int rc;
+    if ((rc = ensure_attrs())) return rc;
+    a.scratch_offset = (uint32_t)regfile;
+    const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
+    if (blocks == 0) return HU_OK;
+    if (blocks > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
+    HU_HIP(hu_clearance::level(kernel, distance_only_kernel != 0, a, (uint32_t)blocks, block, lds, (hipStream_t)stream));
+    return HU_OK;
+}
+
+int clearance_args(const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev,
+                   const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+                   uint64_t* evaluations_dev, hu_clearance::Args& a)
+{
+    if (!table_dev || !windows_dev || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
+        return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "1..64 instances");
+    for (int i = 0; i < 3; ++i)   // (the witness packs an index into 16 bits per axis)
+        if (dims[i] == 0 || dims[i] > 65536u) return fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (!std::isfinite(step) || step < 0.0f) return fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    std::memset(&a, 0, sizeof(a));
+    a.table = static_cast<const hu_interference::InstanceRec*>(table_dev);
+    a.windows = windows_dev;
+    a.n_instances = n;
+    a.parents = static_cast<const uint4*>(parents_dev);
+    a.n_parents_dev = n_parents_dev;
+    a.max_parents = max_parents;
+    for (int i = 0; i < 3; ++i) {
+        a.dims[i] = dims[i];
+        a.corner[i] = corner[i];
+    }
+    a.step = step;
+    a.evaluations = reinterpret_cast<unsigned long long*>(evaluations_dev);
+    return HU_OK;
+}
+
+int clearance_finest(hu_clearance::Kernel kernel, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                     const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                     const uint32_t dims[3], const float corner[3], float step, float t, void* pairs_dev,
+                     uint64_t* evaluations_dev, void* stream)
+{
+    hu_clearance::Args a;
+    int rc;
+    if ((rc = clearance_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+        return rc;
+    if (!pairs_dev) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (!std::isfinite(t) || t < 0.0f) return fail(HU_ERR_BAD_ARG, "t must be finite and not negative");
+    a.child_side = 1u;
+    a.t = t;
+    a.pairs = static_cast<hu_clearance::PairAcc*>(pairs_dev);
+    return clearance_launch(kernel, distance_only_kernel, lane_bytes, a, stream);
+}
+
+}  // namespace
+
+int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                                uint32_t max_parents, uint32_t child_side, const uint32_t dims[3], const float corner[3],
+                                float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                uint64_t* evaluations_dev, void* stream)
+{
+    hu_clearance::Args a;
+    int rc;
+    if ((rc = clearance_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+        return rc;
+    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (child_side < 4u || child_side > 16384u) return fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
+    if (!std::isfinite(thr) || thr < 0.0f) return fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    a.child_side = child_side;
+    a.thr = thr;
+    a.counter = counter_dev;
+    a.children = static_cast<uint4*>(children_dev);
+    a.capacity = capacity;
+    return clearance_launch(hu_clearance::kCells, distance_only_kernel, lane_bytes, a, stream);
+}
+
+int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                               const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                               uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
+                               void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+{
+    return clearance_finest(hu_clearance::kLeaf, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
+                            n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+}
+
+int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                  const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                                  uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
+                                  void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+{
+    return clearance_finest(hu_clearance::kWitness, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
+                            n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
 }
 
 int hu_ray_caster(hu_tape t, const float origin[4], const float forward[4], const float up[4], const float right[4],

@@ -1,0 +1,67 @@
+// codecad_amd/csrc/instance_cells.hpp -- what the kernels over the instances of an assembly share
+// (interference.hip, clearance.hip): a wavefront's cell row, the table of the instances' programs and the box of a lane mask.
+//
+// A CELL is a cube of 4^k lattice samples, a 16-byte row {x0 | y0 << 16, z0, mask lo, mask hi}: its first sample's indices
+// and the 64-bit mask of the instances still candidates in it.  One wavefront takes one cell, lane = 16 x + 4 y + z of its
+// 4 x 4 x 4 parts.  The launch arguments A of every such kernel have `parents`, `n_parents_dev`, `max_parents` and `table`.
+#pragma once
+
+#include "kernels.hpp"
+
+namespace hu_cells {
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the row of the cell wavefront `w` of this workgroup takes, or `have` = false past the list's end (wave-uniform)
+struct CellRow {
+    uint32_t x0, y0, z0;
+    uint64_t mask;
+    bool have;
+};
+template <class A> __device__ __forceinline__ CellRow cell_row(const A& a)
+{
+    const uint32_t listed = *a.n_parents_dev, n = listed < a.max_parents ? listed : a.max_parents;   // (an overflowed list holds max_parents)
+    const uint32_t p = uniform(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    CellRow r{0u, 0u, 0u, 0ull, p < n};
+    if (r.have) {
+        const uint4 row = a.parents[p];
+        r.x0 = uniform(row.x & 0xffffu);
+        r.y0 = uniform(row.x >> 16);
+        r.z0 = uniform(row.y);
+        r.mask = ((uint64_t)uniform(row.w) << 32) | uniform(row.z);
+    }
+    return r;
+}
+
+// A pointer read from the device table is a plain value to the compiler: it cannot tell that it points to global memory
+// this kernel never writes, so the interpreter would fetch the records through it with vector (flat) loads.  Made
+// wave-uniform and cast through the constant address space, every load through it is a scalar load, as in the kernels
+// that take their program as a kernel argument.
+template <class T> __device__ __forceinline__ const T* constant_uniform(const T* p)
+{
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint64_t u = ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v);
+    return (const T*)(const __attribute__((address_space(4))) T*)u;
+}
+
+// distance of instance `n` (wave-uniform) at p: the one interpreter call site of a kernel
+template <bool DO, class A>
+__device__ __forceinline__ float instance_dist(const A& a, uint32_t n, float px, float py, float pz, void* lds)
+{
+    const auto r = a.table[n];
+    return sdfk::InterpEval<DO>{constant_uniform(r.prog), constant_uniform(r.extra), uniform(r.n4)}.dist(px, py, pz, lds);
+}
+
+// min and max of the lane coordinates set in a 64-lane mask (lane = 16 x + 4 y + z), per axis
+__device__ __forceinline__ void mask_box(uint64_t m, uint32_t (&lo)[3], uint32_t (&hi)[3])
+{
+    const uint32_t f16 = (uint32_t)((m | (m >> 16) | (m >> 32) | (m >> 48)) & 0xffffull);   // (y, z) of any x
+    uint32_t ys = 0u;
+    for (uint32_t yy = 0; yy < 4u; ++yy) ys |= ((f16 >> (4u * yy)) & 0xfu) ? 1u << yy : 0u;
+    const uint32_t zs = (f16 | (f16 >> 4) | (f16 >> 8) | (f16 >> 12)) & 0xfu;
+    lo[0] = (uint32_t)__builtin_ctzll(m) >> 4;  hi[0] = (63u - (uint32_t)__builtin_clzll(m)) >> 4;
+    lo[1] = (uint32_t)__builtin_ctz(ys);        hi[1] = 31u - (uint32_t)__builtin_clz(ys);
+    lo[2] = (uint32_t)__builtin_ctz(zs);        hi[2] = 31u - (uint32_t)__builtin_clz(zs);
+}
+
+}  // namespace hu_cells

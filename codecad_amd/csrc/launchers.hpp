@@ -1,4 +1,4 @@
-// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip and interference.hip.
+// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip, interference.hip and clearance.hip.
 //
 // Translation units that hold kernels (hip_util/builder.py lists the flags of each):
 //   hip_util.hip  the dense / leaf-block / classification kernels over the tape interpreter, built with
@@ -8,6 +8,7 @@
 //                 value in a divergent loop (csrc/exchange.hip), so it stays confined to the kernels that are
 //                 nothing but the interpreter's wave-uniform loop around branch-free ops;
 //   interference.hip  the interference check between the instances of an assembly, built without it as well;
+//   clearance.hip     the clearance (near-miss) check between those instances, built without it as well;
 // Each function enqueues one launch and returns hipGetLastError().
 #pragma once
 
@@ -72,3 +73,46 @@ hipError_t allow_big_lds(size_t bytes);
 hipError_t level(bool leaf, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 
 }  // namespace hu_interference
+
+namespace hu_clearance {
+
+// the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j], over the pair's NEAR samples (in both
+// instances' windows, w_i < t and w_j < t): their count and index sums and box as in hu_interference::PairAcc, the order
+// key of the least v = max(w_i, w_j) (starts at 0xffffffff, clearance.hip order_key) and the witness, the least
+// x << 32 | y << 16 | z of the near samples whose v is that least one (starts at ~0)
+struct PairAcc {
+    unsigned long long sums[4];   // count, sum x, sum y, sum z
+    unsigned long long witness;
+    uint32_t lo[3], hi[3];
+    uint32_t key;
+    uint32_t pad;
+};
+static_assert(sizeof(PairAcc) == 72, "clearance.py reads 72-byte accumulators");
+
+struct Args {
+    const hu_interference::InstanceRec* table;
+    const uint32_t* windows;         // n_instances x {lo x, y, z, hi x, y, z}: the samples an instance may be near at
+    uint32_t n_instances;
+    const uint4* parents;            // rows {x0 | y0 << 16, z0, mask lo, mask hi} after the list's header row
+    const uint32_t* n_parents_dev;   // word 0 of the parents' header
+    uint32_t max_parents;            // the parents' capacity (the launch is sized for it)
+    uint32_t child_side;             // cells: side of a child cell in samples (leaf, witness: 1)
+    uint32_t dims[3];
+    float corner[3], step;
+    float thr;                       // cells: a candidate whose distance at a child's centre is >= thr leaves the child
+    float t;                         // leaf, witness: near means w < t
+    uint32_t* counter;               // cells: word 0 of the children's header
+    uint4* children;                 // cells: the children's rows
+    uint32_t capacity;
+    PairAcc* pairs;                  // leaf, witness
+    unsigned long long* evaluations; // per-instance sample evaluations, added up per wavefront
+    uint32_t scratch_offset;         // bytes of LDS taken by the register file (cells: the compaction's scratch follows;
+                                     // leaf, witness: the w of every instance, 256 bytes per instance and wavefront)
+};
+
+enum Kernel { kCells, kLeaf, kWitness };
+
+hipError_t allow_big_lds(size_t bytes);
+hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
+
+}  // namespace hu_clearance

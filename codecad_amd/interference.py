@@ -69,12 +69,13 @@ class InterferenceReport(collections.namedtuple("InterferenceReport",
     __slots__ = ()
 
 
-def lattice(instances, resolution):
-    """(corner float32[3], step float32, dims int64[3]) of the lattice over the union of the instances' boxes."""
+def lattice(instances, resolution, grow=0.0):
+    """(corner float32[3], step float32, dims int64[3]) of the lattice over the union of the instances' boxes, each grown
+    by `grow` on every side (in float64; clearance.py grows them by half its gap)."""
     step = numpy.float32(resolution)
     boxes = [i.shape().bounding_box() for i in instances]
-    a = numpy.array([min(b.a[k] for b in boxes) for k in range(3)], dtype=numpy.float64)
-    b = numpy.array([max(b.b[k] for b in boxes) for k in range(3)], dtype=numpy.float64)
+    a = numpy.array([min(b.a[k] for b in boxes) for k in range(3)], dtype=numpy.float64) - grow
+    b = numpy.array([max(b.b[k] for b in boxes) for k in range(3)], dtype=numpy.float64) + grow
     if not (numpy.isfinite(a).all() and numpy.isfinite(b).all()):
         raise ValueError("interference needs instances with finite bounding boxes")
     dims = numpy.maximum(1, numpy.ceil((b - a) / float(step))).astype(numpy.int64)
@@ -103,16 +104,25 @@ def _top_side(dims):
     return side
 
 
-def _top_cells(instances, corner, step, dims, side):
-    """Rows of the top level: cells of `side` samples that two instances' boxes (grown by a step) reach."""
-    n_cells = -(-dims // side)
-    masks = numpy.zeros(tuple(int(n) for n in n_cells), dtype=numpy.uint64)
+def _windows(instances, corner, step, dims, grow=0.0):
+    """int64[n, 2, 3]: per instance, the first and last lattice index per axis of its box grown by `grow` and a step,
+    clipped to the lattice."""
+    out = numpy.zeros((len(instances), 2, 3), dtype=numpy.int64)
     for n, inst in enumerate(instances):
         box = inst.shape().bounding_box()
-        lo = numpy.floor((numpy.array(tuple(box.a)) - corner - step) / step)
-        hi = numpy.ceil((numpy.array(tuple(box.b)) - corner + step) / step)
-        lo = numpy.clip(lo, 0, dims - 1).astype(numpy.int64) // side
-        hi = numpy.clip(hi, 0, dims - 1).astype(numpy.int64) // side
+        lo = numpy.floor((numpy.array(tuple(box.a)) - grow - corner - step) / step)
+        hi = numpy.ceil((numpy.array(tuple(box.b)) + grow - corner + step) / step)
+        out[n, 0] = numpy.clip(lo, 0, dims - 1)
+        out[n, 1] = numpy.clip(hi, 0, dims - 1)
+    return out
+
+
+def _cell_rows(windows, dims, side):
+    """Rows of the top level: cells of `side` samples that two windows or more reach."""
+    n_cells = -(-dims // side)
+    masks = numpy.zeros(tuple(int(n) for n in n_cells), dtype=numpy.uint64)
+    for n, (lo, hi) in enumerate(windows):
+        lo, hi = lo // side, hi // side
         masks[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1] |= numpy.uint64(1 << n)
     bits = numpy.unpackbits(masks.view(numpy.uint8).reshape(masks.shape + (8,)), axis=-1).sum(axis=-1)
     idx = numpy.argwhere(bits >= 2)
@@ -124,6 +134,11 @@ def _top_cells(instances, corner, step, dims, side):
         rows[:, 2] = (m & numpy.uint64(0xffffffff)).astype(numpy.uint32)
         rows[:, 3] = (m >> numpy.uint64(32)).astype(numpy.uint32)
     return rows
+
+
+def _top_cells(instances, corner, step, dims, side):
+    """Rows of the top level: cells of `side` samples that two instances' boxes (grown by a step) reach."""
+    return _cell_rows(_windows(instances, corner, step, dims), dims, side)
 
 
 def _instance_tape(instance):
@@ -145,6 +160,33 @@ def _instance_tape(instance):
     while len(cache) > _TAPES_PER_PART:
         cache.popitem(last=False)                 # (the tape is freed with its last reference)
     return tape
+
+
+def _device_table(instances, queue):
+    """(device table of the instances' uploaded tapes, distance_only, lane_bytes): hu_interference_table."""
+    tapes = [_instance_tape(i) for i in instances]
+    n = len(tapes)
+    handles = (ctypes.c_void_p * n)(*(t.device_ptr for t in tapes))
+    host_table = numpy.zeros(n * _TABLE_RECORD, dtype=numpy.uint8)
+    distance_only, lane_bytes = ctypes.c_int(0), ctypes.c_uint32(0)
+    check(hip_manager.lib.hu_interference_table(handles, n, host_table.ctypes.data, host_table.nbytes,
+                                                ctypes.byref(distance_only), ctypes.byref(lane_bytes)), "hu_interference_table")
+    table = hip_util.Buffer(numpy.uint8, (host_table.size,), queue=queue)
+    table.enqueue_write(host_table)
+    return table, distance_only.value, lane_bytes.value
+
+
+def _levels(side, n_top, initial_capacity):
+    """(sides of the cells of every level above the finest one, the first capacity of every level's child list)."""
+    sides = []
+    s = side
+    while s > 4:
+        sides.append(s)
+        s //= 4
+    capacities = subdivision.first_capacities([64] * len(sides), n_top=n_top, row_bytes=_ROW)
+    if initial_capacity is not None:
+        capacities = [subdivision.checked_capacity(min(c, max(1, int(initial_capacity)))) for c in capacities]
+    return sides, capacities
 
 
 def _traverse(table, n, distance_only, lane_bytes, top, sides, corner, step, dims, capacities, queue):
@@ -210,29 +252,13 @@ def interference(asm, resolution, initial_capacity=None):
         return empty
 
     queue = hip_manager.queue
-    lib = hip_manager.lib
-    tapes = [_instance_tape(i) for i in instances]
-    n = len(tapes)
-    handles = (ctypes.c_void_p * n)(*(t.device_ptr for t in tapes))
-    host_table = numpy.zeros(n * _TABLE_RECORD, dtype=numpy.uint8)
-    distance_only, lane_bytes = ctypes.c_int(0), ctypes.c_uint32(0)
-    check(lib.hu_interference_table(handles, n, host_table.ctypes.data, host_table.nbytes, ctypes.byref(distance_only),
-                                    ctypes.byref(lane_bytes)), "hu_interference_table")
-    table = hip_util.Buffer(numpy.uint8, (host_table.size,), queue=queue)
-    table.enqueue_write(host_table)
-
-    sides = []
-    s = side
-    while s > 4:
-        sides.append(s)
-        s //= 4
-    capacities = subdivision.first_capacities([64] * len(sides), n_top=len(top), row_bytes=_ROW)
-    if initial_capacity is not None:
-        capacities = [subdivision.checked_capacity(min(c, max(1, int(initial_capacity)))) for c in capacities]
+    n = len(instances)
+    table, distance_only, lane_bytes = _device_table(instances, queue)
+    sides, capacities = _levels(side, len(top), initial_capacity)
     traversals = 0
     while True:
         traversals += 1
-        counts, evaluations, acc = _traverse(table, n, distance_only.value, lane_bytes.value, top, sides, corner, step, dims,
+        counts, evaluations, acc = _traverse(table, n, distance_only, lane_bytes, top, sides, corner, step, dims,
                                              capacities, queue)
         if all(k <= c for k, c in zip(counts, capacities)):
             break

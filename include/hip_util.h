@@ -223,6 +223,35 @@ int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distanc
                                   const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
                                   uint64_t* evaluations_dev, void* stream);
 
+/* ---- clearance (near misses) between the instances of an assembly (codecad_amd/clearance.py) ----
+ * The interference traversal with a threshold: the same table (hu_interference_table), cell lists and lattice.  Each
+ * also takes windows_dev, n x 6 uint32 {lo x, y, z, hi x, y, z}: the lattice indices at which instance k may be near,
+ * inclusive.  A sample is near the pair (i, j) when it lies in both windows and w_i < t, w_j < t (strictly); there
+ * v = max(w_i, w_j).  dims at most 65536 per axis; step, t and thr finite and not negative.
+ * hu_clearance_cells_indirect: as hu_interference_cells_indirect; a candidate also leaves a child whose index range
+ *   misses its window.
+ * hu_clearance_leaf_indirect: a cell of 4^3 samples per parent row; every pair (i < j) of candidates with near samples
+ *   adds to pairs_dev[i * n + j] (72 bytes: uint64 count, x, y, z index sums; uint64 witness; uint32 min x, y, z; uint32
+ *   max x, y, z; uint32 key of the least v; 4 bytes unused).  The caller starts min and key at 0xffffffff and the
+ *   witness at ~0.  The key of v is its float32 bits b (of +0 for either zero) mapped to ~b when the sign is set, else
+ *   b | 0x80000000, so that keys order as the values do.
+ * hu_clearance_witness_indirect: after the leaf launch, over the same list and accumulators: each pair's witness
+ *   becomes the least x << 32 | y << 16 | z of its near samples whose v has the pair's key.
+ * All read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
+int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                                uint32_t max_parents, uint32_t child_side, const uint32_t dims[3], const float corner[3],
+                                float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                uint64_t* evaluations_dev, void* stream);
+int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                               const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                               uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
+                               void* pairs_dev, uint64_t* evaluations_dev, void* stream);
+int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                                  const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                                  uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
+                                  void* pairs_dev, uint64_t* evaluations_dev, void* stream);
+
 /* ---- renderers on the same evaluate() -------------------- */
 /* rendering/ray_caster.cl:146-159, launched by rendering/ray_caster.py:93-110 with global size
  * (width, height).  origin/forward/up/right: float4 as the reference passes them (forward already

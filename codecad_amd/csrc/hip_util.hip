@@ -264,7 +264,8 @@ struct SpecKernels {
     hipFunction_t box_masks = nullptr;   // k_box_masks (box pruning), part of every family that launches over boxes
     bool deferred = false;   // the module was generated with deferred directions (specialise.hpp): dense launches use bricks
     double coord_limit = 0.0;   // a launch whose sample coordinates all stay below this sets sdf::kFlagInRange (specialise.hpp)
-    int tabs[6] = {0, 0, 0, 0, 0, 0};   // columns of a box's tables: x, y, z, xy, xz, yz (specialise.hpp)
+    int tabs[6] = {0, 0, 0, 0, 0, 0};   // columns of a box's tables: x, y, z, xy, xz, yz (specialise.hpp), float4 walks
+    int dtabs[6] = {0, 0, 0, 0, 0, 0};  // ... of the distance walks' tables (kernels.hpp box_tables<true>)
     int prune_words = 0;     // 32-bit words of a box's pruning mask (0: nothing to prune in this tape)
     int prune_bits = 0;
     bool prune_all = false;  // the float4 code is guarded too (else only the distance walks: float4 launches skip the mask kernel)
@@ -314,10 +315,11 @@ std::string generate_source(const hu_tape_s* t, sdf::SpecMeta* meta = nullptr)
     return sdf::specialised_source(t->program, defer_directions(), meta);
 }
 // LDS bytes of a box's tables (sdf::BoxTabs: 16 entries per single-axis column; pair columns of 16 rows of 17 / 24 floats)
-uint32_t box_table_bytes(const SpecKernels* k)
+// (dist: the layout of the distance walks -- leaf blocks and grids of the float layout, classification)
+uint32_t box_table_bytes(const SpecKernels* k, bool dist)
 {
-    return (uint32_t)((k->tabs[0] + k->tabs[1] + k->tabs[2]) * sdf::BoxTabs::kAxis + (k->tabs[3] + k->tabs[4]) * sdf::BoxTabs::kPairX +
-                      k->tabs[5] * sdf::BoxTabs::kPairYZ) * 4u;
+    const int* n = dist ? k->dtabs : k->tabs;
+    return (uint32_t)((n[0] + n[1] + n[2]) * sdf::BoxTabs::kAxis + (n[3] + n[4]) * sdf::BoxTabs::kPairX + n[5] * sdf::BoxTabs::kPairYZ) * 4u;
 }
 
 void keep_programs(hu_tape_s* t, const sdf::DecodedTape& d)
@@ -672,7 +674,7 @@ int hu_grid_eval_slab(hu_tape t, const float corner[4], float step, const uint32
             } else {
                 void* args[] = {&ev, &cx, &cy, &cz, &step, &sx, &sy, &sz, &xs, &n_cells, &boxes, &o, &masks};
                 HU_HIP(hipModuleLaunchKernel(ragged ? t->spec->dense_ragged[layout] : t->spec->dense[layout], grid, 1, 1, block, 1, 1,
-                                             boxes ? box_table_bytes(t->spec) : idle_lds, (hipStream_t)stream, args, nullptr));
+                                             boxes ? box_table_bytes(t->spec, layout != 0) : idle_lds, (hipStream_t)stream, args, nullptr));
             }
             done += nx;
         }
@@ -773,7 +775,7 @@ static int grid_eval_blocks_impl(hu_tape t, const int32_t* blocks_dev, uint32_t 
             } else {
                 void* args[] = {&ev, &b, &n_dev, &first, &chunks, &bricks, &res, &ox, &oy, &oz, &step, &sx, &sy, &sz, &out_dev, &masks};
                 HU_HIP(hipModuleLaunchKernel(ragged ? t->spec->blocks_ragged[layout] : t->spec->blocks[layout], chunks * count, 1, 1, kSpecBlock, 1, 1,
-                                             bricks ? box_table_bytes(t->spec) : 0u, (hipStream_t)stream, args, nullptr));
+                                             bricks ? box_table_bytes(t->spec, layout != 0) : 0u, (hipStream_t)stream, args, nullptr));
             }
         }
         return HU_OK;
@@ -858,7 +860,7 @@ int launch_classify(hu_tape t, ClassifyArgs& a, uint32_t n_parents, const uint32
         if (t->spec->deferred && cells > 256u && bxn * byn * bzn * n_parents >= enough && boxes_worthwhile(dims[0], dims[1], dims[2])) {   // (any extents: the rims of a box are predicated; not where boxes would be mostly padding: 2D)
             a.boxes = ((uint32_t)byn << 16) | (uint32_t)bzn;
             a.chunks = (uint32_t)(bxn * byn * bzn);
-            a.scratch_offset = box_table_bytes(t->spec);
+            a.scratch_offset = box_table_bytes(t->spec, true);
         }
         // (mass-property parents are fp64 corners on the device: their magnitude is not the host's to know)
         const double extent = (double)a.step * (double)std::max(dims[0], std::max(dims[1], dims[2]));
@@ -1844,6 +1846,7 @@ static int load_specialised(hu_tape t, const SpecImage& img, uint32_t set, hipEr
     k->prune_bits = meta.prune_bits;
     k->prune_all = meta.prune_all;
     std::memcpy(k->tabs, meta.tabs, sizeof k->tabs);
+    std::memcpy(k->dtabs, meta.dtabs, sizeof k->dtabs);
     return HU_OK;
 }
 

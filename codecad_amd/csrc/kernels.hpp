@@ -231,12 +231,16 @@ template <class E> __device__ __forceinline__ float walk_coordinate(float v)
 struct BoxTables {
     sdf::lds_float *x, *y, *z, *xy, *xz, *yz;
 };
-template <class E, class PR>
+// DIST: the tables of the distance walks (dist_hoisted_x after hoist_d: leaf blocks, distance grids, classification), which
+// have a layout of their own -- what those walks read, the folded chains among it (specialise.hpp fold_chains) --; else the
+// float4 walks' (eval_hoisted_x after hoist_x)
+template <bool DIST, class E, class PR>
 __device__ __forceinline__ BoxTables box_tables(const E& ev, float4* lds, float cx, float cy, float cz, float step, uint32_t xs0,
                                                 uint32_t x0, uint32_t y0, uint32_t z0, uint32_t nx, uint32_t ny, uint32_t nz, const PR& pr)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr int NX = E::kTabXX, NY = E::kTabXY, NZ = E::kTabXZ, NXY = E::kPairXY, NXZ = E::kPairXZ, NYZ = E::kPairYZ;
+    constexpr int NX = DIST ? E::kDTabXX : E::kTabXX, NY = DIST ? E::kDTabXY : E::kTabXY, NZ = DIST ? E::kDTabXZ : E::kTabXZ;
+    constexpr int NXY = DIST ? E::kDPairXY : E::kPairXY, NXZ = DIST ? E::kDPairXZ : E::kPairXZ, NYZ = DIST ? E::kDPairYZ : E::kPairYZ;
     using Tabs = sdf::BoxTabs;
     sdf::lds_float* const tx = (sdf::lds_float*)lds;
     sdf::lds_float* const ty = tx + NX * Tabs::kAxis;
@@ -247,13 +251,22 @@ __device__ __forceinline__ BoxTables box_tables(const E& ev, float4* lds, float 
     if constexpr (NX + NY + NZ > 0) {
         if (wave == 0u) {
             if constexpr (NX > 0)
-                if (lane < nx) ev.template tab_x_x<Tabs::kAxis>(sample(cx, step, xs0 + x0 + lane), tx + lane);
+                if (lane < nx) {
+                    if constexpr (DIST) ev.template tab_d_x<Tabs::kAxis>(sample(cx, step, xs0 + x0 + lane), tx + lane);
+                    else ev.template tab_x_x<Tabs::kAxis>(sample(cx, step, xs0 + x0 + lane), tx + lane);
+                }
         } else if (wave == 1u) {
             if constexpr (NY > 0)
-                if (lane < ny) ev.template tab_x_y<Tabs::kAxis>(sample(cy, step, y0 + lane), ty + lane);
+                if (lane < ny) {
+                    if constexpr (DIST) ev.template tab_d_y<Tabs::kAxis>(sample(cy, step, y0 + lane), ty + lane);
+                    else ev.template tab_x_y<Tabs::kAxis>(sample(cy, step, y0 + lane), ty + lane);
+                }
         } else if (wave == 2u) {
             if constexpr (NZ > 0)
-                if (lane < nz) ev.template tab_x_z<Tabs::kAxis>(sample(cz, step, z0 + lane), tz + lane);
+                if (lane < nz) {
+                    if constexpr (DIST) ev.template tab_d_z<Tabs::kAxis>(sample(cz, step, z0 + lane), tz + lane);
+                    else ev.template tab_x_z<Tabs::kAxis>(sample(cz, step, z0 + lane), tz + lane);
+                }
         }
         __syncthreads();
     }
@@ -261,17 +274,23 @@ __device__ __forceinline__ BoxTables box_tables(const E& ev, float4* lds, float 
         // one entry per lane: (row, column) = (thread / 16, thread % 16); the column is the table's fastest index
         const uint32_t r = threadIdx.x >> 4, c = threadIdx.x & 15u;
         if constexpr (NXY > 0)
-            if (r < ny && c < nx)
-                ev.template tab_x_xy<Tabs::kPairX>(sample(cx, step, xs0 + x0 + c), sample(cy, step, y0 + r), Tabs{tx + c, ty + r, tz, txy, txz, tyz}, pr,
-                                                   txy + (r * Tabs::kRowX + c));
+            if (r < ny && c < nx) {
+                const Tabs at{tx + c, ty + r, tz, txy, txz, tyz};
+                if constexpr (DIST) ev.template tab_d_xy<Tabs::kPairX>(sample(cx, step, xs0 + x0 + c), sample(cy, step, y0 + r), at, pr, txy + (r * Tabs::kRowX + c));
+                else ev.template tab_x_xy<Tabs::kPairX>(sample(cx, step, xs0 + x0 + c), sample(cy, step, y0 + r), at, pr, txy + (r * Tabs::kRowX + c));
+            }
         if constexpr (NXZ > 0)
-            if (r < nz && c < nx)
-                ev.template tab_x_xz<Tabs::kPairX>(sample(cx, step, xs0 + x0 + c), sample(cz, step, z0 + r), Tabs{tx + c, ty, tz + r, txy, txz, tyz}, pr,
-                                                   txz + (r * Tabs::kRowX + c));
+            if (r < nz && c < nx) {
+                const Tabs at{tx + c, ty, tz + r, txy, txz, tyz};
+                if constexpr (DIST) ev.template tab_d_xz<Tabs::kPairX>(sample(cx, step, xs0 + x0 + c), sample(cz, step, z0 + r), at, pr, txz + (r * Tabs::kRowX + c));
+                else ev.template tab_x_xz<Tabs::kPairX>(sample(cx, step, xs0 + x0 + c), sample(cz, step, z0 + r), at, pr, txz + (r * Tabs::kRowX + c));
+            }
         if constexpr (NYZ > 0)
-            if (r < ny && c < nz)
-                ev.template tab_x_yz<Tabs::kPairYZ>(sample(cy, step, y0 + r), sample(cz, step, z0 + c), Tabs{tx, ty + r, tz + c, txy, txz, tyz}, pr,
-                                                    tyz + (r * Tabs::kRowYZ + c));
+            if (r < ny && c < nz) {
+                const Tabs at{tx, ty + r, tz + c, txy, txz, tyz};
+                if constexpr (DIST) ev.template tab_d_yz<Tabs::kPairYZ>(sample(cy, step, y0 + r), sample(cz, step, z0 + c), at, pr, tyz + (r * Tabs::kRowYZ + c));
+                else ev.template tab_x_yz<Tabs::kPairYZ>(sample(cy, step, y0 + r), sample(cz, step, z0 + c), at, pr, tyz + (r * Tabs::kRowYZ + c));
+            }
         __syncthreads();
     }
     return BoxTables{tx, ty, tz, txy, txz, tyz};
@@ -294,7 +313,7 @@ __device__ __forceinline__ void box_eval(const E& ev, float4* lds, float cx, flo
     const uint32_t nx = min(16u, o.nx - x0), ny = min(16u, sy - y0), nz = min(16u, sz - z0);
     // box pruning: which operands of the tape's selects can win anywhere in this box (k_box_masks ran before this launch)
     const sdf::Prune<E::kPruneWords> pr = sdf::load_prune<E::kPruneWords>(masks, box);
-    const BoxTables t = box_tables(ev, lds, cx, cy, cz, step, xs0, x0, y0, z0, nx, ny, nz, pr);
+    const BoxTables t = box_tables<LAYOUT != 0>(ev, lds, cx, cy, cz, step, xs0, x0, y0, z0, nx, ny, nz, pr);
     sdf::lds_float* const tx = t.x; sdf::lds_float* const ty = t.y; sdf::lds_float* const tz = t.z;
     sdf::lds_float* const txy = t.xy; sdf::lds_float* const txz = t.xz; sdf::lds_float* const tyz = t.yz;
     // The box's (y, z) columns of bricks, at most eight: a wavefront takes column `wave` and the one four on -- the same
@@ -318,7 +337,10 @@ __device__ __forceinline__ void box_eval(const E& ev, float4* lds, float cx, flo
         const float py = sample(cy, step, y0 + yl);
         const bool row_inside = !RAGGED || (z_inside && yl < ny);
         Tabs tb = col;
-        const auto hoisted = ev.hoist_x(py, walk_coordinate<E>(pz), tb, pr);
+        const auto hoisted = [&] {
+            if constexpr (LAYOUT == 0) return ev.hoist_x(py, walk_coordinate<E>(pz), tb, pr);
+            else return ev.hoist_d(py, walk_coordinate<E>(pz), tb, pr);
+        }();
         size_t p = at;
 #pragma unroll 1
         for (uint32_t j = 0; j < bricks_x; ++j) {
@@ -331,7 +353,7 @@ __device__ __forceinline__ void box_eval(const E& ev, float4* lds, float cx, flo
             const T px = pack(xs);
             const float pyb = walk_coordinate<E>(py), pzb = walk_coordinate<E>(pz);
             const auto prb = pr.fresh();
-            if (LAYOUT == 0) {
+            if constexpr (LAYOUT == 0) {
                 const sdf::V4<T> r = ev.eval_hoisted_x(px, pyb, pzb, hoisted, tb, prb);
 #pragma unroll
                 for (int i = 0; i < N; ++i)
@@ -638,7 +660,7 @@ __global__ void __launch_bounds__(256) k_classify(const E ev, const ClassifyArgs
             const uint32_t x0 = qx * 16u, y0 = qy * 16u, z0 = qz * 16u;
             const uint32_t nx = min(16u, a.sx - x0), ny = min(16u, a.sy - y0), nz = min(16u, a.sz - z0);
             const sdf::Prune<E::kPruneWords> pr = sdf::load_prune<E::kPruneWords>(a.masks, blockIdx.x);
-            const BoxTables t = box_tables(ev, lds, cx, cy, cz, a.step, 0u, x0, y0, z0, nx, ny, nz, pr);
+            const BoxTables t = box_tables<true>(ev, lds, cx, cy, cz, a.step, 0u, x0, y0, z0, nx, ny, nz, pr);
             if (MASS) __syncthreads();   // scratch[8..17] zeroed (a tape without tables has no barrier in box_tables)
             const bool nothing_ambiguous = MASS && a.thr == 0.0f;
             const uint64_t below = (1ull << lane) - 1ull;
@@ -704,7 +726,7 @@ __global__ void __launch_bounds__(256) k_classify(const E ev, const ClassifyArgs
                 const bool live = (zl < nz) & (yl < ny);
                 const float py = sample(cy, a.step, y);
                 Tabs tb{t.x + xl, t.y + yl, t.z + zl, t.xy + (yl * Tabs::kRowX + xl), t.xz + (zl * Tabs::kRowX + xl), t.yz + (yl * Tabs::kRowYZ + zl)};
-                const auto hoisted = ev.hoist_x(py, walk_coordinate<E>(pz), tb, pr);
+                const auto hoisted = ev.hoist_d(py, walk_coordinate<E>(pz), tb, pr);
 #pragma unroll 1
                 for (uint32_t j = 0; j < ((nx + 3u) >> 2); ++j) {
                     asm volatile("" ::: "memory");

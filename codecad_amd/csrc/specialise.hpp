@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <numeric>
 #include <sstream>
 #include <string>
@@ -851,6 +852,97 @@ inline PruneInfo analyse_pruning(const Phase1& ph, int min_cost)
     return pi;
 }
 
+// FOLDED CHAINS (round 5), for the distance walks over boxes.  A union of scaled unions -- the sponge's levels: min over l of
+// s_l * min(XY_l, XZ_l, YZ_l) -- reads one pair column per (plane, level) in every brick.  Multiplying by a constant c > 0
+// is monotone and rounds each operand on its own, so min(a, b) * c and min(a * c, b * c) are the same bits (max alike); and
+// min of operands that are no signalling NaN (arithmetic never makes one) does not depend on their order or grouping --
+// the hardware minimum orders -0 below +0 and returns the other operand for a quiet NaN.  So a chain of one kind (min or
+// max), with positive finite scalings between its links, is a set of TERMS (a leaf, then the scalings above it, innermost
+// first), and the terms may be grouped by the sample coordinates their leaf reads: each group is one statement
+// (min over its terms), a pair-table column where the group reads two coordinates -- filled once per pair of samples,
+// where the walk read one column per level.  Not folded: a scaling by zero, a negative or non-finite constant (a mirror);
+// anything box pruning guards or places in a scope (its operands may be dead in a box); the in-place form and the float4
+// walks (their comparisons pick directions in the tape's own order: they keep the tree as it is).
+// -> the root of the distance walk (`root` itself when nothing folds); new statements are appended to ph.e.st
+inline int fold_chains(Phase1& ph, const PruneInfo& pi, int root)
+{
+    Emitter& e = ph.e;
+    auto in_scope0 = [&](int v) { return !pi.guarded(v) && (v >= (int)pi.scope_of.size() || pi.scope_of[v] == 0); };
+    auto kind_of = [&](int v) -> uint8_t {
+        const Stmt& s = e.st[v];
+        if (s.iv == IV_MIN && s.text == "min_x($0, $1)" && in_scope0(v)) return IV_MIN;
+        if (s.iv == IV_MAX && s.text == "max_x($0, $1)" && in_scope0(v)) return IV_MAX;
+        return 0;
+    };
+    auto positive_scale = [&](int v) {
+        const Stmt& s = e.st[v];
+        return s.iv == IV_SCALE && s.ops.size() == 1 && s.iv_a == s.ops[0] && s.iv_c > 0.0f && std::isfinite(s.iv_c) && in_scope0(v) &&
+               s.text == "$0 * " + flit(s.iv_c);
+    };
+    // the chain under v (its kind, 0: none): v itself, or v a positive scaling of one
+    std::function<uint8_t(int)> chain_kind = [&](int v) -> uint8_t {
+        if (const uint8_t k = kind_of(v)) return k;
+        return positive_scale(v) ? chain_kind(e.st[v].ops[0]) : 0;
+    };
+    struct Term { int leaf; std::vector<float> scales; };
+    std::function<void(int, uint8_t, std::vector<float>, std::vector<Term>&)> expand = [&](int v, uint8_t k, std::vector<float> scales, std::vector<Term>& out) {
+        if (kind_of(v) == k) {
+            expand(e.st[v].ops[0], k, scales, out);
+            expand(e.st[v].ops[1], k, scales, out);
+        } else if (positive_scale(v) && chain_kind(e.st[v].ops[0]) == k) {
+            scales.insert(scales.begin(), e.st[v].iv_c);
+            expand(e.st[v].ops[0], k, scales, out);
+        } else out.push_back(Term{v, scales});
+    };
+    std::map<int, int> memo;
+    std::function<int(int)> rewrite = [&](int v) -> int {
+        auto it = memo.find(v);
+        if (it != memo.end()) return it->second;
+        int r = v;
+        const uint8_t k = chain_kind(v);
+        std::vector<Term> terms;
+        if (k) expand(v, k, {}, terms);
+        // grouped by the coordinates the leaf reads, in tape order; worth it where a group of two or more terms is a table
+        // column (reads one or two coordinates): the walk then reads one column where it read one per term
+        std::vector<uint8_t> group_deps;
+        std::vector<std::vector<size_t>> groups;
+        for (size_t i = 0; i < terms.size(); ++i) {
+            const uint8_t d = e.st[terms[i].leaf].deps;
+            const size_t g = std::find(group_deps.begin(), group_deps.end(), d) - group_deps.begin();
+            if (g == group_deps.size()) { group_deps.push_back(d); groups.emplace_back(); }
+            groups[g].push_back(i);
+        }
+        bool worth = false;
+        for (size_t g = 0; g < groups.size(); ++g)
+            worth |= groups[g].size() > 1 && group_deps[g] != 0 && group_deps[g] != (DX | DY | DZ);
+        if (k && worth) {
+            const char* op = k == IV_MIN ? "min_x($0, $1)" : "max_x($0, $1)";
+            int acc = -1;
+            for (const std::vector<size_t>& g : groups) {
+                int part = -1;
+                for (size_t i : g) {
+                    int t = rewrite(terms[i].leaf);
+                    for (float c : terms[i].scales) t = e.add("$0 * " + flit(c), {t});
+                    part = part < 0 ? t : e.add(op, {part, t});
+                }
+                acc = acc < 0 ? part : e.add(op, {acc, part});
+            }
+            r = acc;
+        } else if (!e.st[v].ops.empty() && !e.st[v].mask && in_scope0(v)) {   // (a guarded select keeps its operands as they are)
+            std::vector<int> ops;
+            for (int o : e.st[v].ops) ops.push_back(rewrite(o));
+            if (ops != e.st[v].ops) {
+                const Stmt old = e.st[v];
+                r = e.add(old.text, ops);
+                e.st[r].g = old.g; e.st[r].o = old.o; e.st[r].bounded = old.bounded; e.st[r].abs_h = old.abs_h;
+            }
+        }
+        memo[v] = r;
+        return r;
+    };
+    return rewrite(root);
+}
+
 // Statements as guarded assignments (box pruning): every value is declared first (its type taken from its expression, which
 // nothing evaluates), then assigned in statement order inside the `if`s of its scope's path; a scope is entered again
 // when statements of another scope lie between (rare: a subtree's statements are contiguous in tape order).
@@ -1168,7 +1260,9 @@ inline std::string render_prune_function(const Phase1& ph, const PruneInfo& pi)
 struct SpecMeta {
     bool deferred = false;
     double coord_limit = 0.0;    // the largest |sample coordinate| for which a launch may set sdf::kFlagInRange (0: never)
-    int tabs[6] = {0, 0, 0, 0, 0, 0};   // columns of a box's tables: x, y, z, xy, xz, yz
+    int tabs[6] = {0, 0, 0, 0, 0, 0};   // columns of a box's tables: x, y, z, xy, xz, yz (the float4 walks)
+    int dtabs[6] = {0, 0, 0, 0, 0, 0};  // ... of the distance walks' tables (leaf blocks, distance grids, classification)
+    bool folded = false;         // the distance walks read folded chains (fold_chains)
     int prune_words = 0;         // 32-bit words of a box's pruning mask (0: the tape has nothing to prune)
     int prune_bits = 0;
     bool prune_all = false;      // the float4 walks, `pre` and the table builders are guarded too (else: the distance walks only)
@@ -1214,7 +1308,7 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
         const char* e = std::getenv("HU_PRUNE_MIN");
         return e && *e ? std::atoi(e) : 6;
     }();
-    const PruneInfo prune = analyse_pruning(ph, prune_min);
+    PruneInfo prune = analyse_pruning(ph, prune_min);
     // Where the guards go.  An assembly (many scopes: planetary 131) gets them everywhere: walks of both kinds, `pre`, the pair
     // tables' builders.  A tape with a few (the sponge: 24, all behind repetitions) gets them in the DISTANCE walks only -- leaf
     // blocks, classification, distance grids, where the vector ALU is the bound --: its float4 code, which sits on the store
@@ -1223,6 +1317,16 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     static const int prune_eval_min = [] { const char* e = std::getenv("HU_PRUNE_EVAL_MIN"); return e && *e ? std::atoi(e) : 64; }();
     const bool prune_all = prune.n_bits >= prune_eval_min;
     if (meta) { meta->prune_bits = prune.n_bits; meta->prune_words = prune.words(); meta->prune_all = prune_all; }
+    // the distance walks over boxes read the tape's chains folded per plane (fold_chains; HU_FOLD=0: as they are)
+    static const bool fold = [] { const char* e = std::getenv("HU_FOLD"); return !(e && e[0] == '0'); }();
+    const int folded_root = fold ? fold_chains(ph, prune, ph.root) : ph.root;
+    ph.n_phase1 = (int)ph.e.st.size();
+    // (the folded statements are unguarded and in no scope: fold_chains folds nothing box pruning decides)
+    prune.scope_of.resize(ph.e.st.size(), 0);
+    prune.sel.resize(ph.e.st.size());
+    prune.select_of_choice.resize(ph.e.st.size(), -1);
+    prune.need_iv.resize(ph.e.st.size(), 0);
+    if (meta) meta->folded = folded_root != ph.root;
     std::vector<int> dist_roots{ph.root}, eval_roots{ph.root};
     for (int v : ph.choice_of_rec) if (v >= 0) eval_roots.push_back(v);
     for (int v : ph.keep_w_of_rec) if (v >= 0) eval_roots.push_back(v);
@@ -1443,107 +1547,128 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     const int tab_min = knob("HU_TAB_MIN", 2);      // what a single-axis value must cost to become a table column (0: no tables)
     const bool plain_in_place = paths.size() > kInPlaceDeferredPaths;
     if (meta) meta->plain_in_place = plain_in_place;
+    // ---- axis and pair tables of one kind of walk: the candidates its walk-dependent code (and, for the float4 walks, its
+    // direction blocks) reads become columns; the pair tables are filled from single-axis columns.  The float4 walks and the
+    // distance walks have a layout each: a distance kernel fills only what its walk reads (with folded chains: the folds).
+    struct Layout {
+        std::vector<char> tabc, held, used;
+        std::vector<int> tab_index;
+        int n_tab[6] = {0, 0, 0, 0, 0, 0};
+    };
+    auto allocate = [&](const std::vector<char>& hoistable, uint8_t walk, const std::vector<int>& probe_roots, const std::vector<int>& roots,
+                        bool directions, Layout& L) {
+        L.tab_index.assign(ph.e.st.size(), -1);
+        const std::vector<int> tab_cost = statement_costs(ph);
+        L.tabc = table_candidates(ph, tab_min, knob("HU_TAB_PAIR_MIN", 3));
+        std::vector<char>& tabc = L.tabc;
+        std::vector<int>& tab_index = L.tab_index;
+        std::vector<char>& held = L.held;
+        std::vector<char>& used = L.used;
+        int* n_tab = L.n_tab;
+        for (;;) {
+            // the columns the DISTANCES read in every brick and the walk does not change are kept in registers instead
+            // (`held`), lowest statements first, while the budget lasts: a column with x in it costs two registers, others one
+            const Variant probe = render_variant(ph, hoistable, probe_roots, tabc);
+            held.assign(ph.e.st.size(), 0);
+            // (measured, sponge(4), MI355X, single-axis tables only: leaf blocks 0.327 / 0.325 / 0.319 / 0.325 ms holding
+            // 0 / 6 / 12 / 24 registers' worth; walks of sixteen bricks along z, round 3's first form of the dense kernel,
+            // 0.497 / 0.508 / 0.532 / 0.553 ms at 0 / 6 / 9 / 16 -- registers were dearer there than reads)
+            // (a tape with box pruning holds none: most of its columns are dead in any one box, and the registers decide how many
+            // wavefronts hide its scalar branches -- planetary's distance kernels: 122 -> 78 registers, four -> six wavefronts per SIMD)
+            int budget = knob("HU_TAB_HOLD_X", prune_all ? 0 : 12);
+            for (int i = 0; i < (int)probe.tab_main.size(); ++i) {
+                if (!probe.tab_main[i] || !tabc[i] || (ph.e.st[i].deps & walk)) continue;
+                const int regs = (ph.e.st[i].deps & DX) ? 2 : 1;
+                if (budget >= regs) { held[i] = 1; budget -= regs; }
+            }
+            const Variant all = render_variant(ph, hoistable, roots, tabc, nullptr, held);
+            used = all.tab_read;
+            for (int i = 0; i < (int)held.size(); ++i) if (held[i]) used[i] = 1;
+            if (directions) (void)phase2_for(all.handed, tabc, nullptr, &used);
+            // what the builders of the pair tables read of the single-axis tables
+            for (uint8_t pair : {(uint8_t)(DX | DY), (uint8_t)(DX | DZ), (uint8_t)(DY | DZ)})
+                (void)render_table_builder(ph, pair, tab_index, tabc, std::vector<char>(used), &used);
+            std::fill(tab_index.begin(), tab_index.end(), -1);
+            std::fill(n_tab, n_tab + 6, 0);
+            bool over = false;
+            // (the dearest statements first: when a tape has more two-coordinate statements than pair columns -- an assembly
+            // of extruded profiles --, the columns go to the gears and polygons, not to the circles)
+            std::vector<int> order;
+            for (int i = 0; i < (int)used.size(); ++i) if (used[i]) order.push_back(i);
+            int wanted[6] = {0, 0, 0, 0, 0, 0};
+            for (int i : order) ++wanted[table_slot(ph.e.st[i].deps)];
+            const bool crowded = wanted[0] > kMaxTableColumns || wanted[1] > kMaxTableColumns || wanted[2] > kMaxTableColumns || wanted[3] > kMaxPairColumns ||
+                                 wanted[4] > kMaxPairColumns || wanted[5] > kMaxPairColumns || wanted[3] + wanted[4] + wanted[5] > kMaxPairTotal;
+            if (crowded) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return tab_cost[x] > tab_cost[y]; });
+            for (int i : order) {
+                const int slot = table_slot(ph.e.st[i].deps);
+                const bool fits = slot < 3 ? n_tab[slot] < kMaxTableColumns
+                                           : n_tab[slot] < kMaxPairColumns && n_tab[3] + n_tab[4] + n_tab[5] < kMaxPairTotal;
+                if (fits) tab_index[i] = n_tab[slot]++;
+                else { over = true; used[i] = 0; }
+            }
+            if (!over) break;
+            // what did not fit is computed by the walk itself, which may then reach further candidates: only the
+            // columns that were given out stay candidates, and the walk is looked at again
+            for (int i = 0; i < (int)tabc.size(); ++i) if (tab_index[i] < 0) tabc[i] = 0;
+        }
+        if (std::accumulate(n_tab, n_tab + 6, 0) == 0) { tabc.clear(); held.clear(); }
+    };
+    const char* slot_name[6] = {"x", "y", "z", "xy", "xz", "yz"};
+    const uint8_t slot_deps[6] = {DX, DY, DZ, DX | DY, DX | DZ, DY | DZ};
+    // `pre` and the table builders of one layout: tape_pre<tag>, tape_tab<tag>_<axes>
+    auto emit_tables = [&](const std::string& tag, const Layout& L, const Variant& pre_of, const PruneInfo* pi) {
+        o << "// " << tag << ": hoisted out of walks along x: " << pre_of.n_hoisted << " values; table columns: "
+          << L.n_tab[0] << " / " << L.n_tab[1] << " / " << L.n_tab[2] << " (x / y / z), " << L.n_tab[3] << " / " << L.n_tab[4] << " / " << L.n_tab[5] << " (xy / xz / yz)\n"
+          << "template <class PX, class PY, class PZ, class TB, class PR> __device__ __forceinline__ auto tape_pre" << tag
+          << "(PX px, PY py, PZ pz, const float* __restrict__ extra, uint32_t flags, const TB& tb, const PR& pr)\n{\n    using namespace sdf;\n";
+        if (pre_of.n_hoisted > 0) o << pre_of.pre;
+        else o << "    struct Hoisted {};\n    return Hoisted{};\n";
+        o << "}\n";
+        for (int a = 0; a < 3; ++a)
+            o << "template <int S, class L> __device__ __forceinline__ void tape_tab" << tag << "_" << slot_name[a] << "(float p"
+              << slot_name[a] << ", const float* __restrict__ extra, uint32_t flags, L out)\n{\n    using namespace sdf;\n"
+              << (L.n_tab[a] ? render_table_builder(ph, slot_deps[a], L.tab_index, L.tabc, L.used) : std::string()) << "}\n";
+        // (a pair table's entry: the two coordinates, and the single-axis tables positioned at it)
+        for (int a = 3; a < 6; ++a)
+            o << "template <int S, class TB, class PR, class L> __device__ __forceinline__ void tape_tab" << tag << "_" << slot_name[a]
+              << "(float px, float py, float pz, const float* __restrict__ extra, uint32_t flags, const TB& tb, const PR& pr, L out)\n{\n    using namespace sdf;\n"
+              << (L.n_tab[a] ? render_table_builder(ph, slot_deps[a], L.tab_index, L.tabc, L.used, nullptr, pi) : std::string()) << "}\n";
+    };
     for (const Form& f : forms) {
         if (f.walk == 0 && plain_in_place) continue;      // (specialised_source emits the plain form under these names)
         const std::vector<char> hoistable = hoistable_set(ph, f.walk, knob("HU_HOIST_MIN_X", 8));
-        // ---- axis and pair tables: the candidates this form's walk-dependent code and its direction blocks read become
-        // columns; the pair tables are filled from single-axis columns
-        std::vector<char> tabc;
-        std::vector<int> tab_index(ph.e.st.size(), -1);
-        int n_tab[6] = {0, 0, 0, 0, 0, 0};
-        std::vector<char> held, used;
+        // the distance walk over boxes reads the folded chains; in place, the tree as it is
+        const std::vector<int> walk_dist_roots{f.walk != 0 ? folded_root : ph.root};
+        Layout le, ld;
         if (f.walk != 0 && tab_min > 0) {
-            const std::vector<int> tab_cost = statement_costs(ph);
-            tabc = table_candidates(ph, tab_min, knob("HU_TAB_PAIR_MIN", 3));
-            for (;;) {
-                // the columns the DISTANCES read in every brick and the walk does not change are kept in registers instead
-                // (`held`), lowest statements first, while the budget lasts: a column with x in it costs two registers, others one
-                const Variant probe = render_variant(ph, hoistable, dist_roots, tabc);
-                held.assign(ph.e.st.size(), 0);
-                // (measured, sponge(4), MI355X, single-axis tables only: leaf blocks 0.327 / 0.325 / 0.319 / 0.325 ms holding
-                // 0 / 6 / 12 / 24 registers' worth; walks of sixteen bricks along z, round 3's first form of the dense kernel,
-                // 0.497 / 0.508 / 0.532 / 0.553 ms at 0 / 6 / 9 / 16 -- registers were dearer there than reads)
-                // (a tape with box pruning holds none: most of its columns are dead in any one box, and the registers decide how many
-                // wavefronts hide its scalar branches -- planetary's distance kernels: 122 -> 78 registers, four -> six wavefronts per SIMD)
-                int budget = knob("HU_TAB_HOLD_X", prune_all ? 0 : 12);
-                for (int i = 0; i < (int)probe.tab_main.size(); ++i) {
-                    if (!probe.tab_main[i] || !tabc[i] || (ph.e.st[i].deps & f.walk)) continue;
-                    const int regs = (ph.e.st[i].deps & DX) ? 2 : 1;
-                    if (budget >= regs) { held[i] = 1; budget -= regs; }
-                }
-                const Variant all = render_variant(ph, hoistable, eval_roots, tabc, nullptr, held);
-                used = all.tab_read;
-                for (int i = 0; i < (int)held.size(); ++i) if (held[i]) used[i] = 1;
-                (void)phase2_for(all.handed, tabc, nullptr, &used);
-                // what the builders of the pair tables read of the single-axis tables
-                for (uint8_t pair : {(uint8_t)(DX | DY), (uint8_t)(DX | DZ), (uint8_t)(DY | DZ)})
-                    (void)render_table_builder(ph, pair, tab_index, tabc, std::vector<char>(used), &used);
-                std::fill(tab_index.begin(), tab_index.end(), -1);
-                std::fill(n_tab, n_tab + 6, 0);
-                bool over = false;
-                // (the dearest statements first: when a tape has more two-coordinate statements than pair columns -- an assembly
-                // of extruded profiles --, the columns go to the gears and polygons, not to the circles)
-                std::vector<int> order;
-                for (int i = 0; i < (int)used.size(); ++i) if (used[i]) order.push_back(i);
-                int wanted[6] = {0, 0, 0, 0, 0, 0};
-                for (int i : order) ++wanted[table_slot(ph.e.st[i].deps)];
-                const bool crowded = wanted[0] > kMaxTableColumns || wanted[1] > kMaxTableColumns || wanted[2] > kMaxTableColumns || wanted[3] > kMaxPairColumns ||
-                                     wanted[4] > kMaxPairColumns || wanted[5] > kMaxPairColumns || wanted[3] + wanted[4] + wanted[5] > kMaxPairTotal;
-                if (crowded) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return tab_cost[x] > tab_cost[y]; });
-                for (int i : order) {
-                    const int slot = table_slot(ph.e.st[i].deps);
-                    const bool fits = slot < 3 ? n_tab[slot] < kMaxTableColumns
-                                               : n_tab[slot] < kMaxPairColumns && n_tab[3] + n_tab[4] + n_tab[5] < kMaxPairTotal;
-                    if (fits) tab_index[i] = n_tab[slot]++;
-                    else { over = true; used[i] = 0; }
-                }
-                if (!over) break;
-                // what did not fit is computed by the walk itself, which may then reach further candidates: only the
-                // columns that were given out stay candidates, and the walk is looked at again
-                for (int i = 0; i < (int)tabc.size(); ++i) if (tab_index[i] < 0) tabc[i] = 0;
-            }
-            if (std::accumulate(n_tab, n_tab + 6, 0) == 0) { tabc.clear(); held.clear(); }
+            allocate(hoistable, f.walk, dist_roots, eval_roots, true, le);
+            allocate(hoistable, f.walk, walk_dist_roots, walk_dist_roots, false, ld);
         }
-        if (meta && f.walk != 0) for (int a = 0; a < 6; ++a) meta->tabs[a] = n_tab[a];
+        if (meta && f.walk != 0) for (int a = 0; a < 6; ++a) { meta->tabs[a] = le.n_tab[a]; meta->dtabs[a] = ld.n_tab[a]; }
         // (the in-place form evaluates single points: nothing to decide per box)
         const PruneInfo* pi_dist = f.walk != 0 ? &prune : nullptr;
         const PruneInfo* pi = f.walk != 0 && prune_all ? &prune : nullptr;
-        const Variant vd = render_variant(ph, hoistable, dist_roots, tabc, &tab_index, held, pi_dist),
-                      ve = render_variant(ph, hoistable, eval_roots, tabc, &tab_index, held, pi);
-        // the values handed from `pre`: the union of what the distance and the evaluation read (one struct for both)
-        const Variant& pre_of = ve;   // (eval's roots include dist's root: its frontier covers it)
-        const bool hoists = f.walk != 0 && pre_of.n_hoisted > 0;
+        const Variant vd = render_variant(ph, hoistable, walk_dist_roots, ld.tabc, &ld.tab_index, ld.held, pi_dist),
+                      ve = render_variant(ph, hoistable, eval_roots, le.tabc, &le.tab_index, le.held, pi);
         if (f.walk != 0) {
-            o << "// hoisted out of walks along x: " << pre_of.n_hoisted << " values; table columns: "
-              << n_tab[0] << " / " << n_tab[1] << " / " << n_tab[2] << " (x / y / z), " << n_tab[3] << " / " << n_tab[4] << " / " << n_tab[5] << " (xy / xz / yz)\n"
-              << "template <class PX, class PY, class PZ, class TB, class PR> __device__ __forceinline__ auto tape_pre" << f.suffix
-              << "(PX px, PY py, PZ pz, const float* __restrict__ extra, uint32_t flags, const TB& tb, const PR& pr)\n{\n    using namespace sdf;\n";
-            if (hoists) o << pre_of.pre;
-            else o << "    struct Hoisted {};\n    return Hoisted{};\n";
-            o << "}\n";
-            const char* slot_name[6] = {"x", "y", "z", "xy", "xz", "yz"};
-            const uint8_t slot_deps[6] = {DX, DY, DZ, DX | DY, DX | DZ, DY | DZ};
-            for (int a = 0; a < 3; ++a)
-                o << "template <int S, class L> __device__ __forceinline__ void tape_tab" << f.suffix << "_" << slot_name[a] << "(float p"
-                  << slot_name[a] << ", const float* __restrict__ extra, uint32_t flags, L out)\n{\n    using namespace sdf;\n"
-                  << (n_tab[a] ? render_table_builder(ph, slot_deps[a], tab_index, tabc, used) : std::string()) << "}\n";
-            // (a pair table's entry: the two coordinates, and the single-axis tables positioned at it)
-            for (int a = 3; a < 6; ++a)
-                o << "template <int S, class TB, class PR, class L> __device__ __forceinline__ void tape_tab" << f.suffix << "_" << slot_name[a]
-                  << "(float px, float py, float pz, const float* __restrict__ extra, uint32_t flags, const TB& tb, const PR& pr, L out)\n{\n    using namespace sdf;\n"
-                  << (n_tab[a] ? render_table_builder(ph, slot_deps[a], tab_index, tabc, used, nullptr, pi) : std::string()) << "}\n";
+            // (the float4 walks' `pre` hands what their evaluation reads; the distance walks' what theirs reads)
+            emit_tables(f.suffix, le, ve, pi);
+            emit_tables("_d", ld, vd, pi);
             o << render_prune_function(ph, prune);
         }
         const std::string h_param = f.walk != 0 ? ", const H& h, const TB& tb, const PR& pr" : "";
         const std::string h_tmpl = f.walk != 0 ? ", class H, class TB, class PR" : "";
-        const std::string root_name = ph.e.st[ph.root].ops.empty() ? ph.e.st[ph.root].text : ((ve.handed[ph.root] ? "h.t" : "t") + std::to_string(ph.root));
+        auto root_of = [&](const Variant& v, int root) {
+            return ph.e.st[root].ops.empty() ? ph.e.st[root].text : ((v.handed[root] ? "h.t" : "t") + std::to_string(root));
+        };
         o << "template <class PX, class PY, class PZ" << h_tmpl << "> __device__ __forceinline__ auto tape_dist" << f.suffix
           << "(PX px, PY py, PZ pz, const float* __restrict__ extra, uint32_t flags" << h_param << ")\n{\n" << head
-          << vd.main << "    return as<T>(" << root_name << ");\n}\n";
+          << vd.main << "    return as<T>(" << root_of(vd, walk_dist_roots[0]) << ");\n}\n";
         o << "template <class PX, class PY, class PZ" << h_tmpl << "> __device__ __forceinline__ auto tape_eval" << f.suffix
           << "(PX px, PY py, PZ pz, const float* __restrict__ extra, uint32_t flags" << h_param << ")\n{\n" << head
-          << ve.main << phase2_for(ve.handed, tabc, &tab_index, nullptr)
-          << "    return v4<T>(dir.x, dir.y, dir.z, as<T>(" << root_name << "));\n}\n";
+          << ve.main << phase2_for(ve.handed, le.tabc, &le.tab_index, nullptr)
+          << "    return v4<T>(dir.x, dir.y, dir.z, as<T>(" << root_of(ve, ph.root) << "));\n}\n";
     }
     o << "// deferred directions: " << paths.size() << " (primitive, path) pairs; " << ph.e.st.size() << " statements in phase 1; box pruning: "
       << prune.n_bits << " scopes\n";
@@ -1584,24 +1709,30 @@ inline std::string specialised_source(const SpecProgram& p, bool allow_deferred,
           // the axis tables of the two walks: columns per axis, and the functions that fill one entry of each table
           << "    static constexpr int kTabXX = " << m.tabs[0] << ", kTabXY = " << m.tabs[1] << ", kTabXZ = " << m.tabs[2]
           << ", kPairXY = " << m.tabs[3] << ", kPairXZ = " << m.tabs[4] << ", kPairYZ = " << m.tabs[5] << ";\n"
+          // ... and of the distance walks (tab_d_*, hoist_d): the layout of kernels.hpp box_tables<true>
+          << "    static constexpr int kDTabXX = " << m.dtabs[0] << ", kDTabXY = " << m.dtabs[1] << ", kDTabXZ = " << m.dtabs[2]
+          << ", kDPairXY = " << m.dtabs[3] << ", kDPairXZ = " << m.dtabs[4] << ", kDPairYZ = " << m.dtabs[5] << ";\n"
           // box pruning: words of a box's mask, and the function that decides it (kernels.hpp k_box_masks)
           << "    static constexpr int kPruneWords = " << m.prune_words << ";\n"
           << "    static constexpr bool kPruneAll = " << (m.prune_all ? "true" : "false") << ";\n"
           << "    template <class PR> __device__ __forceinline__ void prune(float cx, float cy, float cz, float hx, float hy, float hz, PR& out) const\n"
           << "    { tape_prune(cx, cy, cz, hx, hy, hz, extra, out); }\n";
-        for (const char* axis : {"x", "y", "z"})
-            o << "    template <int S, class L> __device__ __forceinline__ void tab_x_" << axis << "(float p, L out) const\n"
-              << "    { tape_tab_x_" << axis << "<S>(p, extra, flags, out); }\n";
-        // one entry (a, b) of a pair table
-        o << "    template <int S, class TB, class PR, class L> __device__ __forceinline__ void tab_x_xy(float a, float b, const TB& tb, const PR& pr, L out) const\n"
-          << "    { tape_tab_x_xy<S>(a, b, 0.0f, extra, flags, tb, pr, out); }\n"
-          << "    template <int S, class TB, class PR, class L> __device__ __forceinline__ void tab_x_xz(float a, float b, const TB& tb, const PR& pr, L out) const\n"
-          << "    { tape_tab_x_xz<S>(a, 0.0f, b, extra, flags, tb, pr, out); }\n"
-          << "    template <int S, class TB, class PR, class L> __device__ __forceinline__ void tab_x_yz(float a, float b, const TB& tb, const PR& pr, L out) const\n"
-          << "    { tape_tab_x_yz<S>(0.0f, a, b, extra, flags, tb, pr, out); }\n"
-          // what does not change along x, for the walks of a box with y and z fixed (kernels.hpp box_eval)
-          << "    template <class PY, class PZ, class TB, class PR> __device__ __forceinline__ auto hoist_x(PY py, PZ pz, const TB& tb, const PR& pr) const\n"
-          << "    { return tape_pre_x(0.0f, py, pz, extra, flags, tb, pr); }\n"
+        for (const char* kind : {"x", "d"}) {
+            for (const char* axis : {"x", "y", "z"})
+                o << "    template <int S, class L> __device__ __forceinline__ void tab_" << kind << "_" << axis << "(float p, L out) const\n"
+                  << "    { tape_tab_" << kind << "_" << axis << "<S>(p, extra, flags, out); }\n";
+            // one entry (a, b) of a pair table
+            o << "    template <int S, class TB, class PR, class L> __device__ __forceinline__ void tab_" << kind << "_xy(float a, float b, const TB& tb, const PR& pr, L out) const\n"
+              << "    { tape_tab_" << kind << "_xy<S>(a, b, 0.0f, extra, flags, tb, pr, out); }\n"
+              << "    template <int S, class TB, class PR, class L> __device__ __forceinline__ void tab_" << kind << "_xz(float a, float b, const TB& tb, const PR& pr, L out) const\n"
+              << "    { tape_tab_" << kind << "_xz<S>(a, 0.0f, b, extra, flags, tb, pr, out); }\n"
+              << "    template <int S, class TB, class PR, class L> __device__ __forceinline__ void tab_" << kind << "_yz(float a, float b, const TB& tb, const PR& pr, L out) const\n"
+              << "    { tape_tab_" << kind << "_yz<S>(0.0f, a, b, extra, flags, tb, pr, out); }\n"
+              // what does not change along x, for the walks of a box with y and z fixed (kernels.hpp box_eval)
+              << "    template <class PY, class PZ, class TB, class PR> __device__ __forceinline__ auto hoist_" << kind << "(PY py, PZ pz, const TB& tb, const PR& pr) const\n"
+              << "    { return tape_pre_" << kind << "(0.0f, py, pz, extra, flags, tb, pr); }\n";
+        }
+        o
           << "    template <class PX, class PY, class PZ, class H, class TB, class PR> __device__ __forceinline__ auto eval_hoisted_x(PX px, PY py, PZ pz, const H& h, const TB& tb, const PR& pr) const\n"
           << "    { return tape_eval_x(px, py, pz, extra, flags, h, tb, pr); }\n"
           << "    template <class PX, class PY, class PZ, class H, class TB, class PR> __device__ __forceinline__ auto dist_hoisted_x(PX px, PY py, PZ pz, const H& h, const TB& tb, const PR& pr) const\n"

@@ -193,8 +193,7 @@ int ensure_attrs()
     if ((rc = ensure_attrs_n<1>())) return rc;
     if ((rc = ensure_attrs_n<2>())) return rc;
     HU_HIP(hu_render::allow_big_lds(kMaxLds));   // the ray caster and the bitmap kernels (render.hip)
-    HU_HIP(hu_interference::allow_big_lds(kMaxLds));   // (interference.hip)
-    HU_HIP(hu_clearance::allow_big_lds(kMaxLds));      // (clearance.hip)
+    HU_HIP(hu_cells::allow_big_lds(kMaxLds));          // (instance_pairs.hip)
     done_for_device = dev;
     return HU_OK;
 }
@@ -1089,7 +1088,7 @@ int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, si
 {
     if (!tapes || !table_host || !distance_only_out || !lane_bytes) return fail(HU_ERR_BAD_ARG, "NULL argument");
     if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "an interference table holds 1..64 instances");
-    if (bytes < (size_t)n * sizeof(hu_interference::InstanceRec)) return fail(HU_ERR_BAD_ARG, "table buffer too small");
+    if (bytes < (size_t)n * sizeof(hu_cells::InstanceRec)) return fail(HU_ERR_BAD_ARG, "table buffer too small");
     bool all_do = true;
     for (uint32_t i = 0; i < n; ++i) {
         if (!tapes[i]) return fail(HU_ERR_BAD_ARG, "NULL tape");
@@ -1104,9 +1103,9 @@ int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, si
         n4 = std::max(n4, (uint32_t)(all_do ? tapes[i]->n_point_slots : tapes[i]->n_slots));
         n_res = std::max(n_res, all_do ? (uint32_t)tapes[i]->n_result_slots : 0u);
     }
-    auto* recs = static_cast<hu_interference::InstanceRec*>(table_host);
+    auto* recs = static_cast<hu_cells::InstanceRec*>(table_host);
     for (uint32_t i = 0; i < n; ++i)
-        recs[i] = hu_interference::InstanceRec{all_do ? tapes[i]->recs_do_dev : tapes[i]->recs_dev, tapes[i]->extra_dev, n4, 0u};
+        recs[i] = hu_cells::InstanceRec{all_do ? tapes[i]->recs_do_dev : tapes[i]->recs_dev, tapes[i]->extra_dev, n4, 0u};
     *distance_only_out = all_do ? 1 : 0;
     *lane_bytes = n4 * 16u + n_res * 4u;
     return HU_OK;
@@ -1114,90 +1113,13 @@ int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, si
 
 namespace {
 
-// workgroup size for an interference launch: four wavefronts (four cells) while their register file fits 48 KiB, as
-// launch_shape() sizes the one-voxel interpreter kernels; the LDS holds the largest instance's file
-int interference_launch(bool leaf, int distance_only_kernel, uint32_t lane_bytes, hu_interference::Args& a, void* stream)
+// Workgroup size for a launch over instance cells: four wavefronts (four cells) while their register file fits 48 KiB, as
+// launch_shape() sizes the one-voxel interpreter kernels; the LDS holds the largest instance's file.  `extra_lane_bytes`
+// follow it and count against the same 48 KiB: clearance's w area at the finest level, 4 bytes per instance and lane.
+int cells_launch(hu_cells::Kernel kernel, int distance_only_kernel, uint32_t lane_bytes, size_t extra_lane_bytes, hu_cells::Args& a,
+                 void* stream)
 {
-    uint32_t block = 256;
-    while (block > 64u && (size_t)lane_bytes * block > 48 * 1024) block >>= 1;
-    const size_t regfile = (size_t)lane_bytes * block;
-    if (regfile + kScratchBytes > kMaxLds)
-        return fail(HU_ERR_UNSUPPORTED, "an instance keeps more values live than fit the 160 KiB LDS register file");
-    int rc;
-    if ((rc = ensure_attrs())) return rc;
-    a.scratch_offset = (uint32_t)regfile;
-    const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
-    if (blocks == 0) return HU_OK;
-    if (blocks > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
-    HU_HIP(hu_interference::level(leaf, distance_only_kernel != 0, a, (uint32_t)blocks, block, regfile + kScratchBytes, (hipStream_t)stream));
-    return HU_OK;
-}
-
-int interference_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                      const uint32_t dims[3], const float corner[3], float step, uint64_t* evaluations_dev, hu_interference::Args& a)
-{
-    if (!table_dev || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
-        return fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "1..64 instances");
-    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0 || dims[0] > 65536u || dims[1] > 65536u)
-        return fail(HU_ERR_BAD_ARG, "lattice dims must be positive, x and y at most 65536");
-    std::memset(&a, 0, sizeof(a));
-    a.table = static_cast<const hu_interference::InstanceRec*>(table_dev);
-    a.n_instances = n;
-    a.parents = static_cast<const uint4*>(parents_dev);
-    a.n_parents_dev = n_parents_dev;
-    a.max_parents = max_parents;
-    for (int i = 0; i < 3; ++i) {
-        a.dims[i] = dims[i];
-        a.corner[i] = corner[i];
-    }
-    a.step = step;
-    a.evaluations = reinterpret_cast<unsigned long long*>(evaluations_dev);
-    return HU_OK;
-}
-
-}  // namespace
-
-int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
-                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                                   uint64_t* evaluations_dev, void* stream)
-{
-    hu_interference::Args a;
-    int rc;
-    if ((rc = interference_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a))) return rc;
-    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (child_side < 4u || child_side > 16384u) return fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
-    a.child_side = child_side;
-    a.thr = thr;
-    a.counter = counter_dev;
-    a.children = static_cast<uint4*>(children_dev);
-    a.capacity = capacity;
-    return interference_launch(false, distance_only_kernel, lane_bytes, a, stream);
-}
-
-int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
-                                  uint64_t* evaluations_dev, void* stream)
-{
-    hu_interference::Args a;
-    int rc;
-    if ((rc = interference_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a))) return rc;
-    if (!pairs_dev) return fail(HU_ERR_BAD_ARG, "NULL argument");
-    a.child_side = 1u;
-    a.pairs = static_cast<hu_interference::PairAcc*>(pairs_dev);
-    return interference_launch(true, distance_only_kernel, lane_bytes, a, stream);
-}
-
-namespace {
-
-// workgroup size for a clearance launch, as interference_launch sizes it, but with the leaf's and the witness's w area
-// (4 bytes per instance and lane, clearance.hip) counted with the register file against the same 48 KiB
-int clearance_launch(hu_clearance::Kernel kernel, int distance_only_kernel, uint32_t lane_bytes, hu_clearance::Args& a, void* stream)
-{
-    const size_t per_lane = (size_t)lane_bytes + (kernel == hu_clearance::kCells ? 0u : 4u * a.n_instances);
+    const size_t per_lane = (size_t)lane_bytes + extra_lane_bytes;
     uint32_t block = 256;
     while (block > 64u && per_lane * block > 48 * 1024) block >>= 1;
     const size_t regfile = (size_t)lane_bytes * block, lds = per_lane * block + kScratchBytes;
@@ -1209,22 +1131,25 @@ int clearance_launch(hu_clearance::Kernel kernel, int distance_only_kernel, uint
     const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
     if (blocks == 0) return HU_OK;
     if (blocks > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
-    HU_HIP(hu_clearance::level(kernel, distance_only_kernel != 0, a, (uint32_t)blocks, block, lds, (hipStream_t)stream));
+    HU_HIP(hu_cells::level(kernel, distance_only_kernel != 0, a, (uint32_t)blocks, block, lds, (hipStream_t)stream));
     return HU_OK;
 }
 
-int clearance_args(const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev,
-                   const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                   uint64_t* evaluations_dev, hu_clearance::Args& a)
+// What every entry point over instance cells checks and fills.  The entry points of `clearance` also want the windows,
+// a z extent within 16 bits (the witness packs an index into 16 bits per axis) and a finite step >= 0; interference's
+// were released without those checks and keep accepting what they accepted.
+int cells_args(bool clearance, const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev,
+               const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+               uint64_t* evaluations_dev, hu_cells::Args& a)
 {
-    if (!table_dev || !windows_dev || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
+    if (!table_dev || (clearance && !windows_dev) || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
         return fail(HU_ERR_BAD_ARG, "NULL argument");
     if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "1..64 instances");
-    for (int i = 0; i < 3; ++i)   // (the witness packs an index into 16 bits per axis)
-        if (dims[i] == 0 || dims[i] > 65536u) return fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(step) || step < 0.0f) return fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0 || dims[0] > 65536u || dims[1] > 65536u || (clearance && dims[2] > 65536u))
+        return fail(HU_ERR_BAD_ARG, clearance ? "lattice dims must be in 1..65536" : "lattice dims must be positive, x and y at most 65536");
+    if (clearance && (!std::isfinite(step) || step < 0.0f)) return fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
     std::memset(&a, 0, sizeof(a));
-    a.table = static_cast<const hu_interference::InstanceRec*>(table_dev);
+    a.table = static_cast<const hu_cells::InstanceRec*>(table_dev);
     a.windows = windows_dev;
     a.n_instances = n;
     a.parents = static_cast<const uint4*>(parents_dev);
@@ -1239,24 +1164,66 @@ int clearance_args(const void* table_dev, uint32_t n, const uint32_t* windows_de
     return HU_OK;
 }
 
-int clearance_finest(hu_clearance::Kernel kernel, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                     const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                     const uint32_t dims[3], const float corner[3], float step, float t, void* pairs_dev,
-                     uint64_t* evaluations_dev, void* stream)
+// a level of cells above the finest one, of either check
+int cells_level(bool clearance, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                uint32_t child_side, const uint32_t dims[3], const float corner[3], float step, float thr, uint32_t* counter_dev,
+                void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream)
 {
-    hu_clearance::Args a;
+    hu_cells::Args a;
     int rc;
-    if ((rc = clearance_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+    if ((rc = cells_args(clearance, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+        return rc;
+    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (child_side < 4u || child_side > 16384u) return fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
+    if (clearance && (!std::isfinite(thr) || thr < 0.0f)) return fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    a.child_side = child_side;
+    a.thr = thr;
+    a.counter = counter_dev;
+    a.children = static_cast<uint4*>(children_dev);
+    a.capacity = capacity;
+    return cells_launch(clearance ? hu_cells::kClearanceCells : hu_cells::kInterferenceCells, distance_only_kernel, lane_bytes, 0u, a, stream);
+}
+
+// a launch over the finest cells: interference's leaf (no windows, no t), clearance's leaf or witness
+int cells_finest(hu_cells::Kernel kernel, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                 const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                 const uint32_t dims[3], const float corner[3], float step, float t, void* pairs_dev, uint64_t* evaluations_dev,
+                 void* stream)
+{
+    const bool clearance = kernel != hu_cells::kInterferenceLeaf;
+    hu_cells::Args a;
+    int rc;
+    if ((rc = cells_args(clearance, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
         return rc;
     if (!pairs_dev) return fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (!std::isfinite(t) || t < 0.0f) return fail(HU_ERR_BAD_ARG, "t must be finite and not negative");
+    if (clearance && (!std::isfinite(t) || t < 0.0f)) return fail(HU_ERR_BAD_ARG, "t must be finite and not negative");
     a.child_side = 1u;
     a.t = t;
-    a.pairs = static_cast<hu_clearance::PairAcc*>(pairs_dev);
-    return clearance_launch(kernel, distance_only_kernel, lane_bytes, a, stream);
+    a.pairs = pairs_dev;
+    return cells_launch(kernel, distance_only_kernel, lane_bytes, clearance ? 4u * n : 0u, a, stream);
 }
 
 }  // namespace
+
+int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
+                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                   uint64_t* evaluations_dev, void* stream)
+{
+    return cells_level(false, table_dev, n, distance_only_kernel, lane_bytes, nullptr, parents_dev, n_parents_dev, max_parents,
+                       child_side, dims, corner, step, thr, counter_dev, children_dev, capacity, evaluations_dev, stream);
+}
+
+int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
+                                  uint64_t* evaluations_dev, void* stream)
+{
+    return cells_finest(hu_cells::kInterferenceLeaf, table_dev, n, distance_only_kernel, lane_bytes, nullptr, parents_dev,
+                        n_parents_dev, max_parents, dims, corner, step, 0.0f, pairs_dev, evaluations_dev, stream);
+}
 
 int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
                                 const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
@@ -1264,19 +1231,8 @@ int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_
                                 float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
                                 uint64_t* evaluations_dev, void* stream)
 {
-    hu_clearance::Args a;
-    int rc;
-    if ((rc = clearance_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
-        return rc;
-    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (child_side < 4u || child_side > 16384u) return fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
-    if (!std::isfinite(thr) || thr < 0.0f) return fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
-    a.child_side = child_side;
-    a.thr = thr;
-    a.counter = counter_dev;
-    a.children = static_cast<uint4*>(children_dev);
-    a.capacity = capacity;
-    return clearance_launch(hu_clearance::kCells, distance_only_kernel, lane_bytes, a, stream);
+    return cells_level(true, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev, n_parents_dev, max_parents,
+                       child_side, dims, corner, step, thr, counter_dev, children_dev, capacity, evaluations_dev, stream);
 }
 
 int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
@@ -1284,8 +1240,8 @@ int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_o
                                uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
                                void* pairs_dev, uint64_t* evaluations_dev, void* stream)
 {
-    return clearance_finest(hu_clearance::kLeaf, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
-                            n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+    return cells_finest(hu_cells::kClearanceLeaf, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
+                        n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
 }
 
 int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
@@ -1293,8 +1249,8 @@ int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distanc
                                   uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
                                   void* pairs_dev, uint64_t* evaluations_dev, void* stream)
 {
-    return clearance_finest(hu_clearance::kWitness, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
-                            n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+    return cells_finest(hu_cells::kClearanceWitness, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
+                        n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
 }
 
 int hu_ray_caster(hu_tape t, const float origin[4], const float forward[4], const float up[4], const float right[4],

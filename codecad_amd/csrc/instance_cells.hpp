@@ -1,12 +1,12 @@
-// codecad_amd/csrc/instance_cells.hpp -- what the kernels over the instances of an assembly share
-// (interference.hip, clearance.hip): a wavefront's cell row, the table of the instances' programs and the box of a lane mask.
+// codecad_amd/csrc/instance_cells.hpp -- what a kernel over the instances of an assembly is made of (instance_pairs.hip):
+// a wavefront's cell row, the table of the instances' programs and the box of a lane mask.
 //
 // A CELL is a cube of 4^k lattice samples, a 16-byte row {x0 | y0 << 16, z0, mask lo, mask hi}: its first sample's indices
 // and the 64-bit mask of the instances still candidates in it.  One wavefront takes one cell, lane = 16 x + 4 y + z of its
-// 4 x 4 x 4 parts.  The launch arguments A of every such kernel have `parents`, `n_parents_dev`, `max_parents` and `table`.
+// 4 x 4 x 4 parts.  Every such kernel takes hu_cells::Args (launchers.hpp).
 #pragma once
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace hu_cells {
 
@@ -18,7 +18,7 @@ struct CellRow {
     uint64_t mask;
     bool have;
 };
-template <class A> __device__ __forceinline__ CellRow cell_row(const A& a)
+__device__ __forceinline__ CellRow cell_row(const Args& a)
 {
     const uint32_t listed = *a.n_parents_dev, n = listed < a.max_parents ? listed : a.max_parents;   // (an overflowed list holds max_parents)
     const uint32_t p = uniform(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
@@ -45,8 +45,8 @@ template <class T> __device__ __forceinline__ const T* constant_uniform(const T*
 }
 
 // distance of instance `n` (wave-uniform) at p: the one interpreter call site of a kernel
-template <bool DO, class A>
-__device__ __forceinline__ float instance_dist(const A& a, uint32_t n, float px, float py, float pz, void* lds)
+template <bool DO>
+__device__ __forceinline__ float instance_dist(const Args& a, uint32_t n, float px, float py, float pz, void* lds)
 {
     const auto r = a.table[n];
     return sdfk::InterpEval<DO>{constant_uniform(r.prog), constant_uniform(r.extra), uniform(r.n4)}.dist(px, py, pz, lds);

@@ -1,0 +1,275 @@
+// codecad_amd/csrc/instance_pairs.hip
+//
+// The checks between the instances of an assembly: INTERFERENCE (codecad_amd/interference.py), which pairs of instances
+// have lattice samples inside both, how many, where; and CLEARANCE (codecad_amd/clearance.py), which pairs come closer
+// than a gap, and where.  Every instance has a tape of its own; the kernels reach them through a device table
+// (InstanceRec) and evaluate them with the tape interpreter, one instance at a time, the instance index wave-uniform so
+// that its records still arrive through scalar loads.
+//
+// The lattice is cut into cubic CELLS of side 4^k samples; a cell is a 16-byte row {x0 | y0 << 16, z0, mask lo, mask hi}:
+// its first sample's indices and the 64-bit mask of the instances that may still matter in it (candidates).
+// One WAVEFRONT takes one cell and its 64 lanes take the cell's 4 x 4 x 4 parts, lane = 16 x + 4 y + z
+// (instance_cells.hpp).  Clearance is interference's traversal with a threshold t > 0 instead of 0 and a WINDOW per
+// instance, an index box the host computes: a sample is NEAR the pair (i, j) when it lies in both instances' windows
+// and w_i < t, w_j < t; there v = max(w_i, w_j).
+//   k_instance_cells (side > 4): a lane is a child cell; every candidate is evaluated at the child's centre and dropped
+//     where its distance proves it has no sample inside (interference) or near (clearance: or where the child misses
+//     its window, WINDOWED) the child; children with >= 2 candidates left are compacted into the next list (ballots,
+//     one atomic per workgroup: kernels.hpp wg_compact_slots);
+//   k_interference_leaf (side 4): a lane is a sample; every candidate is evaluated there, which gives the lane's
+//     inside bitmask (w < 0, strictly), and every pair of candidates with a sample inside both adds its count, index
+//     sums and index box to the pair's accumulators (one atomic per accumulator per wavefront);
+//   k_clearance_leaf (side 4): the same with the near bitmask, every w kept in the wavefront's LDS area, [instance][lane],
+//     so that a pair also gives the least order key of v;
+//   k_clearance_witness (side 4), launched after the leaf over the same list: evaluates again and, for every pair, its
+//     first lane whose v has the pair's final least key gives one u64 atomicMin of x << 32 | y << 16 | z.  Lanes go
+//     16 x + 4 y + z, so the wavefront's first such lane is its lexicographically smallest sample.
+// All read their parent count from the list's header on the device (the *_indirect pattern of the other level kernels).
+// Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).  hip_util.hip validates
+// arguments and calls the launch functions at the end of this file.
+#include "instance_cells.hpp"
+
+using namespace sdfk;
+using namespace hu_cells;
+
+namespace {
+
+template <bool DO, bool WINDOWED>
+__global__ void __launch_bounds__(256) k_instance_cells(const Args a)
+{
+    extern __shared__ float4 lds[];
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds) + a.scratch_offset);
+    const uint32_t lane = threadIdx.x & 63u;
+    const CellRow row = cell_row(a);
+    const uint32_t s = a.child_side;
+    const uint32_t x = row.x0 + (lane >> 4) * s, y = row.y0 + ((lane >> 2) & 3u) * s, z = row.z0 + (lane & 3u) * s;
+    const bool live = row.have & (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
+    // the child's centre; its samples lie within (s - 1) * step * sqrt(3) / 2 of it, a.thr is t (interference: 0) plus
+    // more than that (interference.py)
+    const float h = 0.5f * (float)(s - 1u);
+    const float px = a.corner[0] + a.step * ((float)x + h);
+    const float py = a.corner[1] + a.step * ((float)y + h);
+    const float pz = a.corner[2] + a.step * ((float)z + h);
+    const uint32_t* windows = WINDOWED ? constant_uniform(a.windows) : nullptr;
+    uint64_t keep = 0ull;
+    for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {      // wave-uniform
+        const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
+        bool reach = true;
+        if constexpr (WINDOWED) {
+            const uint32_t* win = windows + 6u * n;
+            reach = (x <= win[3]) & (x + s - 1u >= win[0]) & (y <= win[4]) & (y + s - 1u >= win[1]) & (z <= win[5]) &
+                    (z + s - 1u >= win[2]);
+        }
+        const float w = instance_dist<DO>(a, n, px, py, pz, lds);
+        if (reach && !(w >= a.thr)) keep |= 1ull << n;            // (a NaN keeps its candidate)
+    }
+    const uint64_t lives = __ballot(live);
+    if (lane == 0u && lives) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
+    const bool flag[1] = {live && __popcll(keep) >= 2};
+    uint32_t slot[1];
+    wg_compact_slots<1>(flag, a.counter, scratch, slot);         // every wavefront of the workgroup gets here (barriers)
+    if (flag[0] && slot[0] < a.capacity)
+        a.children[slot[0]] = make_uint4(x | (y << 16), z, (uint32_t)keep, (uint32_t)(keep >> 32));
+}
+
+// the sample of a finest cell this lane takes
+struct LeafLane {
+    uint32_t lane, x, y, z;
+    bool live;
+    float px, py, pz;
+};
+__device__ __forceinline__ LeafLane leaf_lane(const Args& a, const CellRow& row)
+{
+    LeafLane l;
+    l.lane = threadIdx.x & 63u;
+    l.x = row.x0 + (l.lane >> 4);
+    l.y = row.y0 + ((l.lane >> 2) & 3u);
+    l.z = row.z0 + (l.lane & 3u);
+    l.live = (l.x < a.dims[0]) & (l.y < a.dims[1]) & (l.z < a.dims[2]);
+    // exactly kernels.hpp sample() (the lattice of oracle.grid_eval)
+    l.px = sample(a.corner[0], a.step, l.x);
+    l.py = sample(a.corner[1], a.step, l.y);
+    l.pz = sample(a.corner[2], a.step, l.z);
+    return l;
+}
+
+// one evaluation per live lane and candidate, counted once per wavefront
+__device__ __forceinline__ void count_evaluations(const Args& a, const CellRow& row, const LeafLane& l)
+{
+    const uint64_t lives = __ballot(l.live);
+    if (l.lane == 0u) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
+}
+
+// f(i, j, both, b) for every pair i < j of `present` (wave-uniform) some lane has both of in its bitmask `mine`: `both`
+// says whether this lane does, `b` is its ballot
+template <class F> __device__ __forceinline__ void for_pairs(uint64_t present, uint64_t mine, F f)
+{
+    for (uint64_t mi = present; mi != 0ull; mi &= mi - 1ull) {
+        const uint32_t i = uniform((uint32_t)__builtin_ctzll(mi));
+        for (uint64_t mj = mi & (mi - 1ull); mj != 0ull; mj &= mj - 1ull) {
+            const uint32_t j = uniform((uint32_t)__builtin_ctzll(mj));
+            const bool both = ((mine >> i) & (mine >> j) & 1ull) != 0ull;
+            const uint64_t b = __ballot(both);
+            if (b == 0ull) continue;                              // wave-uniform
+            f(i, j, both, b);
+        }
+    }
+}
+
+// the lanes of `b` (this lane: `both`) added to a pair's count, index sums and index box
+template <class Acc>
+__device__ __forceinline__ void add_samples(Acc* acc, bool both, uint64_t b, const LeafLane l, const CellRow row)
+{
+    const uint32_t sx = __builtin_amdgcn_readlane(wave_sum_to_last_lane(both ? l.x : 0u), 63);
+    const uint32_t sy = __builtin_amdgcn_readlane(wave_sum_to_last_lane(both ? l.y : 0u), 63);
+    const uint32_t sz = __builtin_amdgcn_readlane(wave_sum_to_last_lane(both ? l.z : 0u), 63);
+    uint32_t lo[3], hi[3];
+    mask_box(b, lo, hi);
+    // lanes 0-3: the u64 sums, 4-6: the minima, 7-9: the maxima -- each accumulator once per wavefront
+    const uint32_t lane = l.lane;
+    const unsigned long long add = lane == 0u ? (unsigned long long)__popcll(b) : lane == 1u ? sx : lane == 2u ? sy : sz;
+    const uint32_t k = lane < 7u ? lane - 4u : lane - 7u;
+    const uint32_t origin = k == 0u ? row.x0 : k == 1u ? row.y0 : row.z0;
+    const uint32_t bound = origin + (lane < 7u ? (k == 0u ? lo[0] : k == 1u ? lo[1] : lo[2]) : (k == 0u ? hi[0] : k == 1u ? hi[1] : hi[2]));
+    if (lane < 4u) atomicAdd(&acc->sums[lane], add);
+    else if (lane < 7u) atomicMin(&acc->lo[k], bound);
+    else if (lane < 10u) atomicMax(&acc->hi[k], bound);
+}
+
+template <bool DO>
+__global__ void __launch_bounds__(256) k_interference_leaf(const Args a)
+{
+    extern __shared__ float4 lds[];
+    const CellRow row = cell_row(a);
+    if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
+    const LeafLane l = leaf_lane(a, row);
+    uint64_t inside = 0ull, present = 0ull;                       // per lane; wave-uniform
+    for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {
+        const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
+        const float w = instance_dist<DO>(a, n, l.px, l.py, l.pz, lds);
+        const bool in = l.live & (w < 0.0f);
+        inside |= in ? 1ull << n : 0ull;
+        present |= __ballot(in) ? 1ull << n : 0ull;
+    }
+    count_evaluations(a, row, l);
+    for_pairs(present, inside, [&](uint32_t i, uint32_t j, bool both, uint64_t b) __attribute__((always_inline)) {
+        add_samples(static_cast<OverlapAcc*>(a.pairs) + (size_t)i * a.n_instances + j, both, b, l, row);
+    });
+}
+
+// the key of v in an order that unsigned comparison keeps: -0 and +0 get the one key of +0 (clearance.py decodes it)
+__device__ __forceinline__ uint32_t order_key(float v)
+{
+    const uint32_t b = __float_as_uint(v == 0.0f ? 0.0f : v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// Minimum over the 64 lanes of a wavefront; it arrives in lane 63.  kernels.hpp wave_sum_to_last_lane with min for +
+// (lanes without a source take 0xffffffff, the identity).
+__device__ __forceinline__ uint32_t wave_min_to_last_lane(uint32_t v)
+{
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
+    return v;
+}
+
+// Clearance's finest cell: every candidate evaluated at the lane's sample, w into the wavefront's LDS area (after the
+// register file) at wl[n * 64 + lane].  `near` is the lane's near bitmask (in n's window and w < t, strictly: a NaN is
+// never near), `present` the instances with a near lane (wave-uniform).
+struct NearLeaf {
+    float* wl;
+    uint64_t near, present;
+    __device__ __forceinline__ uint32_t key(uint32_t i, uint32_t j, uint32_t lane) const
+    {
+        return order_key(fmaxf(wl[i * 64u + lane], wl[j * 64u + lane]));
+    }
+};
+template <bool DO> __device__ __forceinline__ NearLeaf near_leaf(const Args& a, const CellRow& row, const LeafLane& l)
+{
+    extern __shared__ float4 lds[];
+    NearLeaf r;
+    r.wl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + a.scratch_offset) + (threadIdx.x >> 6) * 64u * a.n_instances;
+    r.near = r.present = 0ull;
+    const uint32_t* windows = constant_uniform(a.windows);
+    for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {      // wave-uniform
+        const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
+        const uint32_t* win = windows + 6u * n;
+        const bool in = l.live & (l.x >= win[0]) & (l.x <= win[3]) & (l.y >= win[1]) & (l.y <= win[4]) & (l.z >= win[2]) &
+                        (l.z <= win[5]);
+        const float w = instance_dist<DO>(a, n, l.px, l.py, l.pz, lds);
+        r.wl[n * 64u + l.lane] = w;
+        r.near |= (in & (w < a.t)) ? 1ull << n : 0ull;
+    }
+    count_evaluations(a, row, l);
+    for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {
+        const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
+        r.present |= __ballot((r.near >> n) & 1ull) ? 1ull << n : 0ull;
+    }
+    return r;
+}
+
+template <bool DO>
+__global__ void __launch_bounds__(256) k_clearance_leaf(const Args a)
+{
+    const CellRow row = cell_row(a);
+    if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
+    const LeafLane l = leaf_lane(a, row);
+    const NearLeaf c = near_leaf<DO>(a, row, l);
+    for_pairs(c.present, c.near, [&](uint32_t i, uint32_t j, bool both, uint64_t b) __attribute__((always_inline)) {
+        const uint32_t kmin = __builtin_amdgcn_readlane(wave_min_to_last_lane(both ? c.key(i, j, l.lane) : 0xffffffffu), 63);
+        NearAcc* acc = static_cast<NearAcc*>(a.pairs) + (size_t)i * a.n_instances + j;
+        add_samples(acc, both, b, l, row);
+        if (l.lane == 10u) atomicMin(&acc->key, kmin);            // lane 10: the least key, once per wavefront
+    });
+}
+
+template <bool DO>
+__global__ void __launch_bounds__(256) k_clearance_witness(const Args a)
+{
+    const CellRow row = cell_row(a);
+    if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
+    const LeafLane l = leaf_lane(a, row);
+    const NearLeaf c = near_leaf<DO>(a, row, l);
+    for_pairs(c.present, c.near, [&](uint32_t i, uint32_t j, bool both, uint64_t) __attribute__((always_inline)) {
+        NearAcc* acc = static_cast<NearAcc*>(a.pairs) + (size_t)i * a.n_instances + j;
+        // the leaf launch has finished: the least key is final, and this kernel never writes it (a scalar load)
+        const uint32_t kmin = *constant_uniform(&acc->key);
+        const uint64_t b = __ballot(both && c.key(i, j, l.lane) == kmin);
+        if (b != 0ull && l.lane == (uint32_t)__builtin_ctzll(b))
+            atomicMin(&acc->witness, ((unsigned long long)l.x << 32) | ((unsigned long long)l.y << 16) | l.z);
+    });
+}
+
+// [Kernel][distance_only]
+void (*const kKernelTable[kKernels][2])(Args) = {
+    {k_instance_cells<false, false>, k_instance_cells<true, false>},
+    {k_interference_leaf<false>, k_interference_leaf<true>},
+    {k_instance_cells<false, true>, k_instance_cells<true, true>},
+    {k_clearance_leaf<false>, k_clearance_leaf<true>},
+    {k_clearance_witness<false>, k_clearance_witness<true>},
+};
+
+}  // namespace
+
+namespace hu_cells {
+
+hipError_t allow_big_lds(size_t bytes)
+{
+    hipError_t e = hipSuccess;
+    for (const auto& kernel : kKernelTable)
+        for (const auto variant : kernel)
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return e;
+}
+
+hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream)
+{
+    hipLaunchKernelGGL(kKernelTable[kernel][distance_only], dim3(blocks), dim3(block), lds, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace hu_cells

@@ -1,4 +1,4 @@
-// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip, interference.hip and clearance.hip.
+// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip and instance_pairs.hip.
 //
 // Translation units that hold kernels (hip_util/builder.py lists the flags of each):
 //   hip_util.hip  the dense / leaf-block / classification kernels over the tape interpreter, built with
@@ -7,8 +7,8 @@
 //                 arithmetic self-test -- built WITHOUT it: that option once let a scalar branch choose a per-lane
 //                 value in a divergent loop (csrc/exchange.hip), so it stays confined to the kernels that are
 //                 nothing but the interpreter's wave-uniform loop around branch-free ops;
-//   interference.hip  the interference check between the instances of an assembly, built without it as well;
-//   clearance.hip     the clearance (near-miss) check between those instances, built without it as well;
+//   instance_pairs.hip  the interference and clearance checks between the instances of an assembly, built without
+//                 it as well;
 // Each function enqueues one launch and returns hipGetLastError().
 #pragma once
 
@@ -32,7 +32,7 @@ hipError_t selftest_minmax3(unsigned long long* counts_dev);
 
 }  // namespace hu_render
 
-namespace hu_interference {
+namespace hu_cells {
 
 // one instance of the device table: the program the kernels interpret for it (distance-only or full, the same kind for
 // every instance of a launch), its constants and the float4 slots of the register file (the same for every instance)
@@ -43,76 +43,52 @@ struct InstanceRec {
 };
 static_assert(sizeof(InstanceRec) == 24, "hu_interference_table writes 24-byte records");
 
-// the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j]: samples inside both, the sums of their x, y, z
-// indices, and the box of those indices (lo starts at 0xffffffff, hi at 0)
-struct PairAcc {
+// interference: the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j]: samples inside both, the sums
+// of their x, y, z indices, and the box of those indices (lo starts at 0xffffffff, hi at 0)
+struct OverlapAcc {
     unsigned long long sums[4];   // count, sum x, sum y, sum z
     uint32_t lo[3], hi[3];
     uint32_t pad[2];
 };
-static_assert(sizeof(PairAcc) == 64, "interference.py reads 64-byte accumulators");
+static_assert(sizeof(OverlapAcc) == 64, "interference.py reads 64-byte accumulators");
 
-struct Args {
-    const InstanceRec* table;
-    uint32_t n_instances;
-    const uint4* parents;            // rows {x0 | y0 << 16, z0, mask lo, mask hi} after the list's header row
-    const uint32_t* n_parents_dev;   // word 0 of the parents' header
-    uint32_t max_parents;            // the parents' capacity (the launch is sized for it)
-    uint32_t child_side;             // cells: side of a child cell in samples (leaf: 1)
-    uint32_t dims[3];
-    float corner[3], step, thr;
-    uint32_t* counter;               // cells: word 0 of the children's header
-    uint4* children;                 // cells: the children's rows
-    uint32_t capacity;
-    PairAcc* pairs;                  // leaf
-    unsigned long long* evaluations; // per-instance sample evaluations, added up per wavefront
-    uint32_t scratch_offset;         // bytes of LDS taken by the register file (the compaction's scratch follows)
-};
-
-hipError_t allow_big_lds(size_t bytes);
-hipError_t level(bool leaf, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
-
-}  // namespace hu_interference
-
-namespace hu_clearance {
-
-// the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j], over the pair's NEAR samples (in both
-// instances' windows, w_i < t and w_j < t): their count and index sums and box as in hu_interference::PairAcc, the order
-// key of the least v = max(w_i, w_j) (starts at 0xffffffff, clearance.hip order_key) and the witness, the least
+// clearance: the same over the pair's NEAR samples (in both instances' windows, w_i < t and w_j < t), the order key of
+// the least v = max(w_i, w_j) (starts at 0xffffffff, instance_pairs.hip order_key) and the witness, the least
 // x << 32 | y << 16 | z of the near samples whose v is that least one (starts at ~0)
-struct PairAcc {
+struct NearAcc {
     unsigned long long sums[4];   // count, sum x, sum y, sum z
     unsigned long long witness;
     uint32_t lo[3], hi[3];
     uint32_t key;
     uint32_t pad;
 };
-static_assert(sizeof(PairAcc) == 72, "clearance.py reads 72-byte accumulators");
+static_assert(sizeof(NearAcc) == 72, "clearance.py reads 72-byte accumulators");
 
+// the arguments of every kernel over instance cells; interference leaves `windows` and `t` null and zero and never reads them
 struct Args {
-    const hu_interference::InstanceRec* table;
+    const InstanceRec* table;
     const uint32_t* windows;         // n_instances x {lo x, y, z, hi x, y, z}: the samples an instance may be near at
     uint32_t n_instances;
     const uint4* parents;            // rows {x0 | y0 << 16, z0, mask lo, mask hi} after the list's header row
     const uint32_t* n_parents_dev;   // word 0 of the parents' header
     uint32_t max_parents;            // the parents' capacity (the launch is sized for it)
-    uint32_t child_side;             // cells: side of a child cell in samples (leaf, witness: 1)
+    uint32_t child_side;             // cells: side of a child cell in samples (finest level: 1)
     uint32_t dims[3];
     float corner[3], step;
     float thr;                       // cells: a candidate whose distance at a child's centre is >= thr leaves the child
-    float t;                         // leaf, witness: near means w < t
+    float t;                         // clearance's finest level: near means w < t
     uint32_t* counter;               // cells: word 0 of the children's header
     uint4* children;                 // cells: the children's rows
     uint32_t capacity;
-    PairAcc* pairs;                  // leaf, witness
+    void* pairs;                     // finest level: n_instances^2 OverlapAcc (interference) or NearAcc (clearance)
     unsigned long long* evaluations; // per-instance sample evaluations, added up per wavefront
     uint32_t scratch_offset;         // bytes of LDS taken by the register file (cells: the compaction's scratch follows;
-                                     // leaf, witness: the w of every instance, 256 bytes per instance and wavefront)
+                                     // clearance's finest level: the w of every instance, 256 bytes per instance and wavefront)
 };
 
-enum Kernel { kCells, kLeaf, kWitness };
+enum Kernel { kInterferenceCells, kInterferenceLeaf, kClearanceCells, kClearanceLeaf, kClearanceWitness, kKernels };
 
 hipError_t allow_big_lds(size_t bytes);
 hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 
-}  // namespace hu_clearance
+}  // namespace hu_cells

@@ -1,5 +1,5 @@
 """Assemblies on the host (codecad_amd/assemblies.py, rendering/bom.py) and what the interference check decides without
-a device: its argument checks, its lattice, its top-level cells, and the ISA of its kernels."""
+a device: its argument checks, its lattice, its top-level cells, and the ISA of its kernels and the clearance check's."""
 import collections
 import csv
 import math
@@ -12,7 +12,7 @@ import pytest
 
 import codecad_amd as cc
 from codecad_amd import shapes, util, nodes, assemblies
-from codecad_amd.interference import lattice, _top_cells, _top_side, _visible
+from codecad_amd._instance_cells import lattice, top_cells as _top_cells, top_side as _top_side, visible as _visible
 
 
 def _parts():
@@ -148,17 +148,19 @@ def test_interference_lattice_and_top_cells():
     assert _top_side(numpy.array([4000, 4000, 30])) == 64 and _top_side(numpy.array([4000, 4000, 4000])) == 256
 
 
-def check_interference_isa(text):
-    """Every interference kernel: no scratch; no vector-memory load at all (what they read -- arguments, the instance
-    table, the records and constants of a program, a cell's row and the list's length -- is wave-uniform); and the
-    interpreter's fetch groups as wide scalar loads off one pointer loaded from memory (the program's), not only the
-    single wide load of the kernel arguments."""
+def check_instance_kernels_isa(text):
+    """Every interference and clearance kernel: no scratch; no vector-memory load at all (what they read -- arguments,
+    the instance table, the windows, the records and constants of a program, a cell's row, the list's length and a
+    pair's least key -- is wave-uniform); and the interpreter's fetch groups as wide scalar loads off one pointer loaded
+    from memory (the program's), not only the single wide load of the kernel arguments.  Returns the instantiations
+    seen, as (kernel, its boolean template arguments)."""
     seen = set()
     for chunk in re.split(r"\n(?=_Z\w+:\s+; @)", text):
         m = re.match(r"(_Z\w+):", chunk)
-        if not m or "k_interference" not in m.group(1):
+        if not m or not re.search(r"k_(interference|clearance|instance)_", m.group(1)):
             continue
-        seen.add(re.search(r"(k_interference_\w+?)ILb([01])", m.group(1)).groups())
+        name, flags = re.search(r"(k_(?:interference|clearance|instance)_\w+?)I((?:Lb[01]E)+)E", m.group(1)).groups()
+        seen.add((name, "".join(re.findall(r"Lb([01])E", flags))))
         scratch = re.search(r"; ScratchSize: (\d+)", chunk)
         assert scratch and int(scratch.group(1)) == 0, m.group(1)
         body = chunk.split(".section")[0]
@@ -169,20 +171,24 @@ def check_interference_isa(text):
     return seen
 
 
-def test_interference_kernels_keep_their_records_in_scalar_registers(tmp_path):
-    """The interference kernels reach every instance's program through a device table indexed by a wave-uniform
-    instance number: their records must still come in through scalar loads, and nothing may spill to scratch."""
+def test_instance_kernels_keep_their_records_in_scalar_registers(tmp_path):
+    """The interference and clearance kernels reach every instance's program through a device table indexed by a
+    wave-uniform instance number: their records must still come in through scalar loads, and nothing may spill to
+    scratch.  Every instantiation the library launches: k_instance_cells<distance only, windowed> is interference's
+    cells kernel without windows and clearance's with them."""
     from codecad_amd.hip_util import builder
     hipcc = builder.find_hipcc()
     if hipcc is None:
         pytest.skip("no hipcc in this environment")
-    assert "interference.hip" in builder.SOURCES and "interference.hip" not in builder.FLAGGED_SOURCES
-    out = tmp_path / "interference.s"
+    assert "instance_pairs.hip" in builder.SOURCES and "instance_pairs.hip" not in builder.FLAGGED_SOURCES
+    out = tmp_path / "instance_pairs.s"
     flags = [f for f in builder.HIPCC_FLAGS if f != "-fPIC"]
     subprocess.run([hipcc] + flags + ["-I", builder.INCLUDE, "--cuda-device-only", "-S", "-o", str(out),
-                                      os.path.join(builder.CSRC, "interference.hip")], check=True, capture_output=True)
-    assert check_interference_isa(out.read_text()) == {("k_interference_cells", "0"), ("k_interference_cells", "1"),
-                    ("k_interference_leaf", "0"), ("k_interference_leaf", "1")}
+                                      os.path.join(builder.CSRC, "instance_pairs.hip")], check=True, capture_output=True)
+    assert check_instance_kernels_isa(out.read_text()) == {
+        ("k_instance_cells", "00"), ("k_instance_cells", "10"), ("k_interference_leaf", "0"), ("k_interference_leaf", "1"),
+        ("k_instance_cells", "01"), ("k_instance_cells", "11"), ("k_clearance_leaf", "0"), ("k_clearance_leaf", "1"),
+        ("k_clearance_witness", "0"), ("k_clearance_witness", "1")}
 
 
 def test_interference_entry_points_reject_bad_arguments():

@@ -1,17 +1,14 @@
 """What the clearance check (codecad_amd/clearance.py) decides without a device: its argument checks, its lattice and
-windows, its top-level cells, the argument checks of its entry points and the ISA of its kernels."""
-import collections
+windows, its top-level cells and the argument checks of its entry points (the ISA of its kernels: test_assemblies.py)."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy
 import pytest
 
 import codecad_amd as cc
 from codecad_amd import shapes
-from codecad_amd.interference import lattice as interference_lattice, _top_cells, _top_side, _cell_rows, _visible
+from codecad_amd.interference import lattice as interference_lattice
+from codecad_amd._instance_cells import top_cells as _top_cells, top_side as _top_side, cell_rows as _cell_rows, visible as _visible
 from codecad_amd.clearance import half_gap, lattice, windows
 
 
@@ -76,41 +73,6 @@ def test_clearance_lattice_and_windows():
     # lo = floor((A - t - corner - step) / step): (-1 - 0.25 + 1.125 - 0.25) / 0.25 = -1.5 -> -2 -> 0, (2 - ...) -> 10;
     # hi = ceil((B + t - corner + step) / step): (1 + 0.25 + 1.125 + 0.25) / 0.25 = 10.5 -> 11, (4 + ...) -> 23 -> 21
     assert windows(inst, corner, step, dims, t).tolist() == [[[0, 0, 0], [11, 9, 9]], [[10, 0, 0], [21, 9, 9]]]
-
-
-def check_clearance_isa(text):
-    """Every clearance kernel: no scratch; no vector-memory load at all (what they read -- arguments, the instance table,
-    the windows, the records and constants of a program, a cell's row, the list's length and a pair's least key -- is
-    wave-uniform); and the interpreter's fetch groups as wide scalar loads off one pointer loaded from memory (the
-    program's), not only the single wide load of the kernel arguments."""
-    seen = set()
-    for chunk in re.split(r"\n(?=_Z\w+:\s+; @)", text):
-        m = re.match(r"(_Z\w+):", chunk)
-        if not m or "k_clearance" not in m.group(1):
-            continue
-        seen.add(re.search(r"(k_clearance_\w+?)ILb([01])", m.group(1)).groups())
-        scratch = re.search(r"; ScratchSize: (\d+)", chunk)
-        assert scratch and int(scratch.group(1)) == 0, m.group(1)
-        body = chunk.split(".section")[0]
-        assert not re.search(r"\t(flat|global|buffer)_load", body), m.group(1)
-        loaded = set(re.findall(r"\ts_load_dwordx[24] s\[(\d+):\d+\]", body))       # pointers read from memory
-        wide = collections.Counter(re.findall(r"\ts_load_dwordx(?:8|16) s\[\d+:\d+\], s\[(\d+):\d+\]", body))
-        assert any(n >= 2 and base in loaded for base, n in wide.items()), m.group(1)
-    return seen
-
-
-def test_clearance_kernels_keep_their_records_in_scalar_registers(tmp_path):
-    from codecad_amd.hip_util import builder
-    hipcc = builder.find_hipcc()
-    if hipcc is None:
-        pytest.skip("no hipcc in this environment")
-    assert "clearance.hip" in builder.SOURCES and "clearance.hip" not in builder.FLAGGED_SOURCES
-    out = tmp_path / "clearance.s"
-    flags = [f for f in builder.HIPCC_FLAGS if f != "-fPIC"]
-    subprocess.run([hipcc] + flags + ["-I", builder.INCLUDE, "--cuda-device-only", "-S", "-o", str(out),
-                                      os.path.join(builder.CSRC, "clearance.hip")], check=True, capture_output=True)
-    assert check_clearance_isa(out.read_text()) == {(k, v) for k in ("k_clearance_cells", "k_clearance_leaf",
-                                                                     "k_clearance_witness") for v in "01"}
 
 
 def test_clearance_entry_points_reject_bad_arguments():

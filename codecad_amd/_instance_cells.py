@@ -131,15 +131,17 @@ def instance_tape(instance):
     return tape
 
 
-def device_table(instances, queue):
-    """(device table of the instances' uploaded tapes, distance_only, lane_bytes): hu_interference_table."""
+def device_table(instances, queue, full_programs=False):
+    """(device table of the instances' uploaded tapes, distance_only, lane_bytes): hu_instance_table.  The checks take
+    what it chooses (every instance's distance-only program when all have one); `full_programs` asks for the full
+    programs whatever the instances have (the ray caster over instances follows their directions)."""
     tapes = [instance_tape(i) for i in instances]
     n = len(tapes)
     handles = (ctypes.c_void_p * n)(*(t.device_ptr for t in tapes))
     host_table = numpy.zeros(n * _TABLE_RECORD, dtype=numpy.uint8)
     distance_only, lane_bytes = ctypes.c_int(0), ctypes.c_uint32(0)
-    check(hip_manager.lib.hu_interference_table(handles, n, host_table.ctypes.data, host_table.nbytes,
-                                                ctypes.byref(distance_only), ctypes.byref(lane_bytes)), "hu_interference_table")
+    check(hip_manager.lib.hu_instance_table(handles, n, int(bool(full_programs)), host_table.ctypes.data, host_table.nbytes,
+                                            ctypes.byref(distance_only), ctypes.byref(lane_bytes)), "hu_instance_table")
     table = hip_util.Buffer(numpy.uint8, (host_table.size,), queue=queue)
     table.enqueue_write(host_table)
     return table, distance_only.value, lane_bytes.value

@@ -194,6 +194,7 @@ int ensure_attrs()
     if ((rc = ensure_attrs_n<2>())) return rc;
     HU_HIP(hu_render::allow_big_lds(kMaxLds));   // the ray caster and the bitmap kernels (render.hip)
     HU_HIP(hu_cells::allow_big_lds(kMaxLds));          // (instance_pairs.hip)
+    HU_HIP(hu_cells::allow_big_lds_rays(kMaxLds));     // (instance_rays.hip)
     done_for_device = dev;
     return HU_OK;
 }
@@ -1086,10 +1087,16 @@ int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_d
 int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, size_t bytes, int* distance_only_out,
                           uint32_t* lane_bytes)
 {
+    return hu_instance_table(tapes, n, 0, table_host, bytes, distance_only_out, lane_bytes);
+}
+
+int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void* table_host, size_t bytes, int* distance_only_out,
+                      uint32_t* lane_bytes)
+{
     if (!tapes || !table_host || !distance_only_out || !lane_bytes) return fail(HU_ERR_BAD_ARG, "NULL argument");
     if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "an interference table holds 1..64 instances");
     if (bytes < (size_t)n * sizeof(hu_cells::InstanceRec)) return fail(HU_ERR_BAD_ARG, "table buffer too small");
-    bool all_do = true;
+    bool all_do = !full_programs;
     for (uint32_t i = 0; i < n; ++i) {
         if (!tapes[i]) return fail(HU_ERR_BAD_ARG, "NULL tape");
         all_do = all_do && distance_only(tapes[i]);
@@ -1291,6 +1298,61 @@ int hu_ray_caster(hu_tape t, const float origin[4], const float forward[4], cons
         return HU_OK;
     }
     HU_HIP(hu_render::ray_caster(InterpEval<false>{ls.prog, t->extra_dev, ls.n4}, a, (uint32_t)blocks, ls.block, ls.lds, (hipStream_t)stream));
+    return HU_OK;
+}
+
+int hu_ray_caster_instances(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const float origin[4],
+                            const float forward[4], const float up[4], const float right[4], float pixel_tolerance,
+                            float box_radius, float min_distance, float max_distance, float floor_z, uint32_t render_options,
+                            uint32_t width, uint32_t height, const void* colors_dev, void* out_dev, int32_t* part_ids_dev,
+                            float* depth_dev, uint32_t flags, uint64_t* counters_dev, void* stream)
+{
+    if (!table_dev || !origin || !forward || !up || !right || !colors_dev || !out_dev || !part_ids_dev || !depth_dev)
+        return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n == 0 || n > 64u) return fail(HU_ERR_BAD_ARG, "1..64 instances");
+    if (distance_only_kernel) return fail(HU_ERR_BAD_ARG, "the ray caster needs a table of full programs (hu_instance_table)");
+    if (lane_bytes == 0 || lane_bytes % 16u) return fail(HU_ERR_BAD_ARG, "lane_bytes of a table of full programs is a multiple of 16");
+    if (width == 0 || height == 0) return fail(HU_ERR_BAD_ARG, "image must have at least one pixel");
+    if (render_options > 3u) return fail(HU_ERR_BAD_ARG, "unknown render option bits");
+    if (flags > 1u) return fail(HU_ERR_BAD_ARG, "unknown flag bits");
+    // A lane's LDS: the register file every instance's program fits and one float per instance (instance_rays.hip).  The
+    // workgroup is the largest of 256, 128, 64 lanes that keeps it within 48 KiB (three workgroups or more per CU), the rule
+    // of cells_launch() and launch_shape().
+    const size_t per_lane = (size_t)lane_bytes + 4u * n;
+    uint32_t block = 256;
+    while (block > 64u && per_lane * block > 48 * 1024) block >>= 1;
+    const size_t regfile = (size_t)lane_bytes * block, lds = per_lane * block + kScratchBytes;
+    if (lds > kMaxLds)
+        return fail(HU_ERR_UNSUPPORTED, "an instance keeps more values live than fit the 160 KiB LDS register file");
+    int rc;
+    if ((rc = ensure_attrs())) return rc;
+    const uint64_t tiles = (uint64_t)((width + 7u) / 8u) * ((height + 7u) / 8u);
+    const uint64_t blocks = (tiles + block / 64u - 1) / (block / 64u);
+    if (blocks > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "image too large for one launch");
+    RayCasterArgs a;
+    a.origin = mk3(origin[0], origin[1], origin[2]);
+    a.forward = mk3(forward[0], forward[1], forward[2]);
+    a.up = mk3(up[0], up[1], up[2]);
+    a.right = mk3(right[0], right[1], right[2]);
+    a.pixel_tolerance = pixel_tolerance;
+    a.box_radius = box_radius;
+    a.min_distance = min_distance;
+    a.max_distance = max_distance;
+    a.floor_z = floor_z;
+    a.options = render_options;
+    a.w = width;
+    a.h = height;
+    a.out = static_cast<uint8_t*>(out_dev);
+    hu_cells::RayArgs t;
+    t.table = static_cast<const hu_cells::InstanceRec*>(table_dev);
+    t.n_instances = n;
+    t.colors = static_cast<const float4*>(colors_dev);
+    t.part_ids = part_ids_dev;
+    t.depth = depth_dev;
+    t.counters = reinterpret_cast<unsigned long long*>(counters_dev);
+    t.flags = flags;
+    t.bounds_offset = (uint32_t)regfile;
+    HU_HIP(hu_cells::ray_caster_instances(t, a, (uint32_t)blocks, block, lds, (hipStream_t)stream));
     return HU_OK;
 }
 

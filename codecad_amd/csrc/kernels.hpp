@@ -953,16 +953,17 @@ __device__ __forceinline__ void light_no_trace(F3 normal, F3 to_light, F3 to_cam
     s *= s; s *= s; s *= s;
     specular = s;
 }
-// ray_caster.cl:118-131
-__device__ __forceinline__ F3 map_color(float ambient, float diffuse, float specular)
+// ray_caster.cl:118-131, the hue a parameter: the reference's flat colour is c = default_hue(), for which chroma * c + m is
+// its X + m, chroma + m, 0 + m bit for bit (chroma * 1 and chroma * 0 are exact, chroma >= +0, and nothing is contracted)
+__device__ __forceinline__ F3 default_hue() { return mk3(0.7f, 1.0f, 0.0f); }
+__device__ __forceinline__ F3 map_color(float ambient, float diffuse, float specular, F3 c)
 {
     const float saturation = 0.75f * smoothstepf(0.0f, 0.25f, diffuse);
     const float value = 0.1f + 0.8f * mixf(diffuse, ambient, 0.3f);
     const float chroma = value * saturation;
-    const float X = chroma * 0.7f;
     const float m = value - chroma;
     const float sp = specular * 128.0f;
-    return mk3(255.0f * (X + m) + sp, 255.0f * (chroma + m) + sp, 255.0f * (0.0f + m) + sp);
+    return mk3(255.0f * (chroma * c.x + m) + sp, 255.0f * (chroma * c.y + m) + sp, 255.0f * (chroma * c.z + m) + sp);
 }
 // ray_caster.cl:133-144
 __device__ __forceinline__ F3 map_color_zebra(F3 point, float ambient, float diffuse, float specular)
@@ -980,9 +981,15 @@ __device__ __forceinline__ F3 map_color_zebra(F3 point, float ambient, float dif
 // every lane is done: lanes in different phases share each pass through the tape, the
 // interpreter is instantiated once, and a pixel still sees exactly the reference's sequence of
 // evaluations (pixels are independent).
-template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E ev, const RayCasterArgs a)
+//
+// WHAT is rendered is the scene S, so that the sequence is written once for a single shape (OneShape below) and for the
+// instances of an assembly (instance_rays.hip):
+//   evaluate(p, lds, active, id)  the field at p; may set `id`, the part the value came from (`active`: the lane is not done)
+//   flat_color(id, ambient, diffuse, specular)  the colour of a lit pixel of part `id` without render options
+//   pixel(px, py, hit, id, distance)  what a finished pixel records beside its colour: whether the primary ray hit, the
+//     part of its last evaluation and the distance at the end of the primary march
+template <class S> __device__ __forceinline__ void ray_caster_pixels(S& scene, const RayCasterArgs& a, void* lds)
 {
-    extern __shared__ float4 lds[];
     enum Phase : uint32_t { PRIMARY, RESIDUAL, AO, LIGHT, FLOOR, DONE };
     const uint32_t tiles_y = (a.h + 7u) >> 3;
     const uint32_t tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
@@ -1001,6 +1008,7 @@ template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E e
     // primary march
     float distance = a.min_distance, fallback = a.min_distance;
     float4 pe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // last primary evaluation
+    uint32_t id = 0, pid = 0;                           // ... and the part it came from
     uint32_t step = 0;
     bool hit = false;
     // after the march
@@ -1024,7 +1032,7 @@ template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E e
         case FLOOR: p = add3(a.origin, mul3(direction, floor_distance)); break;
         default: break;
         }
-        const float4 e = sdf::voxel(ev(p.x, p.y, p.z, lds), 0);
+        const float4 e = scene.evaluate(p, lds, phase != DONE, id);
 
         // 0 = stay in the phase; otherwise the transition this evaluation triggers
         enum Next : uint32_t { STAY, END_PRIMARY, BEGIN_LIGHT, END_LIGHT, BEGIN_FLOOR, WRITE };
@@ -1033,6 +1041,7 @@ template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E e
 
         if (phase == PRIMARY) {  // ray_caster.cl:168-196
             pe = e;
+            pid = id;
             if (distance - fallback > e.w) {
                 distance = fallback;
                 if (++step == kPrimaryMaxSteps) next = END_PRIMARY;
@@ -1127,7 +1136,7 @@ template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E e
                 light_no_trace(normal, to_light2, to_camera, d2, s2);
                 const float d = 0.8f * diffuse + 0.2f * d2;
                 const float s = 0.8f * specular + 0.2f * s2;
-                color = (a.options & kZebra) ? map_color_zebra(point, ambient, d, s) : map_color(ambient, d, s);
+                color = (a.options & kZebra) ? map_color_zebra(point, ambient, d, s) : scene.flat_color(pid, ambient, d, s);
             }
             next = BEGIN_FLOOR;
         }
@@ -1138,9 +1147,28 @@ template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E e
         }
         if (next == WRITE) {
             store_rgb(a.out + ((size_t)py + (size_t)a.h * px) * 3, color);
+            scene.pixel(px, py, hit, pid, distance);
             phase = DONE;
         }
     }
+}
+
+// one shape through the evaluator E: the reference's picture
+template <class E> struct OneShape {
+    const E& ev;
+    __device__ __forceinline__ float4 evaluate(F3 p, void* lds, bool, uint32_t&) const { return sdf::voxel(ev(p.x, p.y, p.z, lds), 0); }
+    __device__ __forceinline__ F3 flat_color(uint32_t, float ambient, float diffuse, float specular) const
+    {
+        return map_color(ambient, diffuse, specular, default_hue());
+    }
+    __device__ __forceinline__ void pixel(uint32_t, uint32_t, bool, uint32_t, float) const {}
+};
+
+template <class E> __global__ void __launch_bounds__(256) k_ray_caster(const E ev, const RayCasterArgs a)
+{
+    extern __shared__ float4 lds[];
+    OneShape<E> scene{ev};
+    ray_caster_pixels(scene, a, lds);
 }
 
 // bitmap.cl:1-18: one pixel per lane, y fastest like the output

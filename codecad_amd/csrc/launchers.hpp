@@ -9,6 +9,7 @@
 //                 nothing but the interpreter's wave-uniform loop around branch-free ops;
 //   instance_pairs.hip  the interference and clearance checks between the instances of an assembly, built without
 //                 it as well;
+//   instance_rays.hip   the ray caster over the instances of an assembly (codecad_amd/rendering/assembly_picture.py), likewise;
 // Each function enqueues one launch and returns hipGetLastError().
 #pragma once
 
@@ -88,7 +89,22 @@ struct Args {
 
 enum Kernel { kInterferenceCells, kInterferenceLeaf, kClearanceCells, kClearanceLeaf, kClearanceWitness, kKernels };
 
+// the ray caster over the instance table (instance_rays.hip): what it takes beside sdfk::RayCasterArgs
+struct RayArgs {
+    const InstanceRec* table;        // every instance's FULL program (directions steer the march)
+    uint32_t n_instances;
+    const float4* colors;            // n_instances hues {r, g, b, unused} in [0, 1]
+    int32_t* part_ids;               // [w * h], index y + h * x like the pixels: the instance under the pixel, -1 for none
+    float* depth;                    // [w * h]: the primary ray's distance where it hit, +inf where not
+    unsigned long long* counters;    // NULL, or {instance programs run, instance programs asked for}, added up per wavefront
+    uint32_t flags;                  // bit 0: every instance at every sample (no skipping)
+    uint32_t bounds_offset;          // bytes of LDS taken by the register file; the lanes' bounds follow, [instance][lane]
+};
+constexpr uint32_t kRaysNoSkip = 1u;
+
 hipError_t allow_big_lds(size_t bytes);
+hipError_t allow_big_lds_rays(size_t bytes);
+hipError_t ray_caster_instances(const RayArgs& t, const sdfk::RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 
 }  // namespace hu_cells

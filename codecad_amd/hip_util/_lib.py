@@ -58,12 +58,15 @@ PROTOTYPES = {
     "hu_mass_properties_level_owned": [_vp, _vp, _vp, _u32, _d, _u3, _f, _f, _vp, _vp, _vp, _u32, _u32, _u32, _vp],
     "hu_mass_integrals_indirect": [_vp, _vp, _vp, _u32, _d, _vp, _u32, _vp],
     "hu_interference_table": [_c.POINTER(_vp), _u32, _vp, _sz, _c.POINTER(_i), _c.POINTER(_u32)],
+    "hu_instance_table": [_c.POINTER(_vp), _u32, _i, _vp, _sz, _c.POINTER(_i), _c.POINTER(_u32)],
     "hu_interference_cells_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
     "hu_interference_leaf_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _vp, _vp, _vp],
     "hu_clearance_cells_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
     "hu_clearance_leaf_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _f, _vp, _vp, _vp],
     "hu_clearance_witness_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _f, _vp, _vp, _vp],
     "hu_ray_caster": [_vp, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp],
+    "hu_ray_caster_instances": [_vp, _u32, _i, _u32, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp, _vp, _vp,
+                                _u32, _vp, _vp],
     "hu_bitmap": [_vp, _f4, _f, _u32, _u32, _vp, _vp],
     "hu_process_polygon": [_f4, _f, _vp, _u3, _vp, _vp, _vp, _vp, _vp],
     "hu_process_polygon_blocks": [_vp, _vp, _u32, _d, _d3, _f, _u3, _vp, _vp, _vp, _vp, _vp],

@@ -208,6 +208,17 @@ class _Kernels:
             float(min_distance), float(max_distance), float(floor_z), int(render_options), int(global_size[0]),
             int(global_size[1]), _ptr(output), s), "hu_ray_caster"))
 
+    def ray_caster_instances(self, global_size, local_size, table, n, distance_only, lane_bytes, origin, forward, up, right,
+                             pixel_tolerance, box_radius, min_distance, max_distance, floor_z, render_options, colors, output,
+                             part_ids, depth, flags=0, counters=None, wait_for=None, queue=None):
+        """ray_caster over the instance table of an assembly (rendering/assembly_picture.py); global_size = (width, height)."""
+        v = [_float4(x) for x in (origin, forward, up, right)]
+        return self._launch(wait_for, queue, lambda s: check(self._m.lib.hu_ray_caster_instances(
+            _ptr(table), int(n), int(distance_only), int(lane_bytes), *[x.ctypes.data_as(_lib._f4) for x in v],
+            float(pixel_tolerance), float(box_radius), float(min_distance), float(max_distance), float(floor_z),
+            int(render_options), int(global_size[0]), int(global_size[1]), _ptr(colors), _ptr(output), _ptr(part_ids),
+            _ptr(depth), int(flags), _ptr(counters), s), "hu_ray_caster_instances"))
+
     def bitmap(self, global_size, local_size, scene, origin, step_size, output, wait_for=None, queue=None):
         """rendering/bitmap.cl:1-4; global_size = (width, height)."""
         _note(scene, global_size, group=SPEC_RENDER)

@@ -213,6 +213,11 @@ int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_d
  * evaluations they perform to *evaluations_dev. */
 int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, size_t bytes, int* distance_only,
                           uint32_t* lane_bytes);
+/* The same table for a caller that says which programs it wants: full_programs != 0 writes every instance's FULL
+ * program (*distance_only = 0) whether or not all have a distance-only one -- the ray caster over instances needs the
+ * directions --; full_programs = 0 is hu_interference_table. */
+int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void* table_host, size_t bytes,
+                      int* distance_only, uint32_t* lane_bytes);
 int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
                                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
                                    uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
@@ -261,6 +266,23 @@ int hu_ray_caster(hu_tape t, const float origin[4], const float forward[4], cons
                   const float right[4], float pixel_tolerance, float box_radius, float min_distance,
                   float max_distance, float floor_z, uint32_t render_options, uint32_t width,
                   uint32_t height, void* out_dev, void* stream);
+/* The same ray caster over the instances of an assembly (codecad_amd/rendering/assembly_picture.py; the reference
+ * renders an assembly as one union).  The table arguments are those of the interference entry points, from
+ * hu_instance_table with full_programs = 1 (distance_only must be 0); then hu_ray_caster's.  The field at a point is the
+ * least instance's value, the instance the LOWEST index that attains it.  colors_dev: n float4 {r, g, b, unused} in
+ * [0, 1], the hue of each instance's flat colour ((0.7, 1, 0) is hu_ray_caster's).  out_dev as hu_ray_caster's;
+ * part_ids_dev: int32[width*height], pixel (x, y) at y + height*x: the instance of the primary ray's last evaluation
+ * where it hit, -1 where it did not; depth_dev: float[width*height], the distance along the primary ray where it hit,
+ * +inf where not.  flags bit 0: evaluate every instance at every sample (else an instance whose last value and the
+ * path travelled since prove that it cannot be the least is left out: the same bytes, |grad w| <= 1 assumed).
+ * counters_dev: NULL, or two uint64 the launch adds to: instance programs run, instance programs asked for (samples x
+ * n), both per wavefront.  Allocates nothing, synchronises nothing. */
+int hu_ray_caster_instances(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                            const float origin[4], const float forward[4], const float up[4], const float right[4],
+                            float pixel_tolerance, float box_radius, float min_distance, float max_distance,
+                            float floor_z, uint32_t render_options, uint32_t width, uint32_t height,
+                            const void* colors_dev, void* out_dev, int32_t* part_ids_dev, float* depth_dev,
+                            uint32_t flags, uint64_t* counters_dev, void* stream);
 /* rendering/bitmap.cl:1-4, launched by rendering/bitmap.py:22-26: inside/outside picture of a 2D
  * shape, sample (x, y) at origin + step_size*(x, height-y-1).  out_dev as above. */
 int hu_bitmap(hu_tape t, const float origin[4], float step_size, uint32_t width, uint32_t height,

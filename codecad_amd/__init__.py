@@ -8,7 +8,9 @@ Public layout mirrors the reference package (reference codecad/__init__.py:1-11)
 `util`, `nodes`, `hip_util` (in place of `cl_util`), `grid_eval`, `subdivision`,
 `mass_properties`, `assembly` (assemblies.py) and the renderers the package has (`rendering`);
 `interference(asm, resolution)` finds the overlapping instances of an assembly on the device, and
-`clearance(asm, resolution, min_gap)` the pairs closer than a gap, with how close and where (clearance.py).
+`clearance(asm, resolution, min_gap)` the pairs closer than a gap, with how close and where (clearance.py);
+`section(asm, plane, resolution)` cuts an assembly with a `Plane`: which part owns each sample of the cut, where parts
+overlap on it, and the cut area of every part and pair (section.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -25,7 +27,8 @@ from . import assemblies  # noqa: F401
 from .assemblies import assembly  # noqa: F401
 from .interference import interference, InterferenceReport  # noqa: F401
 from .clearance import clearance, ClearanceReport, NearMiss  # noqa: F401
+from .section import section, Section, Plane  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
-           "ClearanceReport", "NearMiss"]
+           "ClearanceReport", "NearMiss", "section", "Section", "Plane"]

@@ -66,10 +66,12 @@ def checked_lattice(instances, resolution, grow=0.0):
     return corner, step, dims
 
 
-def top_side(dims):
-    side = 16
+def top_side(dims, first=16, factor=4):
+    """The side of the top level's cells: `first` samples, times `factor` (a level's cells per axis: 4 for the cubic
+    cells of the checks, 8 for the square tiles of a section) while there would be too many of them."""
+    side = first
     while numpy.prod(-(-dims // side)) > _MAX_TOP_CELLS:
-        side *= 4
+        side *= factor
     return side
 
 
@@ -86,15 +88,18 @@ def windows(instances, corner, step, dims, grow=0.0):
     return out
 
 
-def cell_rows(wins, dims, side):
-    """Rows of the top level: cells of `side` samples that two windows or more reach."""
+def cell_rows(wins, dims, side, least=2):
+    """Rows of the top level: cells of `side` samples that `least` windows or more reach (a section keeps a tile that one
+    window reaches, and gives an instance that is no candidate anywhere an empty window, lo > hi)."""
     n_cells = -(-dims // side)
     masks = numpy.zeros(tuple(int(n) for n in n_cells), dtype=numpy.uint64)
     for n, (lo, hi) in enumerate(wins):
+        if (lo > hi).any():
+            continue
         lo, hi = lo // side, hi // side
         masks[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1] |= numpy.uint64(1 << n)
     bits = numpy.unpackbits(masks.view(numpy.uint8).reshape(masks.shape + (8,)), axis=-1).sum(axis=-1)
-    idx = numpy.argwhere(bits >= 2)
+    idx = numpy.argwhere(bits >= least)
     rows = numpy.zeros((len(idx), 4), dtype=numpy.uint32)
     if len(idx):
         m = masks[tuple(idx.T)]
@@ -147,13 +152,14 @@ def device_table(instances, queue, full_programs=False):
     return table, distance_only.value, lane_bytes.value
 
 
-def levels(side, n_top, initial_capacity):
-    """(sides of the cells of every level above the finest one, the first capacity of every level's child list)."""
+def levels(side, n_top, initial_capacity, factor=4):
+    """(sides of the cells of every level above the finest one, the first capacity of every level's child list); a cell
+    has `factor` children per axis, 64 in all: 4^3 (the checks) or 8^2 (a section's tiles)."""
     sides = []
     s = side
-    while s > 4:
+    while s > factor:
         sides.append(s)
-        s //= 4
+        s //= factor
     capacities = subdivision.first_capacities([64] * len(sides), n_top=n_top, row_bytes=_ROW)
     if initial_capacity is not None:
         capacities = [subdivision.checked_capacity(min(c, max(1, int(initial_capacity)))) for c in capacities]
@@ -161,7 +167,7 @@ def levels(side, n_top, initial_capacity):
 
 
 def _run(table, n, distance_only, lane_bytes, wins, top, sides, corner, step, dims, capacities, queue, pair_dtype, pair_init, thr,
-         cells, finest):
+         cells, finest, factor, frame):
     """Every level enqueued back to back, ONE synchronisation -> (list counts, evaluations, pair accumulators)."""
     lib = hip_manager.lib
     n_levels = len(sides)                   # levels of cells above the finest one
@@ -184,17 +190,17 @@ def _run(table, n, distance_only, lane_bytes, wins, top, sides, corner, step, di
     evaluations = results.device_ptr + 16 * n_levels
     instances = (table.device_ptr, n, distance_only, lane_bytes) + (() if wins is None else (wins.device_ptr,))
     for level, (side, capacity) in enumerate(zip(sides, capacities)):
-        child = side // 4
+        child = side // factor
         children = hip_util.Buffer(numpy.uint32, (capacity + 1, 4), queue=queue)
         check(lib.hu_memset(children.device_ptr, 0, 16, queue.handle), "hu_memset")
-        check(getattr(lib, cells)(*instances, parents.device_ptr + 16, parents.device_ptr, max_parents, child, d, c, step,
+        check(getattr(lib, cells)(*instances, parents.device_ptr + 16, parents.device_ptr, max_parents, child, d, c, *frame, step,
                                   thr(child), children.device_ptr, children.device_ptr + 16, capacity, evaluations,
                                   queue.handle), cells)
         check(lib.hu_memcpy_d2d(results.device_ptr + 16 * level, children.device_ptr, 16, queue.handle), "hu_memcpy_d2d")
         buffers.append(children)
         parents, max_parents = children, capacity
     for name, extra in finest:              # in this order, on the one stream
-        check(getattr(lib, name)(*instances, parents.device_ptr + 16, parents.device_ptr, max_parents, d, c, step, *extra,
+        check(getattr(lib, name)(*instances, parents.device_ptr + 16, parents.device_ptr, max_parents, d, c, *frame, step, *extra,
                                  results.device_ptr + head, evaluations, queue.handle), name)
     got = results.read()                    # the one synchronisation
     for b in buffers + [results]:
@@ -203,7 +209,8 @@ def _run(table, n, distance_only, lane_bytes, wins, top, sides, corner, step, di
     return counts, int(got[16 * n_levels:head].view(numpy.uint64)[0]), got[head:].view(pair_dtype).reshape(n, n).copy()
 
 
-def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dtype, pair_init, thr, cells, finest, wins=None):
+def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dtype, pair_init, thr, cells, finest, wins=None,
+             factor=4, frame=()):
     """The traversal from the top-level rows `top` (cells of `side` samples), run again with larger lists while one
     overflowed -> (evaluations of the last run, pair accumulators [n, n], runs).  What the check decides: `pair_dtype`
     and `pair_init` ({field: initial value}) of the accumulators; `thr`, child side -> float32 threshold of a level;
@@ -218,12 +225,12 @@ def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dt
         host_wins = numpy.ascontiguousarray(wins.reshape(n, 6).astype(numpy.uint32))
         wins_dev = hip_util.Buffer(numpy.uint32, host_wins.shape, queue=queue)
         wins_dev.enqueue_write(host_wins)
-    sides, capacities = levels(side, len(top), initial_capacity)
+    sides, capacities = levels(side, len(top), initial_capacity, factor)
     runs = 0
     while True:
         runs += 1
         counts, evaluations, acc = _run(table, n, distance_only, lane_bytes, wins_dev, top, sides, corner, step, dims, capacities,
-                                        queue, pair_dtype, pair_init, thr, cells, finest)
+                                        queue, pair_dtype, pair_init, thr, cells, finest, factor, frame)
         if all(k <= c for k, c in zip(counts, capacities)):
             break
         capacities = [subdivision.checked_capacity(max(c, int(k * 1.125) + 16)) for k, c in zip(counts, capacities)]
@@ -238,13 +245,14 @@ def index_position(corner, step, index):
     return util.Vector(*(float(corner[k] + step * numpy.float32(index[k])) for k in range(3)))
 
 
-def pair_fields(acc, corner, step):
-    """[(PairFields, accumulator)] of the pairs i < j with samples, ordered by (i, j), from the accumulators [n, n]."""
+def pair_fields(acc, corner, step, diagonal=False):
+    """[(PairFields, accumulator)] of the pairs i < j with samples, ordered by (i, j), from the accumulators [n, n];
+    `diagonal`: and of the entries [i, i] (a section keeps the samples inside instance i there)."""
     out = []
     cell = float(step) ** 3
     n = len(acc)
     for i in range(n):
-        for j in range(i + 1, n):
+        for j in range(i if diagonal else i + 1, n):
             a = acc[i, j]
             count = int(a["sums"][0])
             if count == 0:

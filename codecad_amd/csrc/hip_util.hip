@@ -195,6 +195,7 @@ int ensure_attrs()
     HU_HIP(hu_render::allow_big_lds(kMaxLds));   // the ray caster and the bitmap kernels (render.hip)
     HU_HIP(hu_cells::allow_big_lds(kMaxLds));          // (instance_pairs.hip)
     HU_HIP(hu_cells::allow_big_lds_rays(kMaxLds));     // (instance_rays.hip)
+    HU_HIP(hu_cells::allow_big_lds_section(kMaxLds));  // (instance_section.hip)
     done_for_device = dev;
     return HU_OK;
 }
@@ -1123,8 +1124,8 @@ namespace {
 // Workgroup size for a launch over instance cells: four wavefronts (four cells) while their register file fits 48 KiB, as
 // launch_shape() sizes the one-voxel interpreter kernels; the LDS holds the largest instance's file.  `extra_lane_bytes`
 // follow it and count against the same 48 KiB: clearance's w area at the finest level, 4 bytes per instance and lane.
-int cells_launch(hu_cells::Kernel kernel, int distance_only_kernel, uint32_t lane_bytes, size_t extra_lane_bytes, hu_cells::Args& a,
-                 void* stream)
+// `launch(blocks, block, lds)` enqueues the kernel.
+extern "C++" template <class Launch> int cells_launch(uint32_t lane_bytes, size_t extra_lane_bytes, hu_cells::Args& a, Launch launch)
 {
     const size_t per_lane = (size_t)lane_bytes + extra_lane_bytes;
     uint32_t block = 256;
@@ -1138,8 +1139,16 @@ int cells_launch(hu_cells::Kernel kernel, int distance_only_kernel, uint32_t lan
     const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
     if (blocks == 0) return HU_OK;
     if (blocks > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
-    HU_HIP(hu_cells::level(kernel, distance_only_kernel != 0, a, (uint32_t)blocks, block, lds, (hipStream_t)stream));
+    HU_HIP(launch((uint32_t)blocks, block, lds));
     return HU_OK;
+}
+
+int cells_launch(hu_cells::Kernel kernel, int distance_only_kernel, uint32_t lane_bytes, size_t extra_lane_bytes, hu_cells::Args& a,
+                 void* stream)
+{
+    return cells_launch(lane_bytes, extra_lane_bytes, a, [&](uint32_t blocks, uint32_t block, size_t lds) {
+        return hu_cells::level(kernel, distance_only_kernel != 0, a, blocks, block, lds, (hipStream_t)stream);
+    });
 }
 
 // What every entry point over instance cells checks and fills.  The entry points of `clearance` also want the windows,
@@ -1258,6 +1267,79 @@ int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distanc
 {
     return cells_finest(hu_cells::kClearanceWitness, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev,
                         n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+}
+
+namespace {
+
+// What both entry points of the section check and fill: cells_args() of a lattice {dims u, dims v, 1} with windows, and the
+// plane's frame.
+int section_args(const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                 uint32_t max_parents, const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], float step,
+                 uint64_t* evaluations_dev, hu_cells::SectionArgs& t)
+{
+    if (!dims || !u || !v) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    const uint32_t dims3[3] = {dims[0], dims[1], 1u};
+    std::memset(&t, 0, sizeof(t));
+    int rc;
+    if ((rc = cells_args(true, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims3, corner, step, evaluations_dev, t.c)))
+        return rc;
+    if ((uint64_t)dims[0] * dims[1] > (1ull << 28)) return fail(HU_ERR_BAD_ARG, "a section holds at most 2^28 samples");
+    for (int i = 0; i < 3; ++i) {
+        if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(corner[i])) return fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
+        t.u[i] = u[i];
+        t.v[i] = v[i];
+    }
+    return HU_OK;
+}
+
+}  // namespace
+
+int hu_section_tiles(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
+                     const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
+                     const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], int with_distance, float step,
+                     float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity, uint64_t* evaluations_dev,
+                     void* stream)
+{
+    hu_cells::SectionArgs t;
+    int rc;
+    if ((rc = section_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, step, evaluations_dev, t)))
+        return rc;
+    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (child_side < 8u || child_side > 8192u || (child_side & (child_side - 1u)))
+        return fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 8..8192");
+    if (std::isnan(radius) || radius < 0.0f) return fail(HU_ERR_BAD_ARG, "radius must not be negative");
+    t.c.child_side = child_side;
+    t.c.thr = radius;
+    t.c.counter = counter_dev;
+    t.c.children = static_cast<uint4*>(children_dev);
+    t.c.capacity = capacity;
+    // WITH_DISTANCE keeps every candidate's w at the children's centres: 4 bytes per instance and lane after the register file
+    return cells_launch(lane_bytes, with_distance ? 4u * n : 0u, t.c, [&](uint32_t blocks, uint32_t block, size_t lds) {
+        return hu_cells::section(false, distance_only_kernel != 0, with_distance != 0, t, blocks, block, lds, (hipStream_t)stream);
+    });
+}
+
+int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
+                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
+                    const float corner[3], const float u[3], const float v[3], int with_distance, float step, int32_t* part_ids_dev,
+                    uint8_t* inside_count_dev, float* distance_dev, int32_t* nearest_dev, void* acc_dev, uint64_t* evaluations_dev,
+                    void* stream)
+{
+    hu_cells::SectionArgs t;
+    int rc;
+    if ((rc = section_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, step, evaluations_dev, t)))
+        return rc;
+    if (!part_ids_dev || !inside_count_dev || !acc_dev || (with_distance && (!distance_dev || !nearest_dev)))
+        return fail(HU_ERR_BAD_ARG, "NULL argument");
+    t.c.child_side = 1u;
+    t.c.pairs = acc_dev;
+    t.part_ids = part_ids_dev;
+    t.inside_count = inside_count_dev;
+    t.distance = distance_dev;
+    t.nearest = nearest_dev;
+    return cells_launch(lane_bytes, 0u, t.c, [&](uint32_t blocks, uint32_t block, size_t lds) {
+        return hu_cells::section(true, distance_only_kernel != 0, with_distance != 0, t, blocks, block, lds, (hipStream_t)stream);
+    });
 }
 
 int hu_ray_caster(hu_tape t, const float origin[4], const float forward[4], const float up[4], const float right[4],

@@ -1,5 +1,6 @@
 // codecad_amd/csrc/instance_cells.hpp -- what a kernel over the instances of an assembly is made of (instance_pairs.hip):
-// a wavefront's cell row, the table of the instances' programs and the box of a lane mask.
+// a wavefront's cell row, the table of the instances' programs, the box of a lane mask and the accumulators of a pair
+// (instance_section.hip builds the section of an assembly from the same pieces, over square tiles of a plane).
 //
 // A CELL is a cube of 4^k lattice samples, a 16-byte row {x0 | y0 << 16, z0, mask lo, mask hi}: its first sample's indices
 // and the 64-bit mask of the instances still candidates in it.  One wavefront takes one cell, lane = 16 x + 4 y + z of its
@@ -62,6 +63,40 @@ __device__ __forceinline__ void mask_box(uint64_t m, uint32_t (&lo)[3], uint32_t
     lo[0] = (uint32_t)__builtin_ctzll(m) >> 4;  hi[0] = (63u - (uint32_t)__builtin_clzll(m)) >> 4;
     lo[1] = (uint32_t)__builtin_ctz(ys);        hi[1] = 31u - (uint32_t)__builtin_clz(ys);
     lo[2] = (uint32_t)__builtin_ctz(zs);        hi[2] = 31u - (uint32_t)__builtin_clz(zs);
+}
+
+// f(i, j, both, b) for every pair i < j of `present` (wave-uniform) some lane has both of in its bitmask `mine`: `both`
+// says whether this lane does, `b` is its ballot
+template <class F> __device__ __forceinline__ void for_pairs(uint64_t present, uint64_t mine, F f)
+{
+    for (uint64_t mi = present; mi != 0ull; mi &= mi - 1ull) {
+        const uint32_t i = uniform((uint32_t)__builtin_ctzll(mi));
+        for (uint64_t mj = mi & (mi - 1ull); mj != 0ull; mj &= mj - 1ull) {
+            const uint32_t j = uniform((uint32_t)__builtin_ctzll(mj));
+            const bool both = ((mine >> i) & (mine >> j) & 1ull) != 0ull;
+            const uint64_t b = __ballot(both);
+            if (b == 0ull) continue;                              // wave-uniform
+            f(i, j, both, b);
+        }
+    }
+}
+
+// the lanes of `b` (this lane: `both`, its sample at the indices x, y, z) added to an accumulator's count, index sums and
+// index box; lo and hi are the least and the greatest index per axis among the samples of b (wave-uniform)
+template <class Acc>
+__device__ __forceinline__ void add_samples(Acc* acc, bool both, uint64_t b, uint32_t lane, uint32_t x, uint32_t y, uint32_t z,
+                                            const uint32_t (&lo)[3], const uint32_t (&hi)[3])
+{
+    const uint32_t sx = __builtin_amdgcn_readlane(sdfk::wave_sum_to_last_lane(both ? x : 0u), 63);
+    const uint32_t sy = __builtin_amdgcn_readlane(sdfk::wave_sum_to_last_lane(both ? y : 0u), 63);
+    const uint32_t sz = __builtin_amdgcn_readlane(sdfk::wave_sum_to_last_lane(both ? z : 0u), 63);
+    // lanes 0-3: the u64 sums, 4-6: the minima, 7-9: the maxima -- each accumulator once per wavefront
+    const unsigned long long add = lane == 0u ? (unsigned long long)__popcll(b) : lane == 1u ? sx : lane == 2u ? sy : sz;
+    const uint32_t k = lane < 7u ? lane - 4u : lane - 7u;
+    const uint32_t bound = lane < 7u ? (k == 0u ? lo[0] : k == 1u ? lo[1] : lo[2]) : (k == 0u ? hi[0] : k == 1u ? hi[1] : hi[2]);
+    if (lane < 4u) atomicAdd(&acc->sums[lane], add);
+    else if (lane < 7u) atomicMin(&acc->lo[k], bound);
+    else if (lane < 10u) atomicMax(&acc->hi[k], bound);
 }
 
 }  // namespace hu_cells

@@ -100,40 +100,18 @@ __device__ __forceinline__ void count_evaluations(const Args& a, const CellRow& 
     if (l.lane == 0u) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
 }
 
-// f(i, j, both, b) for every pair i < j of `present` (wave-uniform) some lane has both of in its bitmask `mine`: `both`
-// says whether this lane does, `b` is its ballot
-template <class F> __device__ __forceinline__ void for_pairs(uint64_t present, uint64_t mine, F f)
-{
-    for (uint64_t mi = present; mi != 0ull; mi &= mi - 1ull) {
-        const uint32_t i = uniform((uint32_t)__builtin_ctzll(mi));
-        for (uint64_t mj = mi & (mi - 1ull); mj != 0ull; mj &= mj - 1ull) {
-            const uint32_t j = uniform((uint32_t)__builtin_ctzll(mj));
-            const bool both = ((mine >> i) & (mine >> j) & 1ull) != 0ull;
-            const uint64_t b = __ballot(both);
-            if (b == 0ull) continue;                              // wave-uniform
-            f(i, j, both, b);
-        }
-    }
-}
-
 // the lanes of `b` (this lane: `both`) added to a pair's count, index sums and index box
 template <class Acc>
 __device__ __forceinline__ void add_samples(Acc* acc, bool both, uint64_t b, const LeafLane l, const CellRow row)
 {
-    const uint32_t sx = __builtin_amdgcn_readlane(wave_sum_to_last_lane(both ? l.x : 0u), 63);
-    const uint32_t sy = __builtin_amdgcn_readlane(wave_sum_to_last_lane(both ? l.y : 0u), 63);
-    const uint32_t sz = __builtin_amdgcn_readlane(wave_sum_to_last_lane(both ? l.z : 0u), 63);
     uint32_t lo[3], hi[3];
     mask_box(b, lo, hi);
-    // lanes 0-3: the u64 sums, 4-6: the minima, 7-9: the maxima -- each accumulator once per wavefront
-    const uint32_t lane = l.lane;
-    const unsigned long long add = lane == 0u ? (unsigned long long)__popcll(b) : lane == 1u ? sx : lane == 2u ? sy : sz;
-    const uint32_t k = lane < 7u ? lane - 4u : lane - 7u;
-    const uint32_t origin = k == 0u ? row.x0 : k == 1u ? row.y0 : row.z0;
-    const uint32_t bound = origin + (lane < 7u ? (k == 0u ? lo[0] : k == 1u ? lo[1] : lo[2]) : (k == 0u ? hi[0] : k == 1u ? hi[1] : hi[2]));
-    if (lane < 4u) atomicAdd(&acc->sums[lane], add);
-    else if (lane < 7u) atomicMin(&acc->lo[k], bound);
-    else if (lane < 10u) atomicMax(&acc->hi[k], bound);
+    const uint32_t origin[3] = {row.x0, row.y0, row.z0};
+    for (int k = 0; k < 3; ++k) {
+        lo[k] += origin[k];
+        hi[k] += origin[k];
+    }
+    add_samples(acc, both, b, l.lane, l.x, l.y, l.z, lo, hi);
 }
 
 template <bool DO>

@@ -10,6 +10,7 @@
 //   instance_pairs.hip  the interference and clearance checks between the instances of an assembly, built without
 //                 it as well;
 //   instance_rays.hip   the ray caster over the instances of an assembly (codecad_amd/rendering/assembly_picture.py), likewise;
+//   instance_section.hip  the planar section of an assembly (codecad_amd/section.py), likewise;
 // Each function enqueues one launch and returns hipGetLastError().
 #pragma once
 
@@ -102,8 +103,25 @@ struct RayArgs {
 };
 constexpr uint32_t kRaysNoSkip = 1u;
 
+// the planar section of an assembly (instance_section.hip): what its kernels take beside Args.  There Args describes a 2D
+// lattice on the plane: dims = {samples along u, along v, 1}, corner = the 3D position of sample (0, 0), a row is a TILE
+// {x0 | y0 << 16, unused, mask lo, mask hi} of 8^k x 8^k samples, windows (n x 6, the third index 0) the samples an
+// instance may be inside at, thr the radius of a child tile, and pairs n_instances^2 OverlapAcc whose diagonal [k][k]
+// holds the samples inside instance k.
+struct SectionArgs {
+    Args c;
+    float u[3], v[3];                // the plane's unit vectors: sample (i, j) sits at (corner + u * (step * i)) + v * (step * j)
+    int32_t* part_ids;               // leaf: [dims v][dims u] maps; the lowest instance a sample is inside of (prefilled with -1)
+    uint8_t* inside_count;           //   how many it is inside of (prefilled with 0)
+    float* distance;                 //   WITH_DISTANCE: the least w of all instances
+    int32_t* nearest;                //   WITH_DISTANCE: the lowest instance that attains it
+};
+
 hipError_t allow_big_lds(size_t bytes);
 hipError_t allow_big_lds_rays(size_t bytes);
+hipError_t allow_big_lds_section(size_t bytes);
+hipError_t section(bool leaf, bool distance_only, bool with_distance, const SectionArgs& a, uint32_t blocks, uint32_t block, size_t lds,
+                   hipStream_t stream);
 hipError_t ray_caster_instances(const RayArgs& t, const sdfk::RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libhip_util.so")
-SOURCES = ["hip_util.hip", "render.hip", "sort.hip", "exchange.hip", "mesh.hip", "instance_pairs.hip", "instance_rays.hip"]
+SOURCES = ["hip_util.hip", "render.hip", "sort.hip", "exchange.hip", "mesh.hip", "instance_pairs.hip", "instance_rays.hip",
+           "instance_section.hip"]
 
 
 def headers():
@@ -33,8 +34,8 @@ HIPCC_FLAGS = [
 #   branch-free ops (ops with divergent branches or loops are __noinline__ functions), plus straight-line index
 #   arithmetic, stores and the ballot compaction -- no divergent loop with more than one exit;
 # every other kernel -- ray caster, bitmap, 2D contouring, mass integrals, self-test (render.hip), the exchange step,
-# the sort, marching cubes, the interference and clearance checks (instance_pairs.hip) and the ray caster over instances
-# (instance_rays.hip) -- is built without it.
+# the sort, marching cubes, the interference and clearance checks (instance_pairs.hip), the ray caster over instances
+# (instance_rays.hip) and the section of an assembly (instance_section.hip) -- is built without it.
 # tests/test_hip_util_host.py checks both halves of that from the ISA: which kernels the flagged object holds, and that
 # its loops have the shape described here.
 FLAGGED_SOURCES = ("hip_util.hip",)

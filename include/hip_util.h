@@ -257,6 +257,31 @@ int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distanc
                                   uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
                                   void* pairs_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- the planar section of an assembly (codecad_amd/section.py) --------------------------------
+ * A 2D lattice of dims[0] x dims[1] samples on a plane, sample (i, j) at (corner + u * (step * i)) + v * (step * j) per
+ * coordinate in float32 (u, v: the plane's unit vectors), over the same instance table.  A list is the cell list above
+ * with rows {x0 | y0 << 16, unused, mask lo, mask hi}: square tiles of samples.  windows_dev: n x 6 uint32 {lo i, lo j,
+ * 0, hi i, hi j, 0}, the samples an instance may be inside at, inclusive.  At most 65536 samples per axis, 2^28 in all.
+ * hu_section_tiles: a tile of side 8 * child_side per parent row; each of its 8 x 8 children keeps a candidate k whose
+ *   distance at the child's centre is below `radius` (and, without with_distance, whose window reaches the child) or,
+ *   with_distance, is at most the least candidate's plus 2 * radius, and is appended to children_dev when any remain.
+ * hu_section_leaf: a tile of 8 x 8 samples per parent row.  Writes, at [j * dims[0] + i], part_ids_dev (int32: the lowest
+ *   instance with w < 0, -1 for none), inside_count_dev (uint8: how many) and, with_distance, distance_dev (float: the
+ *   least w) and nearest_dev (int32: the lowest instance that attains it; both may be NULL otherwise); samples of tiles
+ *   that are in no row are left as they are.  acc_dev: n * n accumulators of hu_interference_leaf_indirect's layout (third
+ *   index 0), [k * n + k] over the samples inside k, [i * n + j] (i < j) over those inside both.
+ * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
+int hu_section_tiles(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                     const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
+                     const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], int with_distance,
+                     float step, float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                     uint64_t* evaluations_dev, void* stream);
+int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
+                    const float corner[3], const float u[3], const float v[3], int with_distance, float step,
+                    int32_t* part_ids_dev, uint8_t* inside_count_dev, float* distance_dev, int32_t* nearest_dev,
+                    void* acc_dev, uint64_t* evaluations_dev, void* stream);
+
 /* ---- renderers on the same evaluate() -------------------- */
 /* rendering/ray_caster.cl:146-159, launched by rendering/ray_caster.py:93-110 with global size
  * (width, height).  origin/forward/up/right: float4 as the reference passes them (forward already

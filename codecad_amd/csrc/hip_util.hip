@@ -1111,6 +1111,9 @@ int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void*
         n4 = std::max(n4, (uint32_t)(all_do ? tapes[i]->n_point_slots : tapes[i]->n_slots));
         n_res = std::max(n_res, all_do ? (uint32_t)tapes[i]->n_result_slots : 0u);
     }
+    // A table asked for with full_programs reports one slot at least: programs that store nothing (plain spheres) keep no
+    // value, and hu_ray_caster_instances takes a lane_bytes of 0 for "not a table of full programs".
+    if (full_programs) n4 = std::max(n4, 1u);
     auto* recs = static_cast<hu_cells::InstanceRec*>(table_host);
     for (uint32_t i = 0; i < n; ++i)
         recs[i] = hu_cells::InstanceRec{all_do ? tapes[i]->recs_do_dev : tapes[i]->recs_dev, tapes[i]->extra_dev, n4, 0u};

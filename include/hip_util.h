@@ -215,7 +215,8 @@ int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, si
                           uint32_t* lane_bytes);
 /* The same table for a caller that says which programs it wants: full_programs != 0 writes every instance's FULL
  * program (*distance_only = 0) whether or not all have a distance-only one -- the ray caster over instances needs the
- * directions --; full_programs = 0 is hu_interference_table. */
+ * directions --, and reports a register file of one float4 slot at least (*lane_bytes >= 16) even when no program
+ * stores a value; full_programs = 0 is hu_interference_table. */
 int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void* table_host, size_t bytes,
                       int* distance_only, uint32_t* lane_bytes);
 int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,

@@ -3,6 +3,7 @@
 The functions mirror the reference kernels' argument lists (reference grid_eval.cl:2-4,
 23-25; subdivision.cl:12-16; mass_properties.cl:7-12) with numpy arrays for buffers.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -16,7 +17,7 @@ _LITERAL64_PATH = os.path.join(_HERE, "_build", "libliteral64.so")
 _lib = None
 _literal = {}
 
-__all__ = ["build", "lib", "evaluate_points", "grid_eval", "grid_eval_pymcubes", "ray_caster", "bitmap", "process_polygon", "marching_cubes", "stl_records", "STL_RECORD",
+__all__ = ["build", "lib", "evaluate_points", "grid_eval", "grid_eval_pymcubes", "ray_caster", "ray_caster_instances", "InstancePicture", "bitmap", "process_polygon", "marching_cubes", "stl_records", "STL_RECORD",
            "subdivision_step", "mass_properties", "det_math", "evaluate_points_literal", "grid_distance_literal",
            "literal_scene", "mass_properties_literal"]
 
@@ -240,6 +241,41 @@ def ray_caster(tape, origin, forward, up, right, pixel_tolerance, box_radius, mi
                                    ctypes.c_float(max_distance), ctypes.c_float(floor_z), ctypes.c_uint32(int(options)),
                                    ctypes.c_uint32(w), ctypes.c_uint32(h), out.ctypes.data_as(_u8p),
                                    ctypes.c_int(threads)), "ray_caster")
+    return out
+
+
+InstancePicture = collections.namedtuple("InstancePicture", "pixels part_ids depth tied")
+
+
+def ray_caster_instances(tapes, hues, origin, forward, up, right, pixel_tolerance, box_radius, min_distance, max_distance,
+                         floor_z, options, size, threads=1):
+    """The picture of an assembly (codecad_amd/rendering/assembly_picture.py) from its definition: the sequence of
+    ray_caster() over the field  F.w = the union chain's minimum of the instances' distances in index order, F.xyz and
+    the part id from the LOWEST index whose distance equals it  (sdf_oracle.c instance_field), every instance evaluated
+    at every sample.  `tapes`: one program per instance; `hues`: (n, 3) float32, the flat colour of each, or None for the
+    single-shape colour.  -> InstancePicture in the device arrays' layout, index y + h*x: pixels uint8 (w, h, 3), part_ids
+    int32 (w, h) (-1: no hit), depth float32 (w, h) (+inf: no hit), tied uint8 (w, h): 1 where the last primary evaluation
+    had two instances or more with the minimum's exact bits, 2 where their directions differ as well."""
+    arrays = [np.ascontiguousarray(t, dtype=np.float32) for t in tapes]
+    n = len(arrays)
+    pointers = (_f32p * n)(*(a.ctypes.data_as(_f32p) for a in arrays))
+    lens = (ctypes.c_int * n)(*(a.size for a in arrays))
+    w, h = int(size[0]), int(size[1])
+    hue_p = None
+    if hues is not None:
+        hues = np.ascontiguousarray(hues, dtype=np.float32)
+        assert hues.shape == (n, 3)
+        hue_p = hues.ctypes.data_as(_f32p)
+    out = InstancePicture(np.zeros((w, h, 3), dtype=np.uint8), np.zeros((w, h), dtype=np.int32),
+                          np.zeros((w, h), dtype=np.float32), np.zeros((w, h), dtype=np.uint8))
+    vec = [np.ascontiguousarray(np.asarray(v, dtype=np.float64)[:3], dtype=np.float32) for v in (origin, forward, up, right)]
+    fn = lib().oracle_ray_caster_instances
+    fn.restype = ctypes.c_int
+    _check(fn(pointers, lens, ctypes.c_int(n), hue_p, *[v.ctypes.data_as(_f32p) for v in vec], ctypes.c_float(pixel_tolerance),
+              ctypes.c_float(box_radius), ctypes.c_float(min_distance), ctypes.c_float(max_distance), ctypes.c_float(floor_z),
+              ctypes.c_uint32(int(options)), ctypes.c_uint32(w), ctypes.c_uint32(h), out.pixels.ctypes.data_as(_u8p),
+              out.part_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), out.depth.ctypes.data_as(_f32p),
+              out.tied.ctypes.data_as(_u8p), ctypes.c_int(threads)), "ray_caster_instances")
     return out
 
 

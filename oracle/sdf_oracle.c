@@ -720,7 +720,9 @@ static inline float smoothstepf(float e0, float e1, float x)
 #define RC_FALSE_COLOR 1u
 #define RC_ZEBRA 2u
 
-typedef struct { const float *tape, *end; } scene_t;
+/* One shape (tape .. end), or -- n > 0 -- the instances of an assembly, each with its own tape (instance_field below). */
+typedef struct { const float *tape, *end; const float *const *tapes; const int *lens; int n; } scene_t;
+#define RC_MAX_INSTANCES 64
 
 /* The renderers below normally run over evaluate() above.  A test may put another evaluator in its place -- the
  * frozen literal-formula one of sdf_literal.c -- to render the reference's baseline images over it as well
@@ -730,9 +732,52 @@ static scene_hook_t g_scene_hook;
 static void *g_scene_handle;
 void oracle_set_scene_evaluator(scene_hook_t fn, void *handle) { g_scene_hook = fn; g_scene_handle = handle; }
 
-static inline f4 scene_eval(const scene_t *s, f3 p)
+/* The field of an assembly's picture, from its definition (rendering/assembly_picture.py), with
+ * e_k = evaluate() on instance k's own tape:
+ *   F(p).w   = the union chain's minimum of e_k(p).w over k = 0..n-1 in index order: the first value as it is, then hw_min,
+ *              the minimum of the union instruction (so a NaN operand yields the other one, and -0 orders below +0);
+ *   F(p).xyz = e_m(p).xyz, id(p) = m: the LOWEST index with e_m(p).w == F(p).w.  When no value compares equal, F(p).w is a
+ *              NaN and so is every e_k(p).w (hw_min gives a number whenever an operand is one): the lowest index among
+ *              them is 0.
+ * Every instance is evaluated at every point: nothing is skipped here.  *tied: 1 when two instances or more have the
+ * minimum's exact bits, 2 when the directions of those differ as well -- what a test needs to show that it holds a tie. */
+static inline f4 instance_field(const scene_t *s, f3 p, int32_t *id, uint8_t *tied)
+{
+    f4 e[RC_MAX_INSTANCES];
+    e[0] = mk4(0, 0, 0, 0);
+    for (int k = 0; k < s->n; ++k) {
+        e[k] = mk4(0, 0, 0, 0);
+        evaluate(s->tapes[k], s->tapes[k] + s->lens[k], mk4(p.x, p.y, p.z, 0), &e[k]);
+    }
+    float w = e[0].w;
+    for (int k = 1; k < s->n; ++k) w = hw_min(w, e[k].w);
+    int m = 0;
+    for (int k = 0; k < s->n; ++k)
+        if (e[k].w == w) { m = k; break; }
+    if (tied) {
+        uint32_t wb, kb;
+        int first = -1, same = 0, differ = 0;
+        memcpy(&wb, &w, 4);
+        for (int k = 0; k < s->n; ++k) {
+            memcpy(&kb, &e[k].w, 4);
+            if (kb != wb) continue;
+            ++same;
+            if (first < 0) first = k;
+            else if (memcmp(&e[k].x, &e[first].x, 4) || memcmp(&e[k].y, &e[first].y, 4) || memcmp(&e[k].z, &e[first].z, 4)) differ = 1;
+        }
+        *tied = (uint8_t)(same < 2 ? 0 : differ ? 2 : 1);
+    }
+    if (id) *id = m;
+    return mk4(e[m].x, e[m].y, e[m].z, w);
+}
+
+/* the field at p; for the instances of an assembly also the part the value came from (one shape: part 0, no tie) */
+static inline f4 scene_eval_id(const scene_t *s, f3 p, int32_t *id, uint8_t *tied)
 {
     f4 r = mk4(0, 0, 0, 0);
+    if (s->n > 0) return instance_field(s, p, id, tied);
+    if (id) *id = 0;
+    if (tied) *tied = 0;
     if (g_scene_hook) {
         const float q[3] = { p.x, p.y, p.z };
         float o[4] = { 0, 0, 0, 0 };
@@ -742,6 +787,7 @@ static inline f4 scene_eval(const scene_t *s, f3 p)
     evaluate(s->tape, s->end, mk4(p.x, p.y, p.z, 0), &r);
     return r;
 }
+static inline f4 scene_eval(const scene_t *s, f3 p) { return scene_eval_id(s, p, NULL, NULL); }
 
 /* ray_caster.cl:13-26 */
 static inline float over_relaxation_step(f3 direction, f4 e)
@@ -798,17 +844,18 @@ static inline float ambient_occlusion(const scene_t *sc, f3 point, f3 normal, fl
     return clampf(1.0f - (occlusion * 0.5f) / (1.0f - scale), 0.0f, 1.0f);
 }
 
-/* ray_caster.cl:118-131 */
-static inline f3 map_color(float ambient, float diffuse, float specular)
+/* ray_caster.cl:118-131 with the hue c a parameter, as kernels.hpp map_color takes it: the reference's flat colour is
+ * c = RC_DEFAULT_HUE, for which chroma * c + m is its X + m, chroma + m, 0 + m bit for bit (chroma * 1 and chroma * 0 are
+ * exact, chroma >= +0, nothing is contracted). */
+#define RC_DEFAULT_HUE mk3(0.7f, 1.0f, 0.0f)
+static inline f3 map_color(float ambient, float diffuse, float specular, f3 c)
 {
     float saturation = 0.75f * smoothstepf(0.0f, 0.25f, diffuse);
     float value = 0.1f + 0.8f * mixf(diffuse, ambient, 0.3f);
     float chroma = value * saturation;
-    float X = chroma * 0.7f;
     float m = value - chroma;
-    f3 color = mk3(255.0f * (X + m), 255.0f * (chroma + m), 255.0f * (0.0f + m));
     float sp = specular * 128.0f;
-    return mk3(color.x + sp, color.y + sp, color.z + sp);
+    return mk3(255.0f * (chroma * c.x + m) + sp, 255.0f * (chroma * c.y + m) + sp, 255.0f * (chroma * c.z + m) + sp);
 }
 
 /* ray_caster.cl:133-144 */
@@ -821,11 +868,14 @@ static inline f3 map_color_zebra(f3 point, float ambient, float diffuse, float s
     return mk3(color, color, color);
 }
 
-/* ray_caster.cl:146-256, one pixel */
+/* ray_caster.cl:146-256, one pixel.  Beside its colour a pixel can record (each pointer may be NULL) what the picture of
+ * an assembly keeps: `part_id`, the part of the last primary evaluation on a hit and -1 otherwise; `depth`, the distance
+ * at the end of the primary march on a hit and +inf otherwise; `tied`, instance_field's mark of that last evaluation.
+ * `hues`: 3 floats per part, the flat colour of a lit pixel of that part; NULL: RC_DEFAULT_HUE. */
 static void ray_caster_pixel(const scene_t *sc, uint32_t x, uint32_t y, uint32_t w, uint32_t h, f3 origin,
                              f3 forward, f3 up, f3 right, float pixel_tolerance, float box_radius,
                              float min_distance, float max_distance, float floor_z, uint32_t options,
-                             uint8_t *out)
+                             const float *hues, uint8_t *out, int32_t *part_id, float *depth, uint8_t *tied)
 {
     float filmx = (float)x - (float)(w - 1) / 2.0f;
     float filmy = (float)y - (float)(h - 1) / 2.0f;
@@ -836,9 +886,11 @@ static void ray_caster_pixel(const scene_t *sc, uint32_t x, uint32_t y, uint32_t
     float distance = min_distance, fallback = min_distance;
     f4 e = mk4(0, 0, 0, 0);
     int hit = 0;
+    int32_t id = 0;
+    uint8_t tie = 0;
     uint32_t step;
     for (step = 0; step < RC_PRIMARY_MAX_STEPS; ++step) {
-        e = scene_eval(sc, add3(origin, mul3(direction, distance)));
+        e = scene_eval_id(sc, add3(origin, mul3(direction, distance)), &id, &tie);
         if (distance - fallback > e.w) { distance = fallback; continue; }
         hit = e.w < pixel_tolerance * distance;
         if (hit) {
@@ -850,6 +902,10 @@ static void ray_caster_pixel(const scene_t *sc, uint32_t x, uint32_t y, uint32_t
         distance = distance + over_relaxation_step(direction, e);
         if (distance > max_distance) { distance = INFINITY; break; }
     }
+
+    if (part_id) *part_id = hit ? id : -1;
+    if (depth) *depth = hit ? distance : INFINITY;
+    if (tied) *tied = tie;
 
     f3 color;
     float local_eps = fmaxf(1e-4f, 2.0f * fabsf(e.w));
@@ -872,7 +928,8 @@ static void ray_caster_pixel(const scene_t *sc, uint32_t x, uint32_t y, uint32_t
         light_no_trace(normal, mul3(light2_dir, -1.0f), to_camera, &d2, &s2);
         d = 0.8f * d + 0.2f * d2;
         s = 0.8f * s + 0.2f * s2;
-        color = (options & RC_ZEBRA) ? map_color_zebra(point, ambient, d, s) : map_color(ambient, d, s);
+        color = (options & RC_ZEBRA) ? map_color_zebra(point, ambient, d, s)
+                                     : map_color(ambient, d, s, hues ? mk3(hues[3 * id], hues[3 * id + 1], hues[3 * id + 2]) : RC_DEFAULT_HUE);
     } else {
         color = mk3(230, 230, 241);
     }
@@ -898,7 +955,7 @@ int oracle_ray_caster(const float *tape, int n_tape, const float *origin, const 
                       float max_distance, float floor_z, uint32_t options, uint32_t w, uint32_t h, uint8_t *out,
                       int threads)
 {
-    scene_t sc = { tape, tape + n_tape };
+    scene_t sc = { tape, tape + n_tape, NULL, NULL, 0 };
     f4 probe;
     if (evaluate(tape, tape + n_tape, mk4(0, 0, 0, 0), &probe)) return -1;
 #pragma omp parallel for num_threads(threads > 0 ? threads : 1) schedule(dynamic, 4)
@@ -906,7 +963,33 @@ int oracle_ray_caster(const float *tape, int n_tape, const float *origin, const 
         for (uint32_t y = 0; y < h; ++y)
             ray_caster_pixel(&sc, x, y, w, h, mk3(origin[0], origin[1], origin[2]), mk3(forward[0], forward[1], forward[2]),
                              mk3(up[0], up[1], up[2]), mk3(right[0], right[1], right[2]), pixel_tolerance, box_radius,
-                             min_distance, max_distance, floor_z, options, out + ((size_t)y + (size_t)h * x) * 3);
+                             min_distance, max_distance, floor_z, options, NULL, out + ((size_t)y + (size_t)h * x) * 3,
+                             NULL, NULL, NULL);
+    return 0;
+}
+
+/* The picture of an assembly (rendering/assembly_picture.py, csrc/instance_rays.hip): the sequence above over
+ * instance_field.  tapes[k] (lens[k] floats) is instance k's program, hues 3 floats per instance or NULL; pixels as
+ * oracle_ray_caster's, part_ids / depth / tied at index y + h*x. */
+int oracle_ray_caster_instances(const float *const *tapes, const int *lens, int n, const float *hues, const float *origin,
+                                const float *forward, const float *up, const float *right, float pixel_tolerance,
+                                float box_radius, float min_distance, float max_distance, float floor_z, uint32_t options,
+                                uint32_t w, uint32_t h, uint8_t *out, int32_t *part_ids, float *depth, uint8_t *tied,
+                                int threads)
+{
+    if (n < 1 || n > RC_MAX_INSTANCES) return -1;
+    scene_t sc = { NULL, NULL, tapes, lens, n };
+    f4 probe;
+    for (int k = 0; k < n; ++k)
+        if (evaluate(tapes[k], tapes[k] + lens[k], mk4(0, 0, 0, 0), &probe)) return -1;
+#pragma omp parallel for num_threads(threads > 0 ? threads : 1) schedule(dynamic, 1)
+    for (uint32_t x = 0; x < w; ++x)
+        for (uint32_t y = 0; y < h; ++y) {
+            const size_t i = (size_t)y + (size_t)h * x;
+            ray_caster_pixel(&sc, x, y, w, h, mk3(origin[0], origin[1], origin[2]), mk3(forward[0], forward[1], forward[2]),
+                             mk3(up[0], up[1], up[2]), mk3(right[0], right[1], right[2]), pixel_tolerance, box_radius,
+                             min_distance, max_distance, floor_z, options, hues, out + i * 3, part_ids + i, depth + i, tied + i);
+        }
     return 0;
 }
 
@@ -914,7 +997,7 @@ int oracle_ray_caster(const float *tape, int n_tape, const float *origin, const 
 int oracle_bitmap(const float *tape, int n_tape, const float *origin, float step_size, uint32_t w, uint32_t h,
                   uint8_t *out)
 {
-    scene_t sc = { tape, tape + n_tape };
+    scene_t sc = { tape, tape + n_tape, NULL, NULL, 0 };
     f4 probe;
     if (evaluate(tape, tape + n_tape, mk4(0, 0, 0, 0), &probe)) return -1;
     for (uint32_t x = 0; x < w; ++x)

@@ -152,34 +152,37 @@ def device_table(instances, queue, full_programs=False):
     return table, distance_only.value, lane_bytes.value
 
 
-def levels(side, n_top, initial_capacity, factor=4):
+def levels(side, n_top, initial_capacity, factor=4, row_bytes=_ROW):
     """(sides of the cells of every level above the finest one, the first capacity of every level's child list); a cell
-    has `factor` children per axis, 64 in all: 4^3 (the checks) or 8^2 (a section's tiles)."""
+    has `factor` children per axis, 64 in all: 4^3 (the checks) or 8^2 (a section's tiles); a list's rows have `row_bytes`
+    (32 for the mass properties' rows with a second mask)."""
     sides = []
     s = side
     while s > factor:
         sides.append(s)
         s //= factor
-    capacities = subdivision.first_capacities([64] * len(sides), n_top=n_top, row_bytes=_ROW)
+    capacities = subdivision.first_capacities([64] * len(sides), n_top=n_top, row_bytes=row_bytes)
     if initial_capacity is not None:
         capacities = [subdivision.checked_capacity(min(c, max(1, int(initial_capacity)))) for c in capacities]
     return sides, capacities
 
 
 def _run(table, n, distance_only, lane_bytes, wins, top, sides, corner, step, dims, capacities, queue, pair_dtype, pair_init, thr,
-         cells, finest, factor, frame):
+         cells, finest, factor, frame, row_bytes=_ROW, cells_extra=None, accumulators=None):
     """Every level enqueued back to back, ONE synchronisation -> (list counts, evaluations, pair accumulators)."""
     lib = hip_manager.lib
     n_levels = len(sides)                   # levels of cells above the finest one
     # one device buffer of everything the host reads: [list headers: 16 B per level | evaluations: 16 B | pairs]
     head = 16 * n_levels + 16
-    init = numpy.zeros(head + n * n * pair_dtype.itemsize, dtype=numpy.uint8)
+    acc_shape = (n, n) if accumulators is None else (accumulators,)
+    init = numpy.zeros(head + int(numpy.prod(acc_shape)) * pair_dtype.itemsize, dtype=numpy.uint8)
     pairs0 = init[head:].view(pair_dtype)
     for field, value in pair_init.items():
         pairs0[field] = value
     results = hip_util.Buffer(numpy.uint8, (init.size,), queue=queue)
     results.enqueue_write(init)
-    first = numpy.zeros((len(top) + 1, 4), dtype=numpy.uint32)
+    words = row_bytes // 4                  # a list: [header row | rows...], the header's word 0 its length
+    first = numpy.zeros((len(top) + 1, words), dtype=numpy.uint32)
     first[0, 0] = len(top)
     first[1:] = top
     parents = hip_util.Buffer(numpy.uint32, first.shape, queue=queue)
@@ -191,32 +194,35 @@ def _run(table, n, distance_only, lane_bytes, wins, top, sides, corner, step, di
     instances = (table.device_ptr, n, distance_only, lane_bytes) + (() if wins is None else (wins.device_ptr,))
     for level, (side, capacity) in enumerate(zip(sides, capacities)):
         child = side // factor
-        children = hip_util.Buffer(numpy.uint32, (capacity + 1, 4), queue=queue)
-        check(lib.hu_memset(children.device_ptr, 0, 16, queue.handle), "hu_memset")
-        check(getattr(lib, cells)(*instances, parents.device_ptr + 16, parents.device_ptr, max_parents, child, d, c, *frame, step,
-                                  thr(child), children.device_ptr, children.device_ptr + 16, capacity, evaluations,
+        children = hip_util.Buffer(numpy.uint32, (capacity + 1, words), queue=queue)
+        check(lib.hu_memset(children.device_ptr, 0, row_bytes, queue.handle), "hu_memset")
+        extra = () if cells_extra is None else tuple(cells_extra) + (results.device_ptr + head,)
+        check(getattr(lib, cells)(*instances, parents.device_ptr + row_bytes, parents.device_ptr, max_parents, child, d, c, *frame, step,
+                                  thr(child), children.device_ptr, children.device_ptr + row_bytes, capacity, *extra, evaluations,
                                   queue.handle), cells)
         check(lib.hu_memcpy_d2d(results.device_ptr + 16 * level, children.device_ptr, 16, queue.handle), "hu_memcpy_d2d")
         buffers.append(children)
         parents, max_parents = children, capacity
     for name, extra in finest:              # in this order, on the one stream
-        check(getattr(lib, name)(*instances, parents.device_ptr + 16, parents.device_ptr, max_parents, d, c, *frame, step, *extra,
+        check(getattr(lib, name)(*instances, parents.device_ptr + row_bytes, parents.device_ptr, max_parents, d, c, *frame, step, *extra,
                                  results.device_ptr + head, evaluations, queue.handle), name)
     got = results.read()                    # the one synchronisation
     for b in buffers + [results]:
         b.release()
     counts = [int(v) for v in got[:16 * n_levels].view(numpy.uint32).reshape(n_levels, 4)[:, 0]]
-    return counts, int(got[16 * n_levels:head].view(numpy.uint64)[0]), got[head:].view(pair_dtype).reshape(n, n).copy()
+    return counts, int(got[16 * n_levels:head].view(numpy.uint64)[0]), got[head:].view(pair_dtype).reshape(acc_shape).copy()
 
 
 def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dtype, pair_init, thr, cells, finest, wins=None,
-             factor=4, frame=()):
+             factor=4, frame=(), row_bytes=_ROW, cells_extra=None, accumulators=None):
     """The traversal from the top-level rows `top` (cells of `side` samples), run again with larger lists while one
     overflowed -> (evaluations of the last run, pair accumulators [n, n], runs).  What the check decides: `pair_dtype`
     and `pair_init` ({field: initial value}) of the accumulators; `thr`, child side -> float32 threshold of a level;
     `cells`, the entry point of the coarser levels; `finest`, [(entry point of the finest level, its arguments between
     step and the accumulators)], launched in that order; `wins`, clearance's windows (int64[n, 2, 3]), uploaded for
-    its entry points."""
+    its entry points; `row_bytes`, the size of a row of `top` and of every list (16, or 32 for rows with a second mask);
+    `cells_extra`, arguments of `cells` between its capacity and its evaluations, after which it then also gets the
+    accumulators (the mass properties' levels add to them); `accumulators`, their number when it is not n * n."""
     queue = hip_manager.queue
     n = len(instances)
     table, distance_only, lane_bytes = device_table(instances, queue)
@@ -225,12 +231,13 @@ def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dt
         host_wins = numpy.ascontiguousarray(wins.reshape(n, 6).astype(numpy.uint32))
         wins_dev = hip_util.Buffer(numpy.uint32, host_wins.shape, queue=queue)
         wins_dev.enqueue_write(host_wins)
-    sides, capacities = levels(side, len(top), initial_capacity, factor)
+    sides, capacities = levels(side, len(top), initial_capacity, factor, row_bytes)
     runs = 0
     while True:
         runs += 1
         counts, evaluations, acc = _run(table, n, distance_only, lane_bytes, wins_dev, top, sides, corner, step, dims, capacities,
-                                        queue, pair_dtype, pair_init, thr, cells, finest, factor, frame)
+                                        queue, pair_dtype, pair_init, thr, cells, finest, factor, frame, row_bytes, cells_extra,
+                                        accumulators)
         if all(k <= c for k, c in zip(counts, capacities)):
             break
         capacities = [subdivision.checked_capacity(max(c, int(k * 1.125) + 16)) for k, c in zip(counts, capacities)]

@@ -196,6 +196,7 @@ int ensure_attrs()
     HU_HIP(hu_cells::allow_big_lds(kMaxLds));          // (instance_pairs.hip)
     HU_HIP(hu_cells::allow_big_lds_rays(kMaxLds));     // (instance_rays.hip)
     HU_HIP(hu_cells::allow_big_lds_section(kMaxLds));  // (instance_section.hip)
+    HU_HIP(hu_cells::allow_big_lds_mass(kMaxLds));     // (instance_mass.hip)
     done_for_device = dev;
     return HU_OK;
 }
@@ -1342,6 +1343,66 @@ int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only_kernel,
     t.nearest = nearest_dev;
     return cells_launch(lane_bytes, 0u, t.c, [&](uint32_t blocks, uint32_t block, size_t lds) {
         return hu_cells::section(true, distance_only_kernel != 0, with_distance != 0, t, blocks, block, lds, (hipStream_t)stream);
+    });
+}
+
+namespace {
+
+// What both entry points of the assembly's mass properties check and fill: cells_args() of interference's lattice, and
+// what the sums need: every index within 16 bits, and a lattice whose second-moment sums fit 64 bits.
+int mass_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+              const uint32_t dims[3], const float corner[3], float step, void* acc_dev, uint64_t* evaluations_dev, hu_cells::Args& a)
+{
+    int rc;
+    if ((rc = cells_args(false, table_dev, n, nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+        return rc;
+    if (!acc_dev) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (dims[2] > 65536u) return fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (!std::isfinite(step) || step < 0.0f) return fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    const uint64_t longest = std::max(dims[0], std::max(dims[1], dims[2])) - 1u;
+    const unsigned __int128 bound = (unsigned __int128)dims[0] * dims[1] * dims[2] * longest * longest;
+    if (bound >> 64) return fail(HU_ERR_BAD_ARG, "the lattice's second-moment index sums would not fit 64 bits");
+    a.pairs = acc_dev;
+    return HU_OK;
+}
+
+}  // namespace
+
+int hu_assembly_mass_cells(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
+                           const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
+                           const float corner[3], float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                           int retire, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+{
+    hu_cells::Args a;
+    int rc;
+    if ((rc = mass_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, acc_dev, evaluations_dev, a))) return rc;
+    if (!counter_dev || (!children_dev && capacity)) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (child_side < 4u || child_side > 16384u || (child_side & (child_side - 1u)))
+        return fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
+    if (!std::isfinite(thr) || thr < 0.0f) return fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    if (max_parents > 0x7fffffffu || capacity > 0x7fffffffu) return fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
+    a.child_side = child_side;
+    a.thr = thr;
+    a.counter = counter_dev;
+    a.children = static_cast<uint4*>(children_dev);
+    a.capacity = capacity;
+    a.flags = retire ? hu_cells::kMassRetire : 0u;
+    return cells_launch(lane_bytes, 0u, a, [&](uint32_t blocks, uint32_t block, size_t lds) {
+        return hu_cells::mass(hu_cells::kMassCells, distance_only_kernel != 0, a, blocks, block, lds, (hipStream_t)stream);
+    });
+}
+
+int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
+                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+                          void* acc_dev, uint64_t* evaluations_dev, void* stream)
+{
+    hu_cells::Args a;
+    int rc;
+    if ((rc = mass_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, acc_dev, evaluations_dev, a))) return rc;
+    if (max_parents > 0x7fffffffu) return fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
+    a.child_side = 1u;
+    return cells_launch(lane_bytes, 0u, a, [&](uint32_t blocks, uint32_t block, size_t lds) {
+        return hu_cells::mass(hu_cells::kMassLeaf, distance_only_kernel != 0, a, blocks, block, lds, (hipStream_t)stream);
     });
 }
 

@@ -11,6 +11,7 @@
 //                 it as well;
 //   instance_rays.hip   the ray caster over the instances of an assembly (codecad_amd/rendering/assembly_picture.py), likewise;
 //   instance_section.hip  the planar section of an assembly (codecad_amd/section.py), likewise;
+//   instance_mass.hip   the mass properties of an assembly (codecad_amd/assembly_mass.py), likewise;
 // Each function enqueues one launch and returns hipGetLastError().
 #pragma once
 
@@ -66,6 +67,17 @@ struct NearAcc {
 };
 static_assert(sizeof(NearAcc) == 72, "clearance.py reads 72-byte accumulators");
 
+// mass properties of an assembly (instance_mass.hip): per instance k the ten index sums n, x, y, z, xx, yy, zz, xy, xz, yz
+// over V_k, the samples inside k, and over O_k, those inside k and inside no instance of lower index, and the index box of
+// V_k (lo starts at 0xffffffff, hi at 0)
+struct MassAcc {
+    unsigned long long v[10];
+    unsigned long long o[10];
+    uint32_t lo[3], hi[3];
+    uint32_t pad[2];
+};
+static_assert(sizeof(MassAcc) == 192, "assembly_mass.py reads 192-byte accumulators");
+
 // the arguments of every kernel over instance cells; interference leaves `windows` and `t` null and zero and never reads them
 struct Args {
     const InstanceRec* table;
@@ -86,9 +98,12 @@ struct Args {
     unsigned long long* evaluations; // per-instance sample evaluations, added up per wavefront
     uint32_t scratch_offset;         // bytes of LDS taken by the register file (cells: the compaction's scratch follows;
                                      // clearance's finest level: the w of every instance, 256 bytes per instance and wavefront)
+    uint32_t flags;                  // instance_mass.hip: kMassRetire
 };
+constexpr uint32_t kMassRetire = 1u;     // a child whose candidates are all provably full adds closed-form sums and leaves the lists
 
 enum Kernel { kInterferenceCells, kInterferenceLeaf, kClearanceCells, kClearanceLeaf, kClearanceWitness, kKernels };
+enum MassKernel { kMassCells, kMassLeaf, kMassKernels };   // (instance_mass.hip; rows of 32 bytes, `pairs` n_instances MassAcc)
 
 // the ray caster over the instance table (instance_rays.hip): what it takes beside sdfk::RayCasterArgs
 struct RayArgs {
@@ -120,6 +135,8 @@ struct SectionArgs {
 hipError_t allow_big_lds(size_t bytes);
 hipError_t allow_big_lds_rays(size_t bytes);
 hipError_t allow_big_lds_section(size_t bytes);
+hipError_t allow_big_lds_mass(size_t bytes);
+hipError_t mass(MassKernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
 hipError_t section(bool leaf, bool distance_only, bool with_distance, const SectionArgs& a, uint32_t blocks, uint32_t block, size_t lds,
                    hipStream_t stream);
 hipError_t ray_caster_instances(const RayArgs& t, const sdfk::RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);

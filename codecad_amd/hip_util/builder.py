@@ -12,7 +12,7 @@ CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libhip_util.so")
 SOURCES = ["hip_util.hip", "render.hip", "sort.hip", "exchange.hip", "mesh.hip", "instance_pairs.hip", "instance_rays.hip",
-           "instance_section.hip"]
+           "instance_section.hip", "instance_mass.hip"]
 
 
 def headers():
@@ -35,7 +35,8 @@ HIPCC_FLAGS = [
 #   arithmetic, stores and the ballot compaction -- no divergent loop with more than one exit;
 # every other kernel -- ray caster, bitmap, 2D contouring, mass integrals, self-test (render.hip), the exchange step,
 # the sort, marching cubes, the interference and clearance checks (instance_pairs.hip), the ray caster over instances
-# (instance_rays.hip) and the section of an assembly (instance_section.hip) -- is built without it.
+# (instance_rays.hip), the section of an assembly (instance_section.hip) and its mass properties (instance_mass.hip) -- is
+# built without it.
 # tests/test_hip_util_host.py checks both halves of that from the ISA: which kernels the flagged object holds, and that
 # its loops have the shape described here.
 FLAGGED_SOURCES = ("hip_util.hip",)

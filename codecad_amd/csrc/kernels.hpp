@@ -1224,9 +1224,11 @@ __device__ __forceinline__ float2 pp_place_vertex(const float (&px)[3], const fl
             gx += val[j].x * tmp;
             gy += val[j].y * tmp;
         }
+        // the reference compares with the double literals 1e-3 and 1e-8: 1e-3f > 1e-3 decides alike for every
+        // binary32 residual, 1e-8f < 1e-8 < its successor makes `g2 < 1e-8` the binary32 test `g2 <= 1e-8f`
         if (residual < 1e-3f) break;
         const float g2 = gx * gx + gy * gy;
-        if (g2 < 1e-8f) break;
+        if (g2 <= 1e-8f) break;
         const float k = residual / g2;
         x -= gx * k;
         y -= gy * k;

@@ -17,6 +17,7 @@ from .. import grid_eval as _grid_eval
 
 LINK_OVERFLOW_MASK = 0xfff00000   # polygon2d.py:11
 _EMPTY = 0xffffffff
+MAX_BLOCKS_PER_LAUNCH = 65535     # hu_process_polygon_blocks puts the block on gridDim.y
 
 
 def _step_from_overflow_spec(spec):
@@ -69,6 +70,25 @@ def stitch(blocks, int_box_step):
             yield chain
 
 
+def launch_process_polygon_blocks(lib, n, dims, resolution, origin, step, corners, blocks, vertices, links, starts, counters,
+                                  stream):
+    """hu_process_polygon_blocks over n blocks whose arrays start at the given device addresses (integers), in as
+    many launches as the limit of blocks per launch asks for: a fine subdivision of a large shape has more leaf
+    blocks than one launch takes.  Per block: float4[gx*gy] corners, int4 block, float2[cells] vertices,
+    uint[cells] links, uint[max((gx-1)+(gy-1), 1)] starts, one counter."""
+    gx, gy = int(dims[0]), int(dims[1])
+    cells = (gx - 1) * (gy - 1) * 2
+    per_block_starts = max((gx - 1) + (gy - 1), 1)
+    d = (ctypes.c_uint32 * 2)(gx, gy)
+    o = (ctypes.c_double * 3)(*origin)
+    for first in range(0, n, MAX_BLOCKS_PER_LAUNCH):
+        count = min(MAX_BLOCKS_PER_LAUNCH, n - first)
+        check(lib.hu_process_polygon_blocks(corners + first * gx * gy * 16, blocks + first * 16, count, float(resolution), o,
+                                            numpy.float32(step), d, vertices + first * cells * 8, links + first * cells * 4,
+                                            starts + first * per_block_starts * 4, counters + first * 4, stream),
+              "hu_process_polygon_blocks")
+
+
 def contour_blocks(leaves, queue=None):
     """GPU part: -> (int_corners (n, 2) int, vertices (n, cells, 2) f32, links (n, cells) u32,
     starts list of u32 arrays), blocks sorted by integer corner."""
@@ -87,13 +107,11 @@ def contour_blocks(leaves, queue=None):
     starts = hip_util.Buffer(numpy.uint32, (n, per_block_starts), queue=queue)
     counters = hip_util.Buffer(numpy.uint32, (n,), queue=queue)
     counters.enqueue_fill(0)   # same in-order stream as the launches below
-    d = (ctypes.c_uint32 * 2)(gx, gy)
-    o = (ctypes.c_double * 3)(leaves.origin.x, leaves.origin.y, leaves.origin.z)
     ev = hip_util.Event(hip_manager, queue)
-    check(hip_manager.lib.hu_process_polygon_blocks(corners.device_ptr, leaves.blocks.device_ptr, n,
-                                                    float(leaves.resolution), o, numpy.float32(leaves.step), d,
-                                                    vertices.device_ptr, links.device_ptr, starts.device_ptr,
-                                                    counters.device_ptr, queue.handle), "hu_process_polygon_blocks")
+    launch_process_polygon_blocks(hip_manager.lib, n, (gx, gy), leaves.resolution,
+                                  (leaves.origin.x, leaves.origin.y, leaves.origin.z), leaves.step, corners.device_ptr,
+                                  leaves.blocks.device_ptr, vertices.device_ptr, links.device_ptr, starts.device_ptr,
+                                  counters.device_ptr, queue.handle)
     ev._done()
     host_blocks = numpy.empty((leaves.blocks.shape[0], 4), dtype=numpy.int32)
     leaves.blocks.read(out=host_blocks)

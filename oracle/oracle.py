@@ -10,6 +10,9 @@ import subprocess
 
 import numpy as np
 
+from . import ref_cl
+from .ref_cl import ref_process_polygon  # noqa: F401  (the reference's kernel itself; raises where oracle/_ref is not built)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "liboracle.so")
 _LITERAL_PATH = os.path.join(_HERE, "_build", "libliteral.so")
@@ -17,7 +20,7 @@ _LITERAL64_PATH = os.path.join(_HERE, "_build", "libliteral64.so")
 _lib = None
 _literal = {}
 
-__all__ = ["build", "lib", "evaluate_points", "grid_eval", "grid_eval_pymcubes", "ray_caster", "ray_caster_instances", "InstancePicture", "bitmap", "process_polygon", "marching_cubes", "stl_records", "STL_RECORD",
+__all__ = ["build", "lib", "evaluate_points", "grid_eval", "grid_eval_pymcubes", "ray_caster", "ray_caster_instances", "InstancePicture", "bitmap", "process_polygon", "ref_process_polygon", "marching_cubes", "stl_records", "STL_RECORD",
            "subdivision_step", "mass_properties", "det_math", "evaluate_points_literal", "grid_distance_literal",
            "literal_scene", "mass_properties_literal"]
 
@@ -27,7 +30,9 @@ _u8p = ctypes.POINTER(ctypes.c_uint8)
 
 
 def build(force=False):
-    """Compile the oracle with gcc (a few seconds).  Building the checker is not using it."""
+    """Compile the oracle with gcc (a few seconds).  Building the checker is not using it.  Where the reference tree
+    is present, its own contouring kernel is built into oracle/_ref as well (oracle/ref_cl.py)."""
+    ref_cl.build(force)
     src = [os.path.join(_HERE, f) for f in ("sdf_oracle.c", "sdf_literal.c", "det_math.h", "mc_table.h", "Makefile")]
     libs = (_LIB_PATH, _LITERAL_PATH, _LITERAL64_PATH)
     if (not force and all(os.path.exists(b) for b in libs)

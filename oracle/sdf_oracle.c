@@ -1017,8 +1017,9 @@ int oracle_bitmap(const float *tape, int n_tape, const float *origin, float step
  * 2D contouring -- SURVEY.md section 8(f) rank 4.  Restated from reference
  * rendering/polygon2d.cl:1-175 (encode_index :5-36, place_vertex :38-80, process_polygon :82-175).
  * The reference's tests never run this kernel (tests/test_polygons2d.py covers the polygon SHAPE
- * only) and there are no fixtures for it: PARITY UNPINNED beyond this line-by-line restatement;
- * tests/test_polygon2d_render.py checks geometric properties of the contours.
+ * only) and ships no fixtures for it; the kernel itself is compiled for the CPU by oracle/ref_cl.py and
+ * tests/test_polygon2d_reference_host.py holds this restatement to it bit for bit on synthetic fields (recorded
+ * in tests/golden/polygon2d_ref.npz); tests/test_polygon2d_render.py checks geometric properties of the contours.
  * `corners`: float4[gx*gy] as written by grid_eval over (gx, gy, 1), index y + gy*x.
  * Global size of the reference launch = (gx-1, gy-1, 2); index = t + 2*(y + (gy-1)*x).
  * `starts` are appended in (x, y, t) scan order here (the reference's atomic order is unspecified).
@@ -1057,9 +1058,12 @@ static void pp_place_vertex(const float pos[3][2], const f4 val[3], float out[2]
             gx += nx * tmp;
             gy += ny * tmp;
         }
-        if (residual < 1e-3f) break;
+        /* polygon2d.cl:69,74 compare with the double literals 1e-3 and 1e-8.  1e-3f lies above 1e-3, so a float
+         * literal would decide alike there; 1e-8f lies below 1e-8, so g2 == 1e-8f breaks here and would not
+         * with a float literal. */
+        if ((double)residual < 1e-3) break;
         float g2 = gx * gx + gy * gy;
-        if (g2 < 1e-8f) break;
+        if ((double)g2 < 1e-8) break;
         float k = residual / g2;
         px -= gx * k;
         py -= gy * k;

@@ -20,7 +20,7 @@ from .hip_util import manager as hip_manager, check
 
 MAX_INSTANCES = 64          # one bit each in a cell's candidate mask
 _ROW = 16                   # bytes per cell row {x0 | y0 << 16, z0, mask lo, mask hi}
-_TABLE_RECORD = 24          # bytes per instance of the device table (launchers.hpp InstanceRec)
+_TABLE_RECORD = 24          # bytes per instance of the device table (instance_args.hpp InstanceRec)
 _MAX_TOP_CELLS = 1 << 15
 _TAPES_PER_PART = MAX_INSTANCES            # placements of one part whose uploaded tapes are kept (instance_tape)
 

@@ -40,7 +40,7 @@ import numpy
 from . import _instance_cells as cells
 from ._instance_cells import Instance
 
-# the accumulators of a pair (launchers.hpp NearAcc)
+# the accumulators of a pair (instance_args.hpp NearAcc)
 _PAIR = numpy.dtype([("sums", "<u8", (4,)), ("witness", "<u8"), ("lo", "<u4", (3,)), ("hi", "<u4", (3,)), ("key", "<u4"),
                      ("pad", "<u4")])
 

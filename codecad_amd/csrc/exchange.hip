@@ -15,12 +15,7 @@
 // written branch-free as well.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <string>
-
-#include "../../include/hip_util.h"
-
-int hu_fail_external(int code, const char* message);   // hip_util.hip: sets the thread's last error
+#include "host.hpp"
 
 namespace {
 
@@ -76,16 +71,16 @@ k_slice_rows(const uint4* __restrict__ gathered, uint32_t world, uint32_t piece_
 static int slice_rows(const void* gathered_dev, uint32_t pieces, uint32_t piece_rows, uint32_t row_bytes, uint32_t rank, uint32_t sharers,
                       void* out_dev, uint32_t out_capacity, uint32_t* stats_dev, void* stream)
 {
-    if (!gathered_dev || !out_dev || !stats_dev) return hu_fail_external(HU_ERR_BAD_ARG, "NULL argument");
+    if (!gathered_dev || !out_dev || !stats_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (pieces == 0 || pieces > kMaxWorld || sharers == 0 || sharers > kMaxWorld || rank >= sharers)
-        return hu_fail_external(HU_ERR_BAD_ARG, "world must be in 1..64 and rank below it");
-    if (row_bytes == 0 || row_bytes % 16 != 0) return hu_fail_external(HU_ERR_BAD_ARG, "row_bytes must be a multiple of 16");
-    if (piece_rows == 0) return hu_fail_external(HU_ERR_BAD_ARG, "a piece has at least its header row");
+        return hu_fail(HU_ERR_BAD_ARG, "world must be in 1..64 and rank below it");
+    if (row_bytes == 0 || row_bytes % 16 != 0) return hu_fail(HU_ERR_BAD_ARG, "row_bytes must be a multiple of 16");
+    if (piece_rows == 0) return hu_fail(HU_ERR_BAD_ARG, "a piece has at least its header row");
     const uint32_t blocks = out_capacity / 256u + 1u;
     hipLaunchKernelGGL(k_slice_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)gathered_dev, pieces,
                        piece_rows, row_bytes / 16u, rank, sharers, (uint4*)out_dev, out_capacity, stats_dev);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hu_fail_external(HU_ERR_HIP, (std::string("k_slice_rows: ") + hipGetErrorString(e)).c_str());
+    if (e != hipSuccess) return hu_fail(HU_ERR_HIP, std::string("k_slice_rows: ") + hipGetErrorString(e));
     return HU_OK;
 }
 

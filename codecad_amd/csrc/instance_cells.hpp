@@ -4,10 +4,16 @@
 //
 // A CELL is a cube of 4^k lattice samples, a 16-byte row {x0 | y0 << 16, z0, mask lo, mask hi}: its first sample's indices
 // and the 64-bit mask of the instances still candidates in it.  One wavefront takes one cell, lane = 16 x + 4 y + z of its
-// 4 x 4 x 4 parts.  Every such kernel takes hu_cells::Args (launchers.hpp).
+// 4 x 4 x 4 parts.  Every such kernel takes hu_cells::Args (instance_args.hpp).  The end of this file has what the entry
+// points of such kernels check, fill and launch alike.
 #pragma once
 
-#include "launchers.hpp"
+#include <cmath>
+#include <cstring>
+
+#include "host.hpp"
+#include "instance_args.hpp"
+#include "kernels.hpp"
 
 namespace hu_cells {
 
@@ -97,6 +103,73 @@ __device__ __forceinline__ void add_samples(Acc* acc, bool both, uint64_t b, uin
     if (lane < 4u) atomicAdd(&acc->sums[lane], add);
     else if (lane < 7u) atomicMin(&acc->lo[k], bound);
     else if (lane < 10u) atomicMax(&acc->hi[k], bound);
+}
+
+// ------------------------------------------------------------------------------------------
+// host side: the entry points over instance cells (instance_pairs.hip, instance_section.hip, instance_mass.hip)
+// ------------------------------------------------------------------------------------------
+
+// What every entry point over instance cells checks and fills.  The entry points of `clearance` also want the windows,
+// a z extent within 16 bits (the witness packs an index into 16 bits per axis) and a finite step >= 0; interference's
+// were released without those checks and keep accepting what they accepted.
+inline int cells_args(bool clearance, const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev,
+                      const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+                      uint64_t* evaluations_dev, Args& a)
+{
+    if (!table_dev || (clearance && !windows_dev) || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
+        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n == 0 || n > 64u) return hu_fail(HU_ERR_BAD_ARG, "1..64 instances");
+    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0 || dims[0] > 65536u || dims[1] > 65536u || (clearance && dims[2] > 65536u))
+        return hu_fail(HU_ERR_BAD_ARG, clearance ? "lattice dims must be in 1..65536" : "lattice dims must be positive, x and y at most 65536");
+    if (clearance && (!std::isfinite(step) || step < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    std::memset(&a, 0, sizeof(a));
+    a.table = static_cast<const InstanceRec*>(table_dev);
+    a.windows = windows_dev;
+    a.n_instances = n;
+    a.parents = static_cast<const uint4*>(parents_dev);
+    a.n_parents_dev = n_parents_dev;
+    a.max_parents = max_parents;
+    for (int i = 0; i < 3; ++i) {
+        a.dims[i] = dims[i];
+        a.corner[i] = corner[i];
+    }
+    a.step = step;
+    a.evaluations = reinterpret_cast<unsigned long long*>(evaluations_dev);
+    return HU_OK;
+}
+
+// ... and what those of a level above the finest one add: the children's list, their side and the threshold that drops a
+// candidate.  The bounds of child_side and thr are each check's own: its entry point tests them after this.
+inline int cells_children(Args& a, uint32_t child_side, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity)
+{
+    if (!counter_dev || (!children_dev && capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    a.child_side = child_side;
+    a.thr = thr;
+    a.counter = counter_dev;
+    a.children = static_cast<uint4*>(children_dev);
+    a.capacity = capacity;
+    return HU_OK;
+}
+
+// The launch of `kernel` over the cells of `a`, which is `k` or a part of it: a wavefront per cell, in workgroups of four
+// wavefronts while their LDS fits 48 KiB (host.hpp hu_workgroup), as launch_shape() sizes the one-voxel interpreter kernels.
+// A lane's LDS: `lane_bytes`, the register file of the largest instance, then `extra_lane_bytes` (clearance's w area at the
+// finest level, the section's at its tiles: 4 bytes per instance and lane).
+template <class K>
+int cells_launch(void (*kernel)(K), K& k, Args& a, uint32_t lane_bytes, size_t extra_lane_bytes, void* stream)
+{
+    uint32_t block;
+    size_t lds;
+    int rc;
+    if ((rc = hu_workgroup((size_t)lane_bytes + extra_lane_bytes, block, lds))) return rc;
+    if ((rc = hu_ensure_attrs())) return rc;
+    a.scratch_offset = lane_bytes * block;
+    const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
+    if (blocks == 0) return HU_OK;
+    if (blocks > 0x7fffffffull) return hu_fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(block), lds, (hipStream_t)stream, k);
+    HU_HIP(hipGetLastError());
+    return HU_OK;
 }
 
 }  // namespace hu_cells

@@ -25,8 +25,8 @@
 //     first lane whose v has the pair's final least key gives one u64 atomicMin of x << 32 | y << 16 | z.  Lanes go
 //     16 x + 4 y + z, so the wavefront's first such lane is its lexicographically smallest sample.
 // All read their parent count from the list's header on the device (the *_indirect pattern of the other level kernels).
-// Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).  hip_util.hip validates
-// arguments and calls the launch functions at the end of this file.
+// Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).  The entry points are at the
+// end of this file.
 #include "instance_cells.hpp"
 
 using namespace sdfk;
@@ -222,32 +222,104 @@ __global__ void __launch_bounds__(256) k_clearance_witness(const Args a)
     });
 }
 
-// [Kernel][distance_only]
-void (*const kKernelTable[kKernels][2])(Args) = {
-    {k_instance_cells<false, false>, k_instance_cells<true, false>},
-    {k_interference_leaf<false>, k_interference_leaf<true>},
-    {k_instance_cells<false, true>, k_instance_cells<true, true>},
-    {k_clearance_leaf<false>, k_clearance_leaf<true>},
-    {k_clearance_witness<false>, k_clearance_witness<true>},
+void (*const kKernels[])(Args) = {
+    k_instance_cells<false, false>, k_instance_cells<true, false>, k_interference_leaf<false>, k_interference_leaf<true>,
+    k_instance_cells<false, true>,  k_instance_cells<true, true>,  k_clearance_leaf<false>,    k_clearance_leaf<true>,
+    k_clearance_witness<false>,     k_clearance_witness<true>,
 };
+
+// a level of cells above the finest one, of either check
+int cells_level(bool clearance, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                uint32_t child_side, const uint32_t dims[3], const float corner[3], float step, float thr, uint32_t* counter_dev,
+                void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream)
+{
+    Args a;
+    int rc;
+    if ((rc = cells_args(clearance, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+        return rc;
+    if ((rc = cells_children(a, child_side, thr, counter_dev, children_dev, capacity))) return rc;
+    if (child_side < 4u || child_side > 16384u) return hu_fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
+    if (clearance && (!std::isfinite(thr) || thr < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    const auto kernel = clearance ? (distance_only_kernel ? k_instance_cells<true, true> : k_instance_cells<false, true>)
+                                  : (distance_only_kernel ? k_instance_cells<true, false> : k_instance_cells<false, false>);
+    return cells_launch(kernel, a, a, lane_bytes, 0u, stream);
+}
+
+// a launch over the finest cells: interference's leaf (no windows, no t), clearance's leaf or witness
+int cells_finest(void (*kernel)(Args), bool clearance, const void* table_dev, uint32_t n, uint32_t lane_bytes, const uint32_t* windows_dev,
+                 const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3],
+                 const float corner[3], float step, float t, void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+{
+    Args a;
+    int rc;
+    if ((rc = cells_args(clearance, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
+        return rc;
+    if (!pairs_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (clearance && (!std::isfinite(t) || t < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "t must be finite and not negative");
+    a.child_side = 1u;
+    a.t = t;
+    a.pairs = pairs_dev;
+    return cells_launch(kernel, a, a, lane_bytes, clearance ? 4u * n : 0u, stream);
+}
 
 }  // namespace
 
-namespace hu_cells {
-
-hipError_t allow_big_lds(size_t bytes)
+hipError_t hu_cells::allow_big_lds(size_t bytes)
 {
     hipError_t e = hipSuccess;
-    for (const auto& kernel : kKernelTable)
-        for (const auto variant : kernel)
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    for (const auto kernel : kKernels)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     return e;
 }
 
-hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream)
+extern "C" {
+
+int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
+                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                   uint64_t* evaluations_dev, void* stream)
 {
-    hipLaunchKernelGGL(kKernelTable[kernel][distance_only], dim3(blocks), dim3(block), lds, stream, a);
-    return hipGetLastError();
+    return cells_level(false, table_dev, n, distance_only_kernel, lane_bytes, nullptr, parents_dev, n_parents_dev, max_parents,
+                       child_side, dims, corner, step, thr, counter_dev, children_dev, capacity, evaluations_dev, stream);
 }
 
-}  // namespace hu_cells
+int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
+                                  uint64_t* evaluations_dev, void* stream)
+{
+    return cells_finest(distance_only_kernel ? k_interference_leaf<true> : k_interference_leaf<false>, false, table_dev, n, lane_bytes,
+                        nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, 0.0f, pairs_dev, evaluations_dev, stream);
+}
+
+int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                                uint32_t max_parents, uint32_t child_side, const uint32_t dims[3], const float corner[3],
+                                float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                                uint64_t* evaluations_dev, void* stream)
+{
+    return cells_level(true, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev, n_parents_dev, max_parents,
+                       child_side, dims, corner, step, thr, counter_dev, children_dev, capacity, evaluations_dev, stream);
+}
+
+int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                               const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                               uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
+                               void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+{
+    return cells_finest(distance_only_kernel ? k_clearance_leaf<true> : k_clearance_leaf<false>, true, table_dev, n, lane_bytes,
+                        windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+}
+
+int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
+                                  const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                                  uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
+                                  void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+{
+    return cells_finest(distance_only_kernel ? k_clearance_witness<true> : k_clearance_witness<false>, true, table_dev, n, lane_bytes,
+                        windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+}
+
+}  // extern "C"

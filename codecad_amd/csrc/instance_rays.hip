@@ -20,8 +20,10 @@
 // goes first, so that the minimum is tight from the first comparison; the tie rule compares indices and holds in any order.
 // Four bytes per instance and lane instead of the 16 of (w_k, q_k): 64 instances take 16 KiB per wavefront, not 64 KiB
 // (DESIGN.md section 9 has the arithmetic).
-// Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).
+// Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).  The entry point is at the end of
+// this file.
 #include "instance_cells.hpp"
+#include "launchers.hpp"
 
 using namespace sdfk;
 using namespace hu_cells;
@@ -131,17 +133,46 @@ __global__ void __launch_bounds__(256) k_ray_caster_instances(const RayArgs t, c
 
 }  // namespace
 
-namespace hu_cells {
-
-hipError_t allow_big_lds_rays(size_t bytes)
+hipError_t hu_cells::allow_big_lds_rays(size_t bytes)
 {
     return hipFuncSetAttribute((const void*)k_ray_caster_instances, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-hipError_t ray_caster_instances(const RayArgs& t, const RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream)
+extern "C" int hu_ray_caster_instances(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const float origin[4],
+                                       const float forward[4], const float up[4], const float right[4], float pixel_tolerance,
+                                       float box_radius, float min_distance, float max_distance, float floor_z, uint32_t render_options,
+                                       uint32_t width, uint32_t height, const void* colors_dev, void* out_dev, int32_t* part_ids_dev,
+                                       float* depth_dev, uint32_t flags, uint64_t* counters_dev, void* stream)
 {
-    hipLaunchKernelGGL(k_ray_caster_instances, dim3(blocks), dim3(block), lds, stream, t, a);
-    return hipGetLastError();
+    if (!table_dev || !origin || !forward || !up || !right || !colors_dev || !out_dev || !part_ids_dev || !depth_dev)
+        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n == 0 || n > 64u) return hu_fail(HU_ERR_BAD_ARG, "1..64 instances");
+    if (distance_only_kernel) return hu_fail(HU_ERR_BAD_ARG, "the ray caster needs a table of full programs (hu_instance_table)");
+    if (lane_bytes == 0 || lane_bytes % 16u) return hu_fail(HU_ERR_BAD_ARG, "lane_bytes of a table of full programs is a multiple of 16");
+    if (width == 0 || height == 0) return hu_fail(HU_ERR_BAD_ARG, "image must have at least one pixel");
+    if (render_options > 3u) return hu_fail(HU_ERR_BAD_ARG, "unknown render option bits");
+    if (flags > 1u) return hu_fail(HU_ERR_BAD_ARG, "unknown flag bits");
+    // a lane's LDS: the register file every instance's program fits, then one float per instance (the bounds of SKIPPING)
+    uint32_t block;
+    size_t lds;
+    int rc;
+    if ((rc = hu_workgroup((size_t)lane_bytes + 4u * n, block, lds))) return rc;
+    if ((rc = hu_ensure_attrs())) return rc;
+    const uint64_t tiles = (uint64_t)((width + 7u) / 8u) * ((height + 7u) / 8u);
+    const uint64_t blocks = (tiles + block / 64u - 1) / (block / 64u);
+    if (blocks > 0x7fffffffull) return hu_fail(HU_ERR_BAD_ARG, "image too large for one launch");
+    const RayCasterArgs a = hu_render::ray_caster_args(origin, forward, up, right, pixel_tolerance, box_radius, min_distance, max_distance,
+                                                       floor_z, render_options, width, height, out_dev);
+    RayArgs t;
+    t.table = static_cast<const InstanceRec*>(table_dev);
+    t.n_instances = n;
+    t.colors = static_cast<const float4*>(colors_dev);
+    t.part_ids = part_ids_dev;
+    t.depth = depth_dev;
+    t.counters = reinterpret_cast<unsigned long long*>(counters_dev);
+    t.flags = flags;
+    t.bounds_offset = lane_bytes * block;
+    hipLaunchKernelGGL(k_ray_caster_instances, dim3((uint32_t)blocks), dim3(block), lds, (hipStream_t)stream, t, a);
+    HU_HIP(hipGetLastError());
+    return HU_OK;
 }
-
-}  // namespace hu_cells

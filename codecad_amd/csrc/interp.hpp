@@ -86,7 +86,7 @@ __device__ __forceinline__ m1 operator&(m1 a, m1 b) { return m1{a.v && b.v, a.w 
 __device__ __forceinline__ m1 operator|(m1 a, m1 b) { return m1{a.v || b.v, a.w | b.w}; }
 __device__ __forceinline__ m2 operator&(m2 a, m2 b) { return m2{a.x && b.x, a.y && b.y, a.wx & b.wx, a.wy & b.wy}; }
 __device__ __forceinline__ m2 operator|(m2 a, m2 b) { return m2{a.x || b.x, a.y || b.y, a.wx | b.wx, a.wy | b.wy}; }
-// complement, and the masks of "all lanes" -- for the path masks of deferred directions (hip_util.hip generate_source)
+// complement, and the masks of "all lanes" -- for the path masks of deferred directions (tape_build.hip generate_source)
 __device__ __forceinline__ m1 operator~(m1 a) { return m1{!a.v, ~a.w}; }
 __device__ __forceinline__ m2 operator~(m2 a) { return m2{!a.x, !a.y, ~a.wx, ~a.wy}; }
 __device__ __forceinline__ m1 gt(float a, float b) { return mk(a > b); }

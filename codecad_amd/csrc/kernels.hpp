@@ -2,7 +2,7 @@
 //
 // The gfx950 kernels of the hot path, generic over HOW a voxel is evaluated:
 //   * InterpEval<DO>: the tape interpreter (interp.hpp run_tape), registers in LDS;
-//   * a specialised evaluator generated per tape and compiled with hipRTC (jit in hip_util.hip).
+//   * a specialised evaluator generated per tape and compiled with hipRTC (built in tape_build.hip).
 // Reference counterparts (paths relative to /root/reference/codecad/):
 //   k_grid_eval            grid_eval.cl:2-34 (both layouts), dense slab of a logical grid
 //   k_grid_eval_blocks     the per-leaf-block launches of rendering/mesh.py:53-60, batched

@@ -1,18 +1,23 @@
-// codecad_amd/csrc/launchers.hpp -- what hip_util.hip calls in render.hip and instance_pairs.hip.
+// codecad_amd/csrc/launchers.hpp -- the two launches that cross a unit boundary, and what both ray casters fill alike.
 //
-// Translation units that hold kernels (hip_util/builder.py lists the flags of each):
-//   hip_util.hip  the dense / leaf-block / classification kernels over the tape interpreter, built with
-//                 -mllvm -structurizecfg-skip-uniform-regions (the interpreter's dispatch loop needs it);
-//   render.hip    every other kernel -- ray caster, bitmap, 2D contouring, the mass-integral reduction, the
-//                 arithmetic self-test -- built WITHOUT it: that option once let a scalar branch choose a per-lane
-//                 value in a divergent loop (csrc/exchange.hip), so it stays confined to the kernels that are
-//                 nothing but the interpreter's wave-uniform loop around branch-free ops;
+// Translation units (hip_util/builder.py lists the flags of each).  A unit holds its kernels AND their extern "C" entry
+// points; what the host code of all of them shares is in host.hpp.
+//   hip_util.hip  the tape handle and the launches of the dense / leaf-block / classification kernels over the tape
+//                 interpreter, built with -mllvm -structurizecfg-skip-uniform-regions (the interpreter's dispatch loop
+//                 needs it);
+//   tape_build.hip  host only: a tape's own kernels, generated, compiled with hipRTC, cached on disk and loaded;
+//   render.hip    every other kernel over one tape or none -- ray caster, bitmap, 2D contouring, the mass-integral
+//                 reduction, the arithmetic self-test -- built WITHOUT that option: it once let a scalar branch choose a
+//                 per-lane value in a divergent loop (csrc/exchange.hip), so it stays confined to the kernels that are
+//                 nothing but the interpreter's wave-uniform loop around branch-free ops.  The tape's ray caster and
+//                 bitmap are validated and shaped in hip_util.hip, which knows the tape, and launched through the two
+//                 functions below;
 //   instance_pairs.hip  the interference and clearance checks between the instances of an assembly, built without
 //                 it as well;
 //   instance_rays.hip   the ray caster over the instances of an assembly (codecad_amd/rendering/assembly_picture.py), likewise;
 //   instance_section.hip  the planar section of an assembly (codecad_amd/section.py), likewise;
 //   instance_mass.hip   the mass properties of an assembly (codecad_amd/assembly_mass.py), likewise;
-// Each function enqueues one launch and returns hipGetLastError().
+//   sort.hip, exchange.hip, mesh.hip  the sort of a block list, the exchange step of the multi-GPU levels, marching cubes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,125 +26,33 @@
 
 namespace hu_render {
 
-hipError_t allow_big_lds(size_t bytes);   // dynamic LDS above 64 KiB for the interpreter instantiations of this unit
+// each enqueues one launch and returns hipGetLastError()
 hipError_t ray_caster(const sdfk::InterpEval<false>& ev, const sdfk::RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds,
                       hipStream_t stream);
 hipError_t bitmap(bool distance_only, const sdf::Rec* prog, const float* extra, uint32_t n4, float ox, float oy, float oz,
                   float step_size, uint32_t width, uint32_t height, uint8_t* out, uint32_t blocks, uint32_t block, size_t lds,
                   hipStream_t stream);
-hipError_t process_polygon(bool batch, const sdfk::PolygonArgs& a, dim3 grid, hipStream_t stream);
-hipError_t mass_integrals(const double4* parents, const uint32_t* sums, uint32_t n_parents, uint32_t per_row, const uint32_t* n_parents_dev,
-                          double s, double* out, uint32_t rows, hipStream_t stream);
-hipError_t selftest_math(unsigned long long* counts_dev);
-hipError_t selftest_minmax3(unsigned long long* counts_dev);
+
+// the camera and the picture of hu_ray_caster and hu_ray_caster_instances
+inline sdfk::RayCasterArgs ray_caster_args(const float origin[4], const float forward[4], const float up[4], const float right[4],
+                                           float pixel_tolerance, float box_radius, float min_distance, float max_distance,
+                                           float floor_z, uint32_t render_options, uint32_t width, uint32_t height, void* out_dev)
+{
+    sdfk::RayCasterArgs a;
+    a.origin = sdfk::mk3(origin[0], origin[1], origin[2]);
+    a.forward = sdfk::mk3(forward[0], forward[1], forward[2]);
+    a.up = sdfk::mk3(up[0], up[1], up[2]);
+    a.right = sdfk::mk3(right[0], right[1], right[2]);
+    a.pixel_tolerance = pixel_tolerance;
+    a.box_radius = box_radius;
+    a.min_distance = min_distance;
+    a.max_distance = max_distance;
+    a.floor_z = floor_z;
+    a.options = render_options;
+    a.w = width;
+    a.h = height;
+    a.out = static_cast<uint8_t*>(out_dev);
+    return a;
+}
 
 }  // namespace hu_render
-
-namespace hu_cells {
-
-// one instance of the device table: the program the kernels interpret for it (distance-only or full, the same kind for
-// every instance of a launch), its constants and the float4 slots of the register file (the same for every instance)
-struct InstanceRec {
-    const sdf::Rec* prog;
-    const float* extra;
-    uint32_t n4, pad;
-};
-static_assert(sizeof(InstanceRec) == 24, "hu_interference_table writes 24-byte records");
-
-// interference: the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j]: samples inside both, the sums
-// of their x, y, z indices, and the box of those indices (lo starts at 0xffffffff, hi at 0)
-struct OverlapAcc {
-    unsigned long long sums[4];   // count, sum x, sum y, sum z
-    uint32_t lo[3], hi[3];
-    uint32_t pad[2];
-};
-static_assert(sizeof(OverlapAcc) == 64, "interference.py reads 64-byte accumulators");
-
-// clearance: the same over the pair's NEAR samples (in both instances' windows, w_i < t and w_j < t), the order key of
-// the least v = max(w_i, w_j) (starts at 0xffffffff, instance_pairs.hip order_key) and the witness, the least
-// x << 32 | y << 16 | z of the near samples whose v is that least one (starts at ~0)
-struct NearAcc {
-    unsigned long long sums[4];   // count, sum x, sum y, sum z
-    unsigned long long witness;
-    uint32_t lo[3], hi[3];
-    uint32_t key;
-    uint32_t pad;
-};
-static_assert(sizeof(NearAcc) == 72, "clearance.py reads 72-byte accumulators");
-
-// mass properties of an assembly (instance_mass.hip): per instance k the ten index sums n, x, y, z, xx, yy, zz, xy, xz, yz
-// over V_k, the samples inside k, and over O_k, those inside k and inside no instance of lower index, and the index box of
-// V_k (lo starts at 0xffffffff, hi at 0)
-struct MassAcc {
-    unsigned long long v[10];
-    unsigned long long o[10];
-    uint32_t lo[3], hi[3];
-    uint32_t pad[2];
-};
-static_assert(sizeof(MassAcc) == 192, "assembly_mass.py reads 192-byte accumulators");
-
-// the arguments of every kernel over instance cells; interference leaves `windows` and `t` null and zero and never reads them
-struct Args {
-    const InstanceRec* table;
-    const uint32_t* windows;         // n_instances x {lo x, y, z, hi x, y, z}: the samples an instance may be near at
-    uint32_t n_instances;
-    const uint4* parents;            // rows {x0 | y0 << 16, z0, mask lo, mask hi} after the list's header row
-    const uint32_t* n_parents_dev;   // word 0 of the parents' header
-    uint32_t max_parents;            // the parents' capacity (the launch is sized for it)
-    uint32_t child_side;             // cells: side of a child cell in samples (finest level: 1)
-    uint32_t dims[3];
-    float corner[3], step;
-    float thr;                       // cells: a candidate whose distance at a child's centre is >= thr leaves the child
-    float t;                         // clearance's finest level: near means w < t
-    uint32_t* counter;               // cells: word 0 of the children's header
-    uint4* children;                 // cells: the children's rows
-    uint32_t capacity;
-    void* pairs;                     // finest level: n_instances^2 OverlapAcc (interference) or NearAcc (clearance)
-    unsigned long long* evaluations; // per-instance sample evaluations, added up per wavefront
-    uint32_t scratch_offset;         // bytes of LDS taken by the register file (cells: the compaction's scratch follows;
-                                     // clearance's finest level: the w of every instance, 256 bytes per instance and wavefront)
-    uint32_t flags;                  // instance_mass.hip: kMassRetire
-};
-constexpr uint32_t kMassRetire = 1u;     // a child whose candidates are all provably full adds closed-form sums and leaves the lists
-
-enum Kernel { kInterferenceCells, kInterferenceLeaf, kClearanceCells, kClearanceLeaf, kClearanceWitness, kKernels };
-enum MassKernel { kMassCells, kMassLeaf, kMassKernels };   // (instance_mass.hip; rows of 32 bytes, `pairs` n_instances MassAcc)
-
-// the ray caster over the instance table (instance_rays.hip): what it takes beside sdfk::RayCasterArgs
-struct RayArgs {
-    const InstanceRec* table;        // every instance's FULL program (directions steer the march)
-    uint32_t n_instances;
-    const float4* colors;            // n_instances hues {r, g, b, unused} in [0, 1]
-    int32_t* part_ids;               // [w * h], index y + h * x like the pixels: the instance under the pixel, -1 for none
-    float* depth;                    // [w * h]: the primary ray's distance where it hit, +inf where not
-    unsigned long long* counters;    // NULL, or {instance programs run, instance programs asked for}, added up per wavefront
-    uint32_t flags;                  // bit 0: every instance at every sample (no skipping)
-    uint32_t bounds_offset;          // bytes of LDS taken by the register file; the lanes' bounds follow, [instance][lane]
-};
-constexpr uint32_t kRaysNoSkip = 1u;
-
-// the planar section of an assembly (instance_section.hip): what its kernels take beside Args.  There Args describes a 2D
-// lattice on the plane: dims = {samples along u, along v, 1}, corner = the 3D position of sample (0, 0), a row is a TILE
-// {x0 | y0 << 16, unused, mask lo, mask hi} of 8^k x 8^k samples, windows (n x 6, the third index 0) the samples an
-// instance may be inside at, thr the radius of a child tile, and pairs n_instances^2 OverlapAcc whose diagonal [k][k]
-// holds the samples inside instance k.
-struct SectionArgs {
-    Args c;
-    float u[3], v[3];                // the plane's unit vectors: sample (i, j) sits at (corner + u * (step * i)) + v * (step * j)
-    int32_t* part_ids;               // leaf: [dims v][dims u] maps; the lowest instance a sample is inside of (prefilled with -1)
-    uint8_t* inside_count;           //   how many it is inside of (prefilled with 0)
-    float* distance;                 //   WITH_DISTANCE: the least w of all instances
-    int32_t* nearest;                //   WITH_DISTANCE: the lowest instance that attains it
-};
-
-hipError_t allow_big_lds(size_t bytes);
-hipError_t allow_big_lds_rays(size_t bytes);
-hipError_t allow_big_lds_section(size_t bytes);
-hipError_t allow_big_lds_mass(size_t bytes);
-hipError_t mass(MassKernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
-hipError_t section(bool leaf, bool distance_only, bool with_distance, const SectionArgs& a, uint32_t blocks, uint32_t block, size_t lds,
-                   hipStream_t stream);
-hipError_t ray_caster_instances(const RayArgs& t, const sdfk::RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
-hipError_t level(Kernel kernel, bool distance_only, const Args& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream);
-
-}  // namespace hu_cells

@@ -10,36 +10,24 @@
 // bits of per-lane masks -- exactly that shape -- so they are built without it.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
 #include <cstdlib>
-#include <string>
 
-#include "../../include/hip_util.h"
+#include "host.hpp"
 #include "mesh_kernels.hpp"
-
-int hu_fail_external(int code, const char* message);   // hip_util.hip: sets the thread's last error
 
 using namespace sdfk;
 
 namespace {
 
-int fail(int code, const char* message) { return hu_fail_external(code, message); }
-
-#define HU_HIP(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return hu_fail_external(HU_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
 // Fills the shape part of McArgs; n_wg = workgroups of 256 segments over all blocks.
 int mesh_shape(uint32_t n_blocks, const uint32_t dims[3], McArgs& a, uint64_t& n_wg)
 {
     uint64_t samples;
-    if (!dims) return fail(HU_ERR_BAD_ARG, "dims is NULL");
-    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0) return fail(HU_ERR_BAD_ARG, "dims must be >= 1 on every axis");
+    if (!dims) return hu_fail(HU_ERR_BAD_ARG, "dims is NULL");
+    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0) return hu_fail(HU_ERR_BAD_ARG, "dims must be >= 1 on every axis");
     samples = (uint64_t)dims[0] * dims[1] * dims[2];
-    if (samples > (1ull << 24)) return fail(HU_ERR_BAD_ARG, "a block may have at most 2^24 samples (256^3)");
-    if (dims[0] > 65535u || dims[1] > 65535u || dims[2] > 65535u) return fail(HU_ERR_BAD_ARG, "block dims must be below 65536");
+    if (samples > (1ull << 24)) return hu_fail(HU_ERR_BAD_ARG, "a block may have at most 2^24 samples (256^3)");
+    if (dims[0] > 65535u || dims[1] > 65535u || dims[2] > 65535u) return hu_fail(HU_ERR_BAD_ARG, "block dims must be below 65536");
     a.A0 = dims[0];
     a.A1 = dims[1];
     a.A2 = dims[2];
@@ -49,7 +37,7 @@ int mesh_shape(uint32_t n_blocks, const uint32_t dims[3], McArgs& a, uint64_t& n
     a.div_spr = make_fast_div(a.spr);
     a.chunks = (a.segments + kMcBlock - 1) / kMcBlock;
     n_wg = (uint64_t)a.chunks * n_blocks;
-    if (n_wg > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "too many workgroups in one launch");
+    if (n_wg > 0x7fffffffull) return hu_fail(HU_ERR_BAD_ARG, "too many workgroups in one launch");
     return HU_OK;
 }
 
@@ -67,7 +55,7 @@ extern "C" {
 int hu_mesh_workgroups(uint32_t n_blocks, const uint32_t dims[3], uint64_t* n_workgroups, uint64_t* count_entries,
                        uint64_t* segments)
 {
-    if (!n_workgroups || !count_entries || !segments) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (!n_workgroups || !count_entries || !segments) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     McArgs a{};
     int rc;
     if ((rc = mesh_shape(n_blocks, dims, a, *n_workgroups))) return rc;
@@ -79,7 +67,7 @@ int hu_mesh_workgroups(uint32_t n_blocks, const uint32_t dims[3], uint64_t* n_wo
 int hu_mesh_count(const float* fields_dev, uint32_t n_blocks, const uint32_t dims[3], uint32_t* masks_dev,
                   uint32_t* wg_counts_dev, void* stream)
 {
-    if (!wg_counts_dev || ((!fields_dev || !masks_dev) && n_blocks)) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (!wg_counts_dev || ((!fields_dev || !masks_dev) && n_blocks)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     McArgs a{};
     uint64_t n_wg;
     int rc;
@@ -110,10 +98,10 @@ int hu_mesh_emit(const float* fields_dev, const int32_t* blocks_dev, uint32_t n_
                  const uint32_t* masks_dev, const uint32_t* wg_counts_dev, uint32_t* seg_info_dev, double* vertices_dev,
                  uint32_t* triangles_dev, void* stream)
 {
-    if (!origin) return fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (!origin) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (n_blocks == 0) return HU_OK;
     if (!fields_dev || !blocks_dev || !masks_dev || !wg_counts_dev || !seg_info_dev || !vertices_dev || !triangles_dev)
-        return fail(HU_ERR_BAD_ARG, "NULL argument");
+        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     McArgs a{};
     uint64_t n_wg;
     int rc;
@@ -145,10 +133,10 @@ int hu_mesh_stl(const double* vertices_dev, const uint32_t* triangles_dev, uint6
                 void* stream)
 {
     if (n_triangles == 0) return HU_OK;
-    if (!vertices_dev || !triangles_dev || !records_dev) return fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(records_dev) & 15u) return fail(HU_ERR_BAD_ARG, "records_dev must be 16-byte aligned");
+    if (!vertices_dev || !triangles_dev || !records_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(records_dev) & 15u) return hu_fail(HU_ERR_BAD_ARG, "records_dev must be 16-byte aligned");
     const uint64_t n_wg = (n_triangles + kStlBlock - 1) / kStlBlock;
-    if (n_wg > 0x7fffffffull) return fail(HU_ERR_BAD_ARG, "too many triangles for one call");
+    if (n_wg > 0x7fffffffull) return hu_fail(HU_ERR_BAD_ARG, "too many triangles for one call");
     hipLaunchKernelGGL(k_stl_records, dim3((uint32_t)n_wg), dim3(kStlBlock), 0, (hipStream_t)stream, vertices_dev,
                        triangles_dev, n_triangles, static_cast<uint8_t*>(records_dev));
     HU_HIP(hipGetLastError());

@@ -4,7 +4,9 @@
 // why): the ray caster and the bitmap renderer over the tape interpreter (reference rendering/ray_caster.cl:146-256,
 // rendering/bitmap.cl:1-18), 2D contouring (rendering/polygon2d.cl:82-175), the reduction of the per-parent moment
 // sums to a level's ten integrals (mass_properties.py:119-148) and the self-test of the arithmetic contract.
-// hip_util.hip validates arguments and calls the launch functions at the end of this file.
+// The entry points of contouring, the reduction and the self-tests are at the end of this file; the tape's ray caster and
+// bitmap are validated in hip_util.hip, which knows the tape, and launched through hu_render::ray_caster / bitmap.
+#include "host.hpp"
 #include "launchers.hpp"
 
 using namespace sdfk;
@@ -180,30 +182,119 @@ hipError_t bitmap(bool distance_only, const sdf::Rec* prog, const float* extra, 
     return hipGetLastError();
 }
 
-hipError_t process_polygon(bool batch, const PolygonArgs& a, dim3 grid, hipStream_t stream)
-{
-    if (batch) hipLaunchKernelGGL(k_process_polygon<true>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(k_process_polygon<false>, grid, dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t mass_integrals(const double4* parents, const uint32_t* sums, uint32_t n_parents, uint32_t per_row, const uint32_t* n_parents_dev,
-                          double s, double* out, uint32_t rows, hipStream_t stream)
-{
-    hipLaunchKernelGGL(k_mass_integrals, dim3(rows), dim3(1024), 0, stream, parents, sums, n_parents, per_row, n_parents_dev, s, out);
-    return hipGetLastError();
-}
-
-hipError_t selftest_math(unsigned long long* counts_dev)
-{
-    hipLaunchKernelGGL(k_selftest_math, dim3(256 * 32), dim3(256), 0, nullptr, counts_dev);
-    return hipGetLastError();
-}
-
-hipError_t selftest_minmax3(unsigned long long* counts_dev)
-{
-    hipLaunchKernelGGL(k_selftest_minmax3, dim3(256 * 8), dim3(256), 0, nullptr, counts_dev);
-    return hipGetLastError();
-}
-
 }  // namespace hu_render
+
+namespace {
+
+int launch_process_polygon(bool batch, PolygonArgs& a, uint32_t n_blocks, void* stream)
+{
+    if (a.gx < 2 || a.gy < 2) return hu_fail(HU_ERR_BAD_ARG, "the corner grid needs at least 2x2 samples");
+    if (a.gx > 512 || a.gy > 512) return hu_fail(HU_ERR_BAD_ARG, "corner grids above 512 overflow the link encoding (polygon2d.py:46)");
+    if (n_blocks == 0) return HU_OK;
+    if (n_blocks > 65535u) return hu_fail(HU_ERR_BAD_ARG, "at most 65535 blocks per launch");
+    const uint32_t cells = (a.gx - 1u) * (a.gy - 1u) * 2u;
+    const dim3 grid((cells + 255u) / 256u, n_blocks);
+    if (batch) hipLaunchKernelGGL(k_process_polygon<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_process_polygon<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    HU_HIP(hipGetLastError());
+    return HU_OK;
+}
+
+// n_parents_dev == NULL: exactly n_parents parents; else at most n_parents, and the slices are cut on the device
+int launch_mass_integrals(const double* parents_dev, const uint32_t* sums_dev, uint32_t n_parents, const uint32_t* n_parents_dev, double s,
+                          double* out_dev, uint32_t rows, void* stream)
+{
+    if (rows == 0 || rows > 65535u) return hu_fail(HU_ERR_BAD_ARG, "rows must be in 1..65535");
+    const uint32_t per_row = n_parents_dev ? 0u : (n_parents + rows - 1) / rows;   // rows past the end get an empty slice and write zeros
+    hipLaunchKernelGGL(k_mass_integrals, dim3(rows), dim3(1024), 0, (hipStream_t)stream, (const double4*)parents_dev, sums_dev, n_parents,
+                       per_row, n_parents_dev, s, out_dev);
+    HU_HIP(hipGetLastError());
+    return HU_OK;
+}
+
+// run `kernel` over N zeroed counters and fetch them
+template <int N>
+int selftest(const char* name, void (*kernel)(unsigned long long*), uint32_t blocks, uint64_t counts[N])
+{
+    if (!counts) return hu_fail(HU_ERR_BAD_ARG, "counts is NULL");
+    unsigned long long* dev = nullptr;
+    HU_HIP(hipMalloc((void**)&dev, N * sizeof(unsigned long long)));
+    hipError_t e = hipMemset(dev, 0, N * sizeof(unsigned long long));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, nullptr, dev);
+        e = hipGetLastError();
+    }
+    unsigned long long host[N] = {};
+    if (e == hipSuccess) e = hipMemcpy(host, dev, sizeof host, hipMemcpyDeviceToHost);
+    (void)hipFree(dev);
+    if (e != hipSuccess) return hu_fail(HU_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
+    for (int i = 0; i < N; ++i) counts[i] = host[i];
+    return HU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hu_process_polygon(const float box_corner[2], float box_step, const void* corners_dev, const uint32_t grid[2],
+                       void* vertices_dev, uint32_t* links_dev, uint32_t* starts_dev, uint32_t* start_counter_dev,
+                       void* stream)
+{
+    if (!box_corner || !corners_dev || !grid || !vertices_dev || !links_dev || !starts_dev || !start_counter_dev)
+        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    PolygonArgs a{};
+    a.corners = static_cast<const float4*>(corners_dev);
+    a.gx = grid[0] + 1u;  // the reference launches over (gx-1, gy-1, 2) triangles
+    a.gy = grid[1] + 1u;
+    a.cx = box_corner[0];
+    a.cy = box_corner[1];
+    a.step = box_step;
+    a.vertices = static_cast<float2*>(vertices_dev);
+    a.links = links_dev;
+    a.starts = starts_dev;
+    a.start_counter = start_counter_dev;
+    return launch_process_polygon(false, a, 1, stream);
+}
+
+int hu_process_polygon_blocks(const void* corners_dev, const int32_t* blocks_dev, uint32_t n_blocks, double resolution,
+                              const double origin[3], float step, const uint32_t dims[2], void* vertices_dev,
+                              uint32_t* links_dev, uint32_t* starts_dev, uint32_t* start_counters_dev, void* stream)
+{
+    if (!origin || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (n_blocks && (!corners_dev || !blocks_dev || !vertices_dev || !links_dev || !starts_dev || !start_counters_dev))
+        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    PolygonArgs a{};
+    a.corners = static_cast<const float4*>(corners_dev);
+    a.gx = dims[0];
+    a.gy = dims[1];
+    a.step = step;
+    a.blocks = reinterpret_cast<const int4*>(blocks_dev);
+    a.res = resolution;
+    a.ox = origin[0];
+    a.oy = origin[1];
+    a.vertices = static_cast<float2*>(vertices_dev);
+    a.links = links_dev;
+    a.starts = starts_dev;
+    a.start_counter = start_counters_dev;
+    return launch_process_polygon(true, a, n_blocks, stream);
+}
+
+int hu_mass_integrals(const double* parents_dev, const uint32_t* sums_dev, uint32_t n_parents, double s,
+                      double* out_dev, uint32_t rows, void* stream)
+{
+    if (!out_dev || ((!parents_dev || !sums_dev) && n_parents)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    return launch_mass_integrals(parents_dev, sums_dev, n_parents, nullptr, s, out_dev, rows, stream);
+}
+
+int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                               double s, double* out_dev, uint32_t rows, void* stream)
+{
+    if (!out_dev || !n_parents_dev || ((!parents_dev || !sums_dev) && max_parents)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    return launch_mass_integrals(parents_dev, sums_dev, max_parents, n_parents_dev, s, out_dev, rows, stream);
+}
+
+int hu_selftest_math(uint64_t counts[4]) { return selftest<4>("hu_selftest_math", k_selftest_math, 256 * 32, counts); }
+
+int hu_selftest_minmax3(uint64_t counts[3]) { return selftest<3>("hu_selftest_minmax3", k_selftest_minmax3, 256 * 8, counts); }
+
+}  // extern "C"

@@ -12,12 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include <cstdint>
-#include <string>
-
-#include "../../include/hip_util.h"
-
-int hu_fail_external(int code, const char* message);   // hip_util.hip: sets the thread's last error
+#include "host.hpp"
 
 namespace {
 
@@ -49,17 +44,17 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 extern "C" int hu_sort_blocks(int32_t* blocks_dev, uint32_t n, void* scratch_dev, size_t scratch_bytes, size_t* needed,
                               void* stream)
 {
-    if (!needed) return hu_fail_external(HU_ERR_BAD_ARG, "needed is NULL");
+    if (!needed) return hu_fail(HU_ERR_BAD_ARG, "needed is NULL");
     hipStream_t s = (hipStream_t)stream;
     size_t sort_bytes = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                              (uint32_t*)nullptr, (uint32_t*)nullptr, n ? n : 1u, 0, 63, s);
-    if (e != hipSuccess) return hu_fail_external(HU_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return hu_fail(HU_ERR_HIP, hipGetErrorString(e));
     // layout: keys in | keys out | index in | index out | sorted rows | flag | rocPRIM's scratch
     const size_t k = align256((size_t)n * 8), v = align256((size_t)n * 4), r = align256((size_t)n * 16);
     *needed = 2 * k + 2 * v + r + 256 + align256(sort_bytes);
     if (!scratch_dev || scratch_bytes < *needed || n < 2) return HU_OK;   // size query (or nothing to do)
-    if (!blocks_dev) return hu_fail_external(HU_ERR_BAD_ARG, "blocks_dev is NULL");
+    if (!blocks_dev) return hu_fail(HU_ERR_BAD_ARG, "blocks_dev is NULL");
     char* p = static_cast<char*>(scratch_dev);
     unsigned long long* keys_in = (unsigned long long*)p;
     unsigned long long* keys_out = (unsigned long long*)(p + k);
@@ -81,7 +76,7 @@ extern "C" int hu_sort_blocks(int32_t* blocks_dev, uint32_t n, void* scratch_dev
     uint32_t bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hu_fail_external(HU_ERR_HIP, hipGetErrorString(e));
-    if (bad) return hu_fail_external(HU_ERR_BAD_ARG, "block corners outside +-2^20 resolution units cannot be packed into sort keys");
+    if (e != hipSuccess) return hu_fail(HU_ERR_HIP, hipGetErrorString(e));
+    if (bad) return hu_fail(HU_ERR_BAD_ARG, "block corners outside +-2^20 resolution units cannot be packed into sort keys");
     return HU_OK;
 }

@@ -2,7 +2,7 @@
 //
 // The analogue of the reference's generate_fixed_eval_source_code (nodes/codegen.py:137-204): the decoded program
 // is unrolled into straight-line code over the SAME op library (interp.hpp) -- one exec_one call per record with the
-// record as a literal and its opcode as a template argument -- and compiled with hipRTC (hip_util.hip).
+// record as a literal and its opcode as a template argument -- and compiled with hipRTC (tape_build.hip).
 //
 // Two forms, same bytes out (tests/test_gpu_variants.py, tests/test_gpu_random_shapes.py):
 //
@@ -1256,7 +1256,7 @@ inline std::string render_prune_function(const Phase1& ph, const PruneInfo& pi)
 }  // namespace spec_detail
 
 // true: the deferred form was emitted; false: nothing was written (use emit_plain)
-// What the host needs to know about the generated code (hip_util.hip SpecKernels).
+// What the host needs to know about the generated code (tape_handle.hpp SpecKernels).
 struct SpecMeta {
     bool deferred = false;
     double coord_limit = 0.0;    // the largest |sample coordinate| for which a launch may set sdf::kFlagInRange (0: never)

@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libhip_util.so")
-SOURCES = ["hip_util.hip", "render.hip", "sort.hip", "exchange.hip", "mesh.hip", "instance_pairs.hip", "instance_rays.hip",
-           "instance_section.hip", "instance_mass.hip"]
+SOURCES = ["hip_util.hip", "tape_build.hip", "render.hip", "sort.hip", "exchange.hip", "mesh.hip", "instance_pairs.hip",
+           "instance_rays.hip", "instance_section.hip", "instance_mass.hip"]
 
 
 def headers():
@@ -29,14 +29,16 @@ HIPCC_FLAGS = [
 ]
 # Which translation unit carries INTERPRETER_FLAGS, and why.  -structurizecfg-skip-uniform-regions is NOT harmless:
 # it once gave a divergent loop with a second, uniform exit its exit-dependent value from a scalar branch
-# (csrc/exchange.hip tells the story).  So it is confined to ONE unit, hip_util.hip, whose kernels are only
+# (csrc/exchange.hip tells the story).  So it is confined to ONE unit, hip_util.hip -- the tape handle and the
+# interpreter's launches --, whose kernels are only
 #   k_grid_eval / k_grid_eval_blocks / k_classify over InterpEval: the interpreter's wave-uniform dispatch loop around
 #   branch-free ops (ops with divergent branches or loops are __noinline__ functions), plus straight-line index
 #   arithmetic, stores and the ballot compaction -- no divergent loop with more than one exit;
 # every other kernel -- ray caster, bitmap, 2D contouring, mass integrals, self-test (render.hip), the exchange step,
 # the sort, marching cubes, the interference and clearance checks (instance_pairs.hip), the ray caster over instances
 # (instance_rays.hip), the section of an assembly (instance_section.hip) and its mass properties (instance_mass.hip) -- is
-# built without it.
+# built without it, each unit with the entry points of its kernels; so is tape_build.hip, the host-only build of a tape's
+# own kernels (hipRTC, the on-disk cache, the precompiled header), which holds no kernel at all.
 # tests/test_hip_util_host.py checks both halves of that from the ISA: which kernels the flagged object holds, and that
 # its loops have the shape described here.
 FLAGGED_SOURCES = ("hip_util.hip",)

@@ -59,7 +59,7 @@ bool distance_only(const hu_tape_s* t)
 }
 
 // Voxels per lane and workgroup size from the register file: the rule of host.hpp hu_workgroup(), and around it the
-// choices only the grid kernels have (voxels per lane, HU_BLOCK, single wavefronts for lanes that share nothing).
+// choices only the grid kernels have (voxels per lane, single wavefronts for lanes that share nothing).
 // Two voxels per lane (packed float2) halve the scalar work per voxel (fetch, decode, compare
 // tree, branch), which is what limits the interpreter once the VALU work is trimmed, but they
 // double the LDS register file.  Measured on MI355X (tools/prof_shape.py):
@@ -94,9 +94,7 @@ int launch_shape(const hu_tape_s* t, LaunchShape& ls, bool distance_only_kernel,
             const size_t groups = kMaxLds / (per_lane * lanes + kScratchBytes), waves = groups * (lanes / 64u);
             return waves < 32 ? waves : (size_t)32;
         };
-        static const uint32_t forced_block = [] { const char* e = getenv("HU_BLOCK"); return e ? (uint32_t)atoi(e) : 0u; }();
-        if (forced_block == 64u || forced_block == 128u || forced_block == 256u) bs = forced_block < bs ? forced_block : bs;
-        else if (lanes_are_independent && bs == 256u && waves_per_cu(64u) > waves_per_cu(256u)) bs = 64u;
+        if (lanes_are_independent && bs == 256u && waves_per_cu(64u) > waves_per_cu(256u)) bs = 64u;
         ls.block = bs;
         ls.regfile_bytes = per_lane * bs;
         ls.lds = ls.regfile_bytes + kScratchBytes;
@@ -227,15 +225,13 @@ uint32_t box_table_bytes(const SpecKernels* k, bool dist)
 }
 
 // Box pruning: run the tape's mask kernel for the `m.n_boxes` workgroups of the launch that follows on `stream` and hand
-// back their masks -- or NULL (nothing to prune in this tape, HU_PRUNE_RUN=0, or a buffer that would have to grow while
+// back their masks -- or NULL (nothing to prune in this tape, or a buffer that would have to grow while
 // the stream is being captured into a graph): the launch then treats everything as alive.
 int prepare_masks(hu_tape_s* t, MaskArgs& m, hipStream_t stream, const uint32_t** masks)
 {
     *masks = nullptr;
     SpecKernels* k = t->spec;
     if (!k || !k->box_masks || k->prune_words <= 0 || m.n_boxes == 0) return HU_OK;
-    static const bool off = [] { const char* e = getenv("HU_PRUNE_RUN"); return e && e[0] == '0'; }();
-    if (off) return HU_OK;
     const size_t bytes = (size_t)m.n_boxes * (size_t)k->prune_words * sizeof(uint32_t);
     SpecKernels::MaskBuffer* buf = nullptr;
     for (auto& b : k->mask_buffers) if (b.stream == stream) buf = &b;
@@ -504,23 +500,21 @@ int hu_grid_eval_slab(hu_tape t, const float corner[4], float step, const uint32
             // along z (2 KiB contiguous per wavefront: sphere, 512^3 float4: 0.34 ms in runs, 0.42 ms in bricks)
             uint32_t boxes = (t->spec->deferred && !spec_runs) ? 1u : 0u;
             const bool ragged = boxes && !brick_tiles(nx, dims[1], dims[2]);
-            // runs of cells (HU_RUN_BLOCK: 64 / 128 / 256 lanes per workgroup, for measurements: the lanes of a run kernel share
-            // nothing, but single-wavefront workgroups were SLOWER on the store-bound tapes -- box, 512^3 float4: 0.409 against
-            // 0.373 ms, its distance grid 0.265 against 0.180 ms)
-            static const uint32_t run_block = [] { const char* e = getenv("HU_RUN_BLOCK"); const int v = e ? atoi(e) : 0; return (v == 64 || v == 128 || v == 256) ? (uint32_t)v : 256u; }();
-            const uint32_t block = boxes ? kSpecBlock : run_block;
+            // (runs of cells take 256 lanes per workgroup too: the lanes of a run kernel share nothing, but single-wavefront
+            // workgroups were SLOWER on the store-bound tapes -- box, 512^3 float4: 0.409 against 0.373 ms, its distance grid
+            // 0.265 against 0.180 ms)
             // A tape of a primitive or two (a box, a sphere: per-tape code in the plain form, over runs) is bound by its
             // store stream, and that stream runs FASTER with fewer wavefronts in flight: box, 512^3 float4: 0.373 ms at eight
             // wavefronts per SIMD (what its 20-odd registers allow), 0.328 ms at four -- the interpreter's rate, whose LDS
-            // register file holds it near there anyway (measured with -DSDF_WAVES_PER_EU: 2 / 4 / 6 / 8 -> 0.382 / 0.328 /
-            // 0.353 / 0.373 ms).  So such a launch asks for 40 KiB of LDS it never touches: four workgroups, sixteen
-            // wavefronts per CU.  (HU_STORE_BOUND_LDS=0: off; longer tapes -- sponge(4): 0.407 -> 0.429 ms at four -- keep all.)
-            static const uint32_t store_bound_kib = [] { const char* e = getenv("HU_STORE_BOUND_LDS"); const int v = e ? atoi(e) : 40; return (uint32_t)((v >= 0 && v <= 64) ? v : 40); }();
+            // register file holds it near there anyway (measured with the register allocator held to 2 / 4 / 6 / 8 waves per
+            // SIMD: 0.382 / 0.328 / 0.353 / 0.373 ms).  So such a launch asks for 40 KiB of LDS it never touches: four
+            // workgroups, sixteen wavefronts per CU.  (Longer tapes -- sponge(4): 0.407 -> 0.429 ms at four -- keep all.)
             // (float4 launches only: the float grid of the same tape stores a quarter of the bytes and is slowed by the limit --
-            // box, 512^3: 0.182 -> 0.206 ms; HU_STORE_BOUND_LDS=<KiB>, 0..64: 32-40 are the best, 53 -- three workgroups per CU,
-            // the best for stores ALONE, tools/experiments/store_patterns.hip -- leaves the arithmetic too few wavefronts: 0.38 ms)
-            const uint32_t idle_lds = (layout == 0 && !boxes && !t->spec->deferred && t->n_instr <= 16) ? store_bound_kib * 1024u : 0u;
-            const uint32_t per_block = block * kSpecVoxelsPerLane;
+            // box, 512^3: 0.182 -> 0.206 ms; of 0..64 KiB, 32-40 are the best, 53 -- three workgroups per CU, the best for
+            // stores ALONE, tools/experiments/store_patterns.hip -- leaves the arithmetic too few wavefronts: 0.38 ms)
+            constexpr uint32_t kStoreBoundLds = 40u * 1024u;
+            const uint32_t idle_lds = (layout == 0 && !boxes && !t->spec->deferred && t->n_instr <= 16) ? kStoreBoundLds : 0u;
+            const uint32_t per_block = kSpecBlock * kSpecVoxelsPerLane;
             uint32_t grid = (n_cells + per_block - 1) / per_block;
             const uint32_t* masks = nullptr;
             if (boxes) {
@@ -532,10 +526,10 @@ int hu_grid_eval_slab(hu_tape t, const float corner[4], float step, const uint32
             }
             if (spec_runs) {
                 void* args[] = {&ev, &cx, &cy, &cz, &step, &sx, &sy, &sz, &xs, &n_cells, &o};
-                HU_HIP(hipModuleLaunchKernel(t->spec->dense_runs[layout], grid, 1, 1, block, 1, 1, 0u, (hipStream_t)stream, args, nullptr));
+                HU_HIP(hipModuleLaunchKernel(t->spec->dense_runs[layout], grid, 1, 1, kSpecBlock, 1, 1, 0u, (hipStream_t)stream, args, nullptr));
             } else {
                 void* args[] = {&ev, &cx, &cy, &cz, &step, &sx, &sy, &sz, &xs, &n_cells, &boxes, &o, &masks};
-                HU_HIP(hipModuleLaunchKernel(ragged ? t->spec->dense_ragged[layout] : t->spec->dense[layout], grid, 1, 1, block, 1, 1,
+                HU_HIP(hipModuleLaunchKernel(ragged ? t->spec->dense_ragged[layout] : t->spec->dense[layout], grid, 1, 1, kSpecBlock, 1, 1,
                                              boxes ? box_table_bytes(t->spec, layout != 0) : idle_lds, (hipStream_t)stream, args, nullptr));
             }
             done += nx;

@@ -41,16 +41,10 @@ __device__ __forceinline__ f2 copysign_(f2 m, f2 s) { return __builtin_elementwi
 __device__ __forceinline__ float rint_(float x) { return __builtin_rintf(x); }
 // |x| - h per voxel: the absolute value rides in the subtraction's source modifier (one instruction per voxel),
 // where the packed form needs a v_and per voxel in front of the packed subtraction
-// (inline asm: written as fabsf(x) - h the compiler re-packs the two voxels and puts the v_and back)
-// SDF_ABS_MINUS_BUILTIN (per-tape code, HU_ABS_BUILTIN=1; an experiment that lost, specialise.hpp): the plain form, which
-// the compiler can hoist out of the loop over a wavefront's bricks where x and y do not change -- an inline asm it will not.
-#if defined(SDF_ABS_MINUS_BUILTIN) && SDF_ABS_MINUS_BUILTIN
-__device__ __forceinline__ float abs_minus(float x, float h) { return __builtin_fabsf(x) - h; }
-__device__ __forceinline__ f2 abs_minus(f2 x, float h) { return __builtin_elementwise_abs(x) - h; }
-#else
+// (inline asm: written as fabsf(x) - h the compiler re-packs the two voxels and puts the v_and back; the plain form, which
+// it can hoist out of the loop over a wavefront's bricks where x and y do not change, was an experiment that lost)
 __device__ __forceinline__ float abs_minus(float x, float h) { float r; asm("v_sub_f32 %0, |%1|, %2" : "=v"(r) : "v"(x), "s"(h)); return r; }
 __device__ __forceinline__ f2 abs_minus(f2 x, float h) { f2 r; r.x = abs_minus(x.x, h); r.y = abs_minus(x.y, h); return r; }
-#endif
 // The hardware's v_min_f32 / v_max_f32 (ISA pseudocode: a NaN operand yields the other one, -0 orders below
 // +0): one full-rate instruction where `a < b ? a : b` is a compare and a select.  The canonical distance of
 // union / intersection / subtraction and of the nearer-slab case; the oracle restates it in
@@ -120,16 +114,8 @@ __device__ __forceinline__ f2 make_f2(float a, float b) { f2 r; r.x = a; r.y = b
 // Does any lane of the wavefront (any voxel of any lane) have the flag set?  Wave-uniform, so a
 // branch on it is a scalar branch: used to skip the sqrt / reciprocal blocks of the
 // perpendicular-intersection ops when no lane is in the corner region that needs them.
-#ifndef SDF_SKIP_CORNER
-#define SDF_SKIP_CORNER 1
-#endif
-#if SDF_SKIP_CORNER
 __device__ __forceinline__ bool any_lane(m1 m) { return m.w != 0ull; }
 __device__ __forceinline__ bool any_lane(m2 m) { return (m.wx | m.wy) != 0ull; }
-#else
-__device__ __forceinline__ bool any_lane(m1) { return true; }
-__device__ __forceinline__ bool any_lane(m2) { return true; }
-#endif
 
 template <class T> struct V4 { T x, y, z, w; };
 template <class T> __device__ __forceinline__ V4<T> v4(T x, T y, T z, T w) { V4<T> r = {x, y, z, w}; return r; }
@@ -179,9 +165,6 @@ template <class T> __device__ __forceinline__ T dot3(T ax, T ay, T az, T bx, T b
 // step from y is wrong for 200 of the 2^32 inputs, and two steps are still wrong for some and no faster.)  Not an approximation argument: tests/test_gpu_math.py runs hu_selftest_math, which compares
 // these functions with the IEEE expansions on ALL 2^32 inputs on the device.  Outside that range
 // (zeros, denormals, infinities, NaN, huge values) a wave-uniform branch takes the IEEE path.
-#ifndef SDF_FAST_CR_MATH
-#define SDF_FAST_CR_MATH 1
-#endif
 // In straight-line (per-tape) code the compiler otherwise speculates the small IEEE sqrt block and pays its
 // 13 VALU instructions per voxel every time (measured: sponge(4) distance-only 1.35 -> 1.02 ms with the
 // branch kept).  Inside the interpreter's dispatch loop the same marker has the opposite effect (3.0 ->
@@ -205,7 +188,6 @@ template <> struct mask_of<f2> { using type = m2; static __device__ __forceinlin
 // sqrt(x), identical to sqrt_(x) in every lane/voxel where `used` holds
 template <class T, class M> __device__ __forceinline__ T sqrt_cr(T x, M used)
 {
-#if SDF_FAST_CR_MATH
     const T y = rsq_hw(x);
     const T s0 = x * y, h = 0.5f * y;
     T s = fma_(fma_(-s0, s0, x), h, s0);
@@ -214,14 +196,10 @@ template <class T, class M> __device__ __forceinline__ T sqrt_cr(T x, M used)
         s = sqrt_(x);
     }
     return s;
-#else
-    return sqrt_(x);
-#endif
 }
 // s = sqrt(x), r = 1.0f / s, identical to the plain operations where `used` holds
 template <class T, class M> __device__ __forceinline__ void sqrt_inv_cr(T x, M used, T& s, T& r)
 {
-#if SDF_FAST_CR_MATH
     const T y = rsq_hw(x);
     const T s0 = x * y, h = 0.5f * y;
     s = fma_(fma_(-s0, s0, x), h, s0);
@@ -232,10 +210,6 @@ template <class T, class M> __device__ __forceinline__ void sqrt_inv_cr(T x, M u
         s = sqrt_(x);
         r = 1.0f / s;
     }
-#else
-    s = sqrt_(x);
-    r = 1.0f / s;
-#endif
 }
 
 template <class T> __device__ __forceinline__ T len2(T x, T y) { return sqrt_cr(fma_(y, y, x * x), mask_of<T>::all()); }
@@ -245,24 +219,6 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
     return fma_(az, bz, fma_(ay, by, ax * bx));
 }
 __device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return fma_(ay, by, ax * bx); }
-
-// reference shapes/common.cl:1-6; k = w*w - dot(v,v) is folded at decode time
-template <class T>
-__device__ __forceinline__ void quat_xform(float qx, float qy, float qz, float qw, float k, T px, T py, T pz,
-                                           T& ox, T& oy, T& oz)
-{
-    const T QX = bc<T>(qx), QY = bc<T>(qy), QZ = bc<T>(qz), QW = bc<T>(qw), K = bc<T>(k);
-    T d = fma_(QZ, pz, fma_(QY, py, QX * px));
-    T cx = fma_(QY, pz, -(QZ * py));
-    T cy = fma_(QZ, px, -(QX * pz));
-    T cz = fma_(QX, py, -(QY * px));
-    T tx = fma_(cx, QW, QX * d);
-    T ty = fma_(cy, QW, QY * d);
-    T tz = fma_(cz, QW, QZ * d);
-    ox = fma_(px, K, tx + tx);
-    oy = fma_(py, K, ty + ty);
-    oz = fma_(pz, K, tz + tz);
-}
 
 // Rotation about a coordinate axis as the 2x2 rotation-and-scale it is (constants A, B, C folded by the
 // decoder, tape.hpp axis_constants): `along` is the coordinate on the axis, (u, v) the other two in cyclic
@@ -382,7 +338,6 @@ template <class R, class T> __device__ __forceinline__ V4<R> widen4(const V4<T>&
 constexpr uint32_t kFlagInRange = 1u;
 template <class T, class M> __device__ __forceinline__ T sqrt_cr(T x, M used, uint32_t flags)
 {
-#if SDF_FAST_CR_MATH
     const T y = rsq_hw(x);
     const T s0 = x * y, h = 0.5f * y;
     T s = fma_(fma_(-s0, s0, x), h, s0);
@@ -394,9 +349,6 @@ template <class T, class M> __device__ __forceinline__ T sqrt_cr(T x, M used, ui
         }
     }
     return s;
-#else
-    return sqrt_(x);
-#endif
 }
 // perp_w for operands of different widths (same operations as perp_w above, in the wider type)
 template <class A, class B> __device__ __forceinline__ wider_t<A, B> perp_w_x(A a, B b, uint32_t flags)
@@ -433,7 +385,6 @@ template <class M, class A, class B> __device__ __forceinline__ auto sel_x(M m, 
 }
 template <class T, class M> __device__ __forceinline__ void sqrt_inv_cr(T x, M used, T& s, T& r, uint32_t flags)
 {
-#if SDF_FAST_CR_MATH
     const T y = rsq_hw(x);
     const T s0 = x * y, h = 0.5f * y;
     s = fma_(fma_(-s0, s0, x), h, s0);
@@ -447,10 +398,6 @@ template <class T, class M> __device__ __forceinline__ void sqrt_inv_cr(T x, M u
             r = 1.0f / s;
         }
     }
-#else
-    s = sqrt_(x);
-    r = 1.0f / s;
-#endif
 }
 // shell (a component of the direction, the distance that entered) and symmetrical_from (x of the direction, x of the point)
 template <class C, class W> __device__ __forceinline__ wider_t<C, W> shell_dir_x(C c, W w)
@@ -888,10 +835,7 @@ __device__ __forceinline__ f2 opaque(f2 x) { asm volatile("" : "+v"(x)); return 
 // of once per tape instruction (SMEM returns out of order, so a wave can only wait for
 // "everything").  The build disables MachineSink (builder.py) so that the loads stay there.
 // ---------------------------------------------------------------------------------------
-#ifndef SDF_FETCH_GROUP
-#define SDF_FETCH_GROUP 4
-#endif
-constexpr int kFetchGroup = SDF_FETCH_GROUP;  // tape.hpp pads the program with kTapePadding _return records
+constexpr int kFetchGroup = 4;  // tape.hpp pads the program with kTapePadding _return records
 
 template <class T, bool DISTANCE_ONLY, class R>
 __device__ __forceinline__ void exec_leaf(const Rec& cur, V4<T>& last, T px, T py, T pz, R& regs);   // below
@@ -915,12 +859,9 @@ __device__ __forceinline__ bool exec_one(const Rec& cur, V4<T>& last, const floa
         if (DISTANCE_ONLY && (fold & kFoldLoadResult)) last.w = regs.load_res(fold & 0xffu);
         else last = regs.load(fold & 0xffu);
     }
-#ifndef SDF_LEAF_FIRST
-#define SDF_LEAF_FIRST 1
-#endif
     // the interpreter's programs are mostly fused leaves (tape.hpp fuse_leaves): one test instead of the walk down
     // the compare tree
-    if (SDF_LEAF_FIRST && !kStaticOp && op == OPX_LEAF) {
+    if (!kStaticOp && op == OPX_LEAF) {
         exec_leaf<T, DISTANCE_ONLY, R>(cur, last, px, py, pz, regs);
     } else
     switch (op) {
@@ -966,20 +907,6 @@ __device__ __forceinline__ bool exec_one(const Rec& cur, V4<T>& last, const floa
         last = per_voxel(last, none, [=](float4 l, float4) { return twist_revolution_to_op(a, b, l); });
         break;
     }
-#if !SDF_TO_SPECIAL || defined(SDF_EXP_KEEP_QUAT)   // (tape_format.hpp: the decoder leaves none of these)
-    case OP_INITIAL_TRANSFORMATION_TO: {
-        T ox, oy, oz;
-        quat_xform<T>(p[0], p[1], p[2], p[3], p[7], px, py, pz, ox, oy, oz);
-        last = v4<T>(ox + p[4], oy + p[5], oz + p[6], bc<T>(0.0f));
-        break;
-    }
-    case OP_TRANSFORMATION_TO: {
-        T ox, oy, oz;
-        quat_xform<T>(p[0], p[1], p[2], p[3], p[7], last.x, last.y, last.z, ox, oy, oz);
-        last = v4<T>(ox + p[4], oy + p[5], oz + p[6], bc<T>(0.0f));
-        break;
-    }
-#endif
     case OPX_POINT: last = v4<T>(px, py, pz, bc<T>(0.0f)); break;
     // a general quaternion as its matrix (tape_format.hpp): x' is parked in w, then y', z' and the assembly
     case OPX_TO_ROW_X:
@@ -1013,18 +940,6 @@ __device__ __forceinline__ bool exec_one(const Rec& cur, V4<T>& last, const floa
         last = v4<T>(x, y, z, bc<T>(0.0f));
         break;
     }
-#if !SDF_FROM_SPECIAL || defined(SDF_EXP_KEEP_QUAT)
-    case OP_TRANSFORMATION_FROM: {
-        if (DISTANCE_ONLY) {
-            last.w = last.w * p[5];
-            break;
-        }
-        T ox, oy, oz;
-        quat_xform<T>(p[0], p[1], p[2], p[3], p[4], last.x, last.y, last.z, ox, oy, oz);
-        last = v4<T>(ox * p[6], oy * p[6], oz * p[6], last.w * p[5]);
-        break;
-    }
-#endif
     case OPX_INIT_ROW_X:
         last.w = fma_(px, bc<T>(p[0]), fma_(py, bc<T>(p[1]), fma_(pz, bc<T>(p[2]), bc<T>(p[3]))));
         break;
@@ -1192,11 +1107,7 @@ __device__ __forceinline__ void exec_leaf(const Rec& cur, V4<T>& last, T px, T p
         if (DISTANCE_ONLY) r.w = perp_w<T>(abs_minus(q.z, p[kLeafExtrude]), r.w);
         else r = extrusion_op(p[kLeafExtrude], r, q);
     }
-#if SDF_LEAF_FROM_LAST
-    const uint32_t from = (c & kLeafFromLast) ? 0u : ((c >> kLeafFromShift) & 7u);
-#else
     const uint32_t from = (c >> kLeafFromShift) & 7u;
-#endif
     if (from != 0u) {
         const float* f = p + kLeafFrom;
         if (DISTANCE_ONLY) {
@@ -1234,12 +1145,6 @@ __device__ __forceinline__ void exec_leaf(const Rec& cur, V4<T>& last, T px, T p
             else r = neg(rounded_union(-1.0f, neg(r), b));
         }
     }
-#if SDF_LEAF_FROM_LAST
-    if (c & kLeafFromLast) {   // a scaling applied to the combined value (OPX_FROM_SCALE after the selects)
-        if (DISTANCE_ONLY) r.w = r.w * p[kLeafScale];
-        else r = v4<T>(r.x * p[kLeafFrom], r.y * p[kLeafFrom], r.z * p[kLeafFrom], r.w * p[kLeafScale]);
-    }
-#endif
     last = r;
 }
 

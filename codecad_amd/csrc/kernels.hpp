@@ -15,13 +15,6 @@
 
 #include "interp.hpp"
 
-// Occupancy hint for experiments (-DSDF_WAVES_PER_EU=n): waves per SIMD the register allocator aims for.
-#ifdef SDF_WAVES_PER_EU
-#define SDF_KERNEL_ATTRS __attribute__((amdgpu_waves_per_eu(SDF_WAVES_PER_EU, SDF_WAVES_PER_EU)))
-#else
-#define SDF_KERNEL_ATTRS
-#endif
-
 namespace sdfk {
 
 using sdf::Rec;
@@ -70,30 +63,8 @@ __device__ __forceinline__ uint32_t div(uint32_t x, Dim d)
     return d.n == 1u ? x : q;  // kernel-uniform select
 }
 
-// Grid stores.  Non-temporal stores (-DSDF_NT_STORES=1) were measured and are OFF: a 512^3 float4 grid of a
-// store-bound tape takes 1.03 ms with `global_store_dwordx4 ... nt` (2.1 TB/s) against 0.40 ms with plain stores.
-#ifndef SDF_NT_STORES
-#define SDF_NT_STORES 0
-#endif
-typedef float f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_voxel(float4* p, float4 v)
-{
-#if SDF_NT_STORES
-    f4v t;
-    t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-    __builtin_nontemporal_store(t, reinterpret_cast<f4v*>(p));
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ void store_voxel(float* p, float v)
-{
-#if SDF_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+// Grid stores are plain stores.  Non-temporal ones were measured and lost: a 512^3 float4 grid of a store-bound tape
+// takes 1.03 ms with `global_store_dwordx4 ... nt` (2.1 TB/s) against 0.40 ms with plain stores.
 
 // N = voxels per lane (1: T = float, 2: T = packed float2, see interp.hpp)
 template <int N> struct Pack { using T = float; };
@@ -358,13 +329,13 @@ __device__ __forceinline__ void box_eval(const E& ev, float4* lds, float cx, flo
 #pragma unroll
                 for (int i = 0; i < N; ++i)
                     if (!RAGGED || (row_inside && j * 4u + xl + 2u * (uint32_t)i < nx))
-                        store_voxel(static_cast<float4*>(o.out) + p + (size_t)i * second, sdf::voxel(r, i));
+                        *(static_cast<float4*>(o.out) + p + (size_t)i * second) = sdf::voxel(r, i);
             } else {
                 const T w = ev.dist_hoisted_x(px, pyb, pzb, hoisted, tb, prb);
 #pragma unroll
                 for (int i = 0; i < N; ++i)
                     if (!RAGGED || (row_inside && j * 4u + xl + 2u * (uint32_t)i < nx))
-                        store_voxel(static_cast<float*>(o.out) + p + (size_t)i * second, sdf::get(w, i));
+                        *(static_cast<float*>(o.out) + p + (size_t)i * second) = sdf::get(w, i);
             }
             tb.x += 4; tb.xy += 4; tb.xz += 4;
             p += brick;
@@ -402,21 +373,16 @@ __device__ __forceinline__ void grid_eval_boxes(const E& ev, float4* lds, float 
     // the output (a box's row is 16 floats): both L2s hold half-written lines.  So every XCD takes a CONTIGUOUS eighth of
     // the boxes, its workgroups walking it in order: neighbours meet in one L2.  Measured, 512^3, per-tape code over boxes
     // (profiles/r04_hbm_sweep.jsonl): float grids 0.16-0.18 -> 0.12-0.14 ms (csg_example 0.177 -> 0.116, sponge(4) 0.171 ->
-    // 0.138), float4 grids of light tapes -2...-4 % (whole lines either way), sponge(4)'s unchanged.  -DSDF_BOX_ORDER=0: off.
-    uint32_t b = blockIdx.x;
-#if !defined(SDF_BOX_ORDER) || SDF_BOX_ORDER
-    {
-        const uint32_t k = b & 7u, q = gridDim.x >> 3, r = gridDim.x & 7u;     // XCD k takes q + (k < r) boxes
-        b = k * q + (k < r ? k : r) + (b >> 3);
-    }
-#endif
+    // 0.138), float4 grids of light tapes -2...-4 % (whole lines either way), sponge(4)'s unchanged.
+    const uint32_t k = blockIdx.x & 7u, q = gridDim.x >> 3, r = gridDim.x & 7u;     // XCD k takes q + (k < r) boxes
+    const uint32_t b = k * q + (k < r ? k : r) + (blockIdx.x >> 3);
     const uint32_t qz = b % boxes_z, qt = b / boxes_z, qy = qt % boxes_y, qx = qt / boxes_y;
     const BoxOut o{out, 0, sx, sy, sz, LAYOUT == 0 ? 0u : x0, nx_slab};
     box_eval<E, LAYOUT, N, RAGGED>(ev, lds, cx, cy, cz, step, x0, qx * 16u, qy * 16u, qz * 16u, o, masks, b);
 }
 
 template <class E, int LAYOUT, int N>
-__global__ void __launch_bounds__(256) SDF_KERNEL_ATTRS
+__global__ void __launch_bounds__(256)
 k_grid_eval(const E ev, float cx, float cy, float cz, float step, uint32_t sx, Dim dy, Dim dz, uint32_t x0,
             uint32_t n_cells, uint32_t boxes, void* __restrict__ out, const uint32_t* __restrict__ masks)
 {
@@ -431,7 +397,7 @@ k_grid_eval(const E ev, float cx, float cy, float cz, float step, uint32_t sx, D
 // the same over boxes that may end anywhere (box_eval RAGGED): a kernel of its own, because its predicated stores and its
 // longer live ranges are not for the aligned launches to pay
 template <class E, int LAYOUT, int N>
-__global__ void __launch_bounds__(256) SDF_KERNEL_ATTRS
+__global__ void __launch_bounds__(256)
 k_grid_eval_ragged(const E ev, float cx, float cy, float cz, float step, uint32_t sx, Dim dy, Dim dz, uint32_t x0,
                    uint32_t n_cells, uint32_t boxes, void* __restrict__ out, const uint32_t* __restrict__ masks)
 {
@@ -443,7 +409,7 @@ k_grid_eval_ragged(const E ev, float cx, float cy, float cz, float step, uint32_
 // (a 2D grid is one voxel deep: seven of a brick's eight z lanes idle -- 2048^2 float4: 0.081 ms over ragged boxes, slower
 // than interpreted; the launchers take this kernel where less than half of the padded bricks' voxels exist)
 template <class E, int LAYOUT, int N>
-__global__ void __launch_bounds__(256) SDF_KERNEL_ATTRS
+__global__ void __launch_bounds__(256)
 k_grid_eval_runs(const E ev, float cx, float cy, float cz, float step, uint32_t sx, Dim dy, Dim dz, uint32_t x0,
                  uint32_t n_cells, void* __restrict__ out)
 {
@@ -467,7 +433,7 @@ __device__ __forceinline__ void grid_eval_runs(const E& ev, float4* lds, float c
             if (!c.active[i]) continue;
             // INDEX3 = z + sz*(y + sy*x) (cl_util/indexing.h:4): inside a slab this is the linear
             // cell index; each store instruction of a wavefront writes 1 KiB contiguous.
-            store_voxel(static_cast<float4*>(out) + lin0 + (uint32_t)i * kLaneStride, sdf::voxel(r, i));
+            *(static_cast<float4*>(out) + lin0 + (uint32_t)i * kLaneStride) = sdf::voxel(r, i);
         }
     } else {
         const T w = ev.dist(px, py, pz, lds);
@@ -476,7 +442,7 @@ __device__ __forceinline__ void grid_eval_runs(const E& ev, float4* lds, float c
             if (!c.active[i]) continue;
             // grid_eval.cl:18: z + (x + (sy-1-y)*sx)*sz; z-fastest so a wave stores contiguous runs
             const size_t idx = (size_t)c.z[i] + ((size_t)(x0 + c.x[i]) + (size_t)(sy - 1u - c.y[i]) * sx) * sz;
-            store_voxel(static_cast<float*>(out) + idx, sdf::get(w, i));
+            *(static_cast<float*>(out) + idx) = sdf::get(w, i);
         }
     }
 }
@@ -516,18 +482,18 @@ __device__ __forceinline__ void grid_eval_blocks_body(const E& ev, float4* lds, 
         const sdf::V4<T> r = ev(px, py, pz, lds);
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            if (c.active[i]) store_voxel(static_cast<float4*>(out) + base + lin0 + (uint32_t)i * kLaneStride, sdf::voxel(r, i));
+            if (c.active[i]) *(static_cast<float4*>(out) + base + lin0 + (uint32_t)i * kLaneStride) = sdf::voxel(r, i);
     } else {
         const T w = ev.dist(px, py, pz, lds);
 #pragma unroll
         for (int i = 0; i < N; ++i)
             if (c.active[i])
-                store_voxel(static_cast<float*>(out) + base + (size_t)c.z[i] + ((size_t)c.x[i] + (size_t)(sy - 1u - c.y[i]) * sx) * sz, sdf::get(w, i));
+                *(static_cast<float*>(out) + base + (size_t)c.z[i] + ((size_t)c.x[i] + (size_t)(sy - 1u - c.y[i]) * sx) * sz) = sdf::get(w, i);
     }
 }
 // (two kernels for evaluators with box code, like k_grid_eval / k_grid_eval_ragged)
 template <class E, int LAYOUT, int N>
-__global__ void __launch_bounds__(256) SDF_KERNEL_ATTRS
+__global__ void __launch_bounds__(256)
 k_grid_eval_blocks(const E ev, const int4* __restrict__ blocks, const uint32_t* __restrict__ n_blocks_dev, uint32_t b0,
                    uint32_t chunks, uint32_t bricks, double res, double ox, double oy, double oz, float step, uint32_t sx,
                    Dim dy, Dim dz, void* __restrict__ out, const uint32_t* __restrict__ masks)
@@ -536,7 +502,7 @@ k_grid_eval_blocks(const E ev, const int4* __restrict__ blocks, const uint32_t* 
     grid_eval_blocks_body<E, LAYOUT, N, (E::kBricks && N == 2)>(ev, lds, blocks, n_blocks_dev, b0, chunks, bricks, res, ox, oy, oz, step, sx, dy, dz, out, masks);
 }
 template <class E, int LAYOUT, int N>
-__global__ void __launch_bounds__(256) SDF_KERNEL_ATTRS
+__global__ void __launch_bounds__(256)
 k_grid_eval_blocks_ragged(const E ev, const int4* __restrict__ blocks, const uint32_t* __restrict__ n_blocks_dev, uint32_t b0,
                           uint32_t chunks, uint32_t bricks, double res, double ox, double oy, double oz, float step, uint32_t sx,
                           Dim dy, Dim dz, void* __restrict__ out, const uint32_t* __restrict__ masks)
@@ -548,7 +514,7 @@ k_grid_eval_blocks_ragged(const E ev, const int4* __restrict__ blocks, const uin
 
 // (... and over runs of cells, for blocks in which boxes would be mostly padding: k_grid_eval_runs)
 template <class E, int LAYOUT, int N>
-__global__ void __launch_bounds__(256) SDF_KERNEL_ATTRS
+__global__ void __launch_bounds__(256)
 k_grid_eval_blocks_runs(const E ev, const int4* __restrict__ blocks, const uint32_t* __restrict__ n_blocks_dev, uint32_t b0,
                         uint32_t chunks, double res, double ox, double oy, double oz, float step, uint32_t sx, Dim dy, Dim dz,
                         void* __restrict__ out)

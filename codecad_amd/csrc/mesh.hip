@@ -44,8 +44,7 @@ int mesh_shape(uint32_t n_blocks, const uint32_t dims[3], McArgs& a, uint64_t& n
 // a block of at most 256 rows of at most 32 samples: one workgroup owns it (mesh_kernels.hpp k_mc_block_*)
 bool mesh_block_form(const McArgs& a)
 {
-    static const bool off = [] { const char* e = getenv("HU_MC_BLOCK_FORM"); return e && e[0] == '0'; }();
-    return !off && a.chunks == 1u && a.spr == 1u && (uint64_t)(a.A0 - 1u) * (a.A1 - 1u) * (a.A2 - 1u) <= kMcBlockCells;
+    return a.chunks == 1u && a.spr == 1u && (uint64_t)(a.A0 - 1u) * (a.A1 - 1u) * (a.A2 - 1u) <= kMcBlockCells;
 }
 
 }  // namespace

@@ -55,7 +55,7 @@ inline std::string rec_literal(const Rec& r, bool clear_fold, uint32_t hdr)
     char buf[32];
     std::snprintf(buf, sizeof buf, "0x%08xu", hdr);
     o << "Rec{" << buf << ", {";
-    for (int i = 0; i < SDF_REC_DWORDS - 1; ++i) {
+    for (int i = 0; i < kRecDwords - 1; ++i) {
         uint32_t bits;
         std::memcpy(&bits, &r.p[i], 4);
         if (clear_fold && i == kFoldParam) bits = 0;
@@ -836,10 +836,8 @@ inline PruneInfo analyse_pruning(const Phase1& ph, int min_cost)
     // its primitives are table reads, three vector instructions each, and the scalar tests cost more than what they skip
     // (measured: the bench's leaf blocks 0.137 -> 0.187 ms, C5 6.5 -> 8.5 ms with the sponge's 24 scopes guarded in its
     // distance walks, 0.41 -> 0.66 ms for its float4 grid guarded throughout).  Bounds behind a repetition serve assemblies
-    // that contain one (a bolt circle), not fractals.  HU_PRUNE_COND_SHARE: the share of conditional leaves from which on a
-    // tape gets no scopes (percent, default 50).
-    static const int cond_share = [] { const char* e = std::getenv("HU_PRUNE_COND_SHARE"); return e && *e ? std::atoi(e) : 50; }();
-    if (leaves > 0 && conditional * 100 > leaves * cond_share) {
+    // that contain one (a bolt circle), not fractals.  From half of the leaves conditional on, a tape gets no scopes.
+    if (leaves > 0 && conditional * 2 > leaves) {
         PruneInfo none;
         none.scope_of.assign(st.size(), 0);
         none.sel.assign(st.size(), PruneInfo::Sel());
@@ -1075,11 +1073,10 @@ inline Variant render_variant(const Phase1& ph, const std::vector<char>& hoistab
     // min(min(a, b), c) -> min3(a, b, c) (and max) where this body is the inner result's only reader -- the distances of a
     // union of several shapes when no comparison of the direction phase looks at the partial minimum (interp.hpp min3_)
     std::vector<int> readers(n, 0), fused_inner(n, -1);
-    static const bool fuse = [] { const char* e = std::getenv("HU_MINMAX3"); return !(e && e[0] == '0'); }();
     for (int i = 0; i < n; ++i) if (in_main[i]) for (int o : st[i].ops) ++readers[o];
     for (int r : roots) if (r >= 0) ++readers[r];
     std::vector<char> dead(n, 0);
-    for (int i = 0; fuse && i < n; ++i) {
+    for (int i = 0; i < n; ++i) {
         if (!in_main[i] || st[i].ops.size() != 2) continue;
         if (st[i].text != "min_x($0, $1)" && st[i].text != "max_x($0, $1)") continue;
         const int j = st[i].ops[0];
@@ -1275,6 +1272,9 @@ constexpr size_t kInPlaceDeferredPaths = 40;
 constexpr int kMaxTableColumns = 48;   // per axis (a column of a 16^3 box is 64 B of LDS)
 constexpr int kMaxPairColumns = 16;    // per pair of axes (a column of a 16^3 box is 1 KiB) ...
 constexpr int kMaxPairTotal = 24;      // ... and in all: the tables of a box stay below 28 KiB, five workgroups to a CU
+constexpr int kPruneMinCost = 6;       // what an operand must cost, in instructions, to be worth a scalar branch (box pruning)
+constexpr int kPruneAllScopes = 64;    // the number of box-pruning scopes from which a tape counts as an assembly
+constexpr int kRecomputeLimit = 40;    // up to this cost a direction block computes a kept distance again (emit_deferred)
 
 inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t max_paths = 400, SpecMeta* meta = nullptr)
 {
@@ -1300,26 +1300,17 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     if (!symbolic_phase1(p, nodes, root, is_choice, keep_w, ph, &pt)) return false;
     if (meta) meta->coord_limit = coordinate_limit(ph);
     ph.n_phase1 = (int)ph.e.st.size();
-    // box pruning: which operands of which selects can be decided per box (HU_PRUNE=0: none; HU_PRUNE_MIN: what an operand
-    // must cost, in instructions, to be worth a scalar branch)
-    static const int prune_min = [] {
-        const char* off = std::getenv("HU_PRUNE");
-        if (off && off[0] == '0') return 0;
-        const char* e = std::getenv("HU_PRUNE_MIN");
-        return e && *e ? std::atoi(e) : 6;
-    }();
-    PruneInfo prune = analyse_pruning(ph, prune_min);
+    // box pruning: which operands of which selects can be decided per box (HU_PRUNE=0: none)
+    static const bool prune_off = [] { const char* e = std::getenv("HU_PRUNE"); return e && e[0] == '0'; }();
+    PruneInfo prune = analyse_pruning(ph, prune_off ? 0 : kPruneMinCost);
     // Where the guards go.  An assembly (many scopes: planetary 131) gets them everywhere: walks of both kinds, `pre`, the pair
     // tables' builders.  A tape with a few (the sponge: 24, all behind repetitions) gets them in the DISTANCE walks only -- leaf
     // blocks, classification, distance grids, where the vector ALU is the bound --: its float4 code, which sits on the store
-    // roof, stays exactly as it was (and its launches skip the mask kernel).  HU_PRUNE_EVAL_MIN: the number of scopes from
-    // which a tape counts as an assembly.
-    static const int prune_eval_min = [] { const char* e = std::getenv("HU_PRUNE_EVAL_MIN"); return e && *e ? std::atoi(e) : 64; }();
-    const bool prune_all = prune.n_bits >= prune_eval_min;
+    // roof, stays exactly as it was (and its launches skip the mask kernel).
+    const bool prune_all = prune.n_bits >= kPruneAllScopes;
     if (meta) { meta->prune_bits = prune.n_bits; meta->prune_words = prune.words(); meta->prune_all = prune_all; }
-    // the distance walks over boxes read the tape's chains folded per plane (fold_chains; HU_FOLD=0: as they are)
-    static const bool fold = [] { const char* e = std::getenv("HU_FOLD"); return !(e && e[0] == '0'); }();
-    const int folded_root = fold ? fold_chains(ph, prune, ph.root) : ph.root;
+    // the distance walks over boxes read the tape's chains folded per plane (fold_chains)
+    const int folded_root = fold_chains(ph, prune, ph.root);
     ph.n_phase1 = (int)ph.e.st.size();
     // (the folded statements are unguarded and in no scope: fold_chains folds nothing box pruning decides)
     prune.scope_of.resize(ph.e.st.size(), 0);
@@ -1339,8 +1330,7 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     // (reusing phase 1's registers across the whole second phase would cost more than recomputing: interp.hpp opaque).
     Emitter& e = ph.e;
     const int zero = e.add("0.0f", {});
-    struct PathCode { std::string mask; int d[3]; };
-    std::vector<PathCode> codes;
+    std::vector<std::array<int, 3>> codes;   // per path: the three components of its direction
     {
         auto full_record = [&](const Rec& r, const int (&last)[4], const int (&operand)[4]) {
             const uint32_t op = r.hdr & 0xffu;
@@ -1349,10 +1339,6 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
         };
         auto mulc = [&](int v, float c) { return e.add("$0 * " + flit(c), {v}); };
         for (const Path& path : paths) {
-            PathCode code;
-            for (size_t k = 0; k < path.choices.size(); ++k)
-                code.mask += std::string(k ? " & " : "") + (path.choices[k].second ? "" : "~") + "as_mask(@" + std::to_string(ph.choice_of_rec[path.choices[k].first]) + "@, T())";
-            if (path.choices.empty()) code.mask = "mask_of<T>::all()";
             const Node& leaf = nodes[path.leaf];
             const Rec& lr = p.full[leaf.rec];
             const std::array<int, 3>& c = pt[leaf.a];
@@ -1427,8 +1413,7 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
                 }
                 }
             }
-            code.d[0] = d[0]; code.d[1] = d[1]; code.d[2] = d[2];
-            codes.push_back(code);
+            codes.push_back({{d[0], d[1], d[2]}});
         }
     }
     // phase 1's values that phase 2 reads where they are (not computed again): the comparisons, the kept distances
@@ -1440,7 +1425,6 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     for (int v : ph.choice_of_rec) if (v >= 0) lives[v] = 1;
     for (int v : ph.keep_w_of_rec) if (v >= 0) kept_w[v] = 1;
     const std::vector<int> p1_cost = statement_costs(ph);
-    static const int recompute_limit = [] { const char* e = std::getenv("HU_KEEP_RECOMPUTE"); return e && *e ? std::atoi(e) : 40; }();
     // `tabc` / `tab_index` / `tab_used`: the axis tables (render_variant): a block reads a table column where it would
     // have recomputed the statement; `tab_used` (may be NULL) collects which candidates the blocks read
     auto phase2_for = [&](const std::vector<char>& hoistable, const std::vector<char>& tabc, const std::vector<int>* tab_index,
@@ -1459,7 +1443,7 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
         };
         std::vector<char> live_here = lives;
         for (int i = 0; i < (int)kept_w.size(); ++i)
-            if (kept_w[i] && !handed(i) && !tabled(i) && !(p1_cost[i] <= recompute_limit && again(i))) live_here[i] = 1;
+            if (kept_w[i] && !handed(i) && !tabled(i) && !(p1_cost[i] <= kRecomputeLimit && again(i))) live_here[i] = 1;
         std::ostringstream o2;
         o2 << "    // ---- phase 2\n"
            << "    const auto qx = opaque(px); const auto qy = opaque(py); const auto qz = opaque(pz);\n";
@@ -1469,10 +1453,10 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
         // the body of path k's block (`m` = its lanes): the closure of the direction's statements, up to values that live
         // outside it, then three selects per voxel
         auto block_body = [&](size_t k, const std::string& pad) {
-            const PathCode& code = codes[k];
+            const std::array<int, 3>& d = codes[k];
             std::ostringstream ob;
             std::vector<char> inside(st.size(), 0), loads(st.size(), 0);
-            std::vector<int> stack{code.d[0], code.d[1], code.d[2]};
+            std::vector<int> stack{d[0], d[1], d[2]};
             while (!stack.empty()) {
                 const int i = stack.back();
                 stack.pop_back();
@@ -1489,49 +1473,34 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
                 if (loads[i]) ob << pad << "const auto u" << i << " = " << table_load(st[i], tab_index ? (*tab_index)[i] : 0) << ";\n";
                 else if (inside[i]) ob << pad << "const auto u" << i << " = " << render(st[i], name) << ";\n";
             }
-            ob << pad << "dir.x = sel(m, as<T>(" << name(code.d[0]) << "), dir.x); dir.y = sel(m, as<T>(" << name(code.d[1])
-               << "), dir.y); dir.z = sel(m, as<T>(" << name(code.d[2]) << "), dir.z);\n";
+            ob << pad << "dir.x = sel(m, as<T>(" << name(d[0]) << "), dir.x); dir.y = sel(m, as<T>(" << name(d[1])
+               << "), dir.y); dir.z = sel(m, as<T>(" << name(d[2]) << "), dir.z);\n";
             return ob.str();
         };
-        static const bool tree = [] { const char* e = std::getenv("HU_PHASE2_TREE"); return !(e && e[0] == '0'); }();
-        if (tree) {
-            // The blocks hang in the tree of the selects: a select splits its lanes between its operands (one scalar
-            // and / and-not per voxel of the lane), and an operand nobody chose is left with everything below it -- where
-            // the flat form formed every path's product of choices and tested it, 13 paths of up to six factors for
-            // sponge(4) (150 scalar instructions per brick against 95 vector ones).  collect_paths met the leaves in
-            // this order.
-            size_t next = 0;
-            std::function<void(int, const std::string&, int)> walk = [&](int at, const std::string& lanes, int depth) {
-                const Node& n = nodes[at];
-                const std::string pad(4 + 4 * (size_t)depth, ' ');
-                if (n.role == LEAF) {
-                    o2 << pad << "{   // the primitive of record " << n.rec << "\n" << pad << "    const M m = " << (lanes.empty() ? "mask_of<T>::all()" : lanes) << ";\n"
-                       << block_body(next++, pad + "    ") << pad << "}\n";
-                } else if (n.role == SELECT) {
-                    const std::string c = "as_mask(" + outer(ph.choice_of_rec[n.rec]) + ", T())", id = std::to_string(n.rec);
-                    const std::string ma = "m" + id + "a", mb = "m" + id + "b";
-                    o2 << pad << "const M " << ma << " = " << (lanes.empty() ? "" : lanes + " & ") << c << ", " << mb << " = " << (lanes.empty() ? "" : lanes + " & ") << "~" << c << ";\n"
-                       << pad << "if (wave_any(" << ma << ")) {\n";
-                    walk(n.a, ma, depth + 1);
-                    o2 << pad << "}\n" << pad << "if (wave_any(" << mb << ")) {\n";
-                    walk(n.b, mb, depth + 1);
-                    o2 << pad << "}\n";
-                } else walk(n.a, lanes, depth);
-            };
-            walk(root, "", 0);
-        } else
-        for (size_t k = 0; k < paths.size(); ++k) {
-            const PathCode& code = codes[k];
-            std::string mask;
-            for (size_t i = 0; i < code.mask.size(); ++i) {
-                if (code.mask[i] != '@') { mask += code.mask[i]; continue; }
-                const size_t end = code.mask.find('@', i + 1);
-                mask += outer(std::atoi(code.mask.substr(i + 1, end - i - 1).c_str()));
-                i = end;
-            }
-            o2 << "    {   // the primitive of record " << nodes[paths[k].leaf].rec << " along one path to the root\n        const M m = " << mask
-               << ";\n        if (wave_any(m)) {\n" << block_body(k, "            ") << "        }\n    }\n";
-        }
+        // The blocks hang in the tree of the selects: a select splits its lanes between its operands (one scalar
+        // and / and-not per voxel of the lane), and an operand nobody chose is left with everything below it -- where
+        // a flat list formed every path's product of choices and tested it, 13 paths of up to six factors for
+        // sponge(4) (150 scalar instructions per brick against 95 vector ones).  collect_paths met the leaves in
+        // this order.
+        size_t next = 0;
+        std::function<void(int, const std::string&, int)> walk = [&](int at, const std::string& lanes, int depth) {
+            const Node& n = nodes[at];
+            const std::string pad(4 + 4 * (size_t)depth, ' ');
+            if (n.role == LEAF) {
+                o2 << pad << "{   // the primitive of record " << n.rec << "\n" << pad << "    const M m = " << (lanes.empty() ? "mask_of<T>::all()" : lanes) << ";\n"
+                   << block_body(next++, pad + "    ") << pad << "}\n";
+            } else if (n.role == SELECT) {
+                const std::string c = "as_mask(" + outer(ph.choice_of_rec[n.rec]) + ", T())", id = std::to_string(n.rec);
+                const std::string ma = "m" + id + "a", mb = "m" + id + "b";
+                o2 << pad << "const M " << ma << " = " << (lanes.empty() ? "" : lanes + " & ") << c << ", " << mb << " = " << (lanes.empty() ? "" : lanes + " & ") << "~" << c << ";\n"
+                   << pad << "if (wave_any(" << ma << ")) {\n";
+                walk(n.a, ma, depth + 1);
+                o2 << pad << "}\n" << pad << "if (wave_any(" << mb << ")) {\n";
+                walk(n.b, mb, depth + 1);
+                o2 << pad << "}\n";
+            } else walk(n.a, lanes, depth);
+        };
+        walk(root, "", 0);
         return o2.str();
     };
 
@@ -1676,7 +1645,7 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
 }
 
 // The whole translation unit handed to hipRTC.  `meta` (may be NULL) <- what the host needs to know about it.
-inline std::string specialised_source(const SpecProgram& p, bool allow_deferred, SpecMeta* meta = nullptr)
+inline std::string specialised_source(const SpecProgram& p, SpecMeta* meta = nullptr)
 {
     std::ostringstream o, d;
     SpecMeta m;
@@ -1684,7 +1653,7 @@ inline std::string specialised_source(const SpecProgram& p, bool allow_deferred,
     // compiler cannot hoist from and kept distances read again from the tables, planetary's 80 pairs run its float4 grid
     // in 1.0 ms where the plain form takes 4.7)
     static const size_t max_paths = [] { const char* e = std::getenv("HU_MAX_PATHS"); return e && *e ? (size_t)std::atoi(e) : (size_t)400; }();
-    const bool ok = allow_deferred && emit_deferred(d, p, max_paths, &m);
+    const bool ok = emit_deferred(d, p, max_paths, &m);
     if (!ok) m = SpecMeta();
     m.deferred = ok;
     if (meta) *meta = m;

@@ -187,10 +187,6 @@ inline float q_scale(const float* q) { return fma_(q[3], q[3], fma_(q[2], q[2], 
 // kFold*).  Order of effects is unchanged: the load happens first, the store last.
 inline void fold_moves(std::vector<Rec>& prog)
 {
-#ifndef SDF_FOLD_MOVES
-#define SDF_FOLD_MOVES 1
-#endif
-    if (!SDF_FOLD_MOVES) return;
     auto fold_of = [](Rec& r) -> uint32_t& { return reinterpret_cast<uint32_t&>(r.p[kFoldParam]); };
     std::vector<Rec> out;
     out.reserve(prog.size());
@@ -234,9 +230,6 @@ inline void fold_moves(std::vector<Rec>& prog)
 // store only on the last; the store of the transformed point that an extrusion reads back is kept, or dropped when
 // nothing else reads it), selects must be plain (r < 0).  Per-tape code is generated from the unfused records.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef SDF_FUSE_LEAVES
-#define SDF_FUSE_LEAVES 1
-#endif
 namespace fuse_detail {
 inline uint32_t& fold_word(Rec& r) { return reinterpret_cast<uint32_t&>(r.p[kFoldParam]); }
 inline uint32_t fold_word(const Rec& r) { uint32_t f; std::memcpy(&f, &r.p[kFoldParam], 4); return f; }
@@ -274,7 +267,6 @@ inline void fuse_leaves(const std::vector<Rec>& prog, bool typed, std::vector<Re
 {
     using namespace fuse_detail;
     out.clear();
-    if (!SDF_FUSE_LEAVES || SDF_REC_DWORDS < 16) { out = prog; return; }
     const size_t n = prog.size();
     size_t i = 0;
     while (i < n) {
@@ -368,17 +360,6 @@ inline void fuse_leaves(const std::vector<Rec>& prog, bool typed, std::vector<Re
             ++j;
             ++parts;
         }
-        // [from: a scaling of the combined value] -- `to prim select select from_scale`, the tail of a repeated cross
-        if (SDF_LEAF_FROM_LAST && ok && !closed && j < n && !(control & (7u << kLeafFromShift)) && (control & (3u << kLeafComb1Shift)) &&
-            op_of(prog[j]) == OPX_FROM_SCALE && !(fold_word(prog[j]) & kFoldLoad)) {
-            const Rec& r = prog[j];
-            control |= (1u << kLeafFromShift) | kLeafFromLast;
-            leaf.p[kLeafFrom + 0] = r.p[0]; leaf.p[kLeafFrom + 1] = r.p[1]; leaf.p[kLeafFrom + 2] = r.p[2];
-            leaf.p[kLeafScale] = r.p[5];
-            if (fold_word(r) & kFoldStore) { fold |= fold_word(r) & (kFoldStore | kFoldStoreResult | 0xff0000u); closed = true; }
-            ++j;
-            ++parts;
-        }
         // The folded store of the transformed point: dropped when nothing reads the slot afterwards (the fused
         // extrusion has the point in registers), which includes the leaf's own final store overwriting it.
         if (ok && have_mid_store) {
@@ -444,8 +425,7 @@ inline std::string decode_tape(const float* tape, size_t n, DecodedTape& out)
                 for (int i = 4; i < 7; ++i) r.p[i] = p[i] + 0.0f;
                 const bool zx = p[0] == 0.0f, zy = p[1] == 0.0f, zz = p[2] == 0.0f;
                 uint32_t special = op;
-                if (!SDF_TO_SPECIAL) special = op;
-                else if (zx && zy && zz) special = OPX_TO_SCALE;
+                if (zx && zy && zz) special = OPX_TO_SCALE;
                 else if (zy && zz) special = OPX_TO_AXIS_X;
                 else if (zx && zz) special = OPX_TO_AXIS_Y;
                 else if (zx && zy) special = OPX_TO_AXIS_Z;
@@ -459,7 +439,7 @@ inline std::string decode_tape(const float* tape, size_t n, DecodedTape& out)
                     r.hdr = special | (reg << 8);
                     const float q = special == OPX_TO_AXIS_X ? p[0] : special == OPX_TO_AXIS_Y ? p[1] : special == OPX_TO_AXIS_Z ? p[2] : 0.0f;
                     axis_constants(q, p[3], 1.0, r.p[0], r.p[1], r.p[2]);   // p[0..2] = A, B, C (p[3], p[7] unused)
-                } else if (SDF_TO_SPECIAL) {
+                } else {
                     // general quaternion: two records (tape_format.hpp OPX_TO_ROW_X / OPX_TO_ROWS_YZ)
                     float m[9];
                     matrix_constants(p, 1.0, m);
@@ -484,8 +464,7 @@ inline std::string decode_tape(const float* tape, size_t n, DecodedTape& out)
                 r.p[6] = 1.0f / scale;
                 const bool zx = p[0] == 0.0f, zy = p[1] == 0.0f, zz = p[2] == 0.0f;
                 uint32_t special = op;
-                if (!SDF_FROM_SPECIAL) special = op;
-                else if (zx && zy && zz) special = OPX_FROM_SCALE;
+                if (zx && zy && zz) special = OPX_FROM_SCALE;
                 else if (zy && zz) special = OPX_FROM_AXIS_X;
                 else if (zx && zz) special = OPX_FROM_AXIS_Y;
                 else if (zx && zy) special = OPX_FROM_AXIS_Z;
@@ -493,7 +472,7 @@ inline std::string decode_tape(const float* tape, size_t n, DecodedTape& out)
                 if (special != op) {
                     const float q = special == OPX_FROM_AXIS_X ? p[0] : special == OPX_FROM_AXIS_Y ? p[1] : special == OPX_FROM_AXIS_Z ? p[2] : 0.0f;
                     axis_constants(q, p[3], (double)scale, r.p[0], r.p[1], r.p[2]);   // p[0..2] = A, B, C over |Q|^2; p[5] = scale
-                } else if (SDF_FROM_SPECIAL) {
+                } else {
                     float m[9];
                     matrix_constants(p, (double)scale, m);
                     std::memset(&r, 0, sizeof(r));

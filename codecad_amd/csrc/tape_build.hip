@@ -32,16 +32,9 @@ using sdf::Rec;
 
 namespace {
 
-// HU_DEFER_DIRECTIONS=0 keeps the plain straight-line form of every tape (measurements, bisecting)
-bool defer_directions()
-{
-    static const bool off = [] { const char* e = getenv("HU_DEFER_DIRECTIONS"); return e && e[0] == '0'; }();
-    return !off;
-}
-
 std::string generate_source(const hu_tape_s* t, sdf::SpecMeta* meta = nullptr)
 {
-    return sdf::specialised_source(t->program, defer_directions(), meta);
+    return sdf::specialised_source(t->program, meta);
 }
 
 // ---- specialised code objects: hipRTC build + optional on-disk cache ------------------------
@@ -620,13 +613,12 @@ int hu_tape_listing(const float* tape, size_t n, int which, char* buf, size_t ca
             std::memcpy(&c, &r.p[sdf::kLeafControl], 4);
             o << "(" << ((c & sdf::kLeafSample) ? "sample " : "") << "to:" << kinds[(c >> sdf::kLeafToShift) & 7u]
               << ((c & sdf::kLeafMidStore) ? " store-point:" + std::to_string(slot) : std::string()) << " "
-              << prims[(c >> sdf::kLeafPrimShift) & 3u] << ((c & sdf::kLeafExtrusion) ? " extrusion" : "");
-            if (!(c & sdf::kLeafFromLast)) o << " from:" << kinds[(c >> sdf::kLeafFromShift) & 7u];
+              << prims[(c >> sdf::kLeafPrimShift) & 3u] << ((c & sdf::kLeafExtrusion) ? " extrusion" : "")
+              << " from:" << kinds[(c >> sdf::kLeafFromShift) & 7u];
             for (int k = 0; k < 2; ++k) {
                 const uint32_t cb = c >> (k == 0 ? sdf::kLeafComb1Shift : sdf::kLeafComb2Shift);
                 if (cb & 3u) o << " " << combs[cb & 3u] << ":" << ((cb >> 2) & 0xffu);
             }
-            if (c & sdf::kLeafFromLast) o << " then-from:scale";
             o << ")";
         } else if (sdf::rec_arity(op) == 2 || op == sdf::OP_STORE || op == sdf::OP_LOAD) {
             o << " " << slot << ((r.hdr & sdf::kResultKind) ? "r" : "");

@@ -57,26 +57,16 @@ constexpr uint32_t kLeafToShift = 1, kLeafPrimShift = 4, kLeafFromShift = 8;   /
 constexpr uint32_t kLeafExtrusion = 1u << 7;
 constexpr uint32_t kLeafComb1Shift = 11, kLeafComb2Shift = 21;   // 2 bits kind (1 union, 2 intersection, 3 subtraction) + 8 bits slot
 constexpr uint32_t kLeafMidStore = 1u << 31;         // the transformed point is also stored, to the slot in hdr
-// OFF: measured on one box, the same day: with the block that applies the late scaling compiled into the leaf the
-// interpreter runs sponge(4) in 3.45 ms (905 vector + 750 scalar instructions per wavefront, 22 records), without it
-// in 3.31 ms (863 + 654, 26 records) -- the four dispatches saved cost less than what the extra block does to the
-// leaf's code.  -DSDF_LEAF_FROM_LAST=1 brings it back.
-#ifndef SDF_LEAF_FROM_LAST
-#define SDF_LEAF_FROM_LAST 0
-#endif
-constexpr uint32_t kLeafFromLast = 1u << 6;          // the from-part (a scaling) runs AFTER the selects: to prim select select from
+// (A from-part that is a scaling is NOT fused after the selects: measured on one box, the same day, with the block that
+// applies the late scaling compiled into the leaf the interpreter runs sponge(4) in 3.45 ms (905 vector + 750 scalar
+// instructions per wavefront, 22 records), without it in 3.31 ms (863 + 654, 26 records) -- the four dispatches saved
+// cost less than what the extra block does to the leaf's code.)
 enum LeafPrim : uint32_t { LEAF_RECTANGLE = 0, LEAF_CIRCLE = 1, LEAF_SPHERE = 2, LEAF_HALF_SPACE = 3 };
 
 
 
 // The decoder rewrites every transformation_to / transformation_from into a reduced or a matrix form (tape.hpp), so the
-// quaternion forms of the tape never reach a kernel: their cases are compiled only when the rewriting is switched off.
-#ifndef SDF_TO_SPECIAL
-#define SDF_TO_SPECIAL 1
-#endif
-#ifndef SDF_FROM_SPECIAL
-#define SDF_FROM_SPECIAL 1
-#endif
+// quaternion forms of the tape never reach a kernel and no kernel has a case for them.
 
 constexpr int kRefRegisterCount = 512;  // reference nodes/__init__.py:6
 constexpr int kVariableParams = -1;
@@ -94,14 +84,12 @@ constexpr uint32_t kResultKind = 0x80000000u;  // distance-only program: the slo
 constexpr int kFoldParam = 10;   // p[10]: no op uses it (records have 11 parameter dwords)
 constexpr uint32_t kFoldLoad = 0x100u, kFoldLoadResult = 0x200u;          // bits 0-7: slot
 constexpr uint32_t kFoldStore = 0x1000000u, kFoldStoreResult = 0x2000000u;  // bits 16-23: slot
-#ifndef SDF_REC_DWORDS
-#define SDF_REC_DWORDS 16     // 64-byte records: one s_load_dwordx16 each, and room for a fused leaf (OPX_LEAF)
-#endif
-struct alignas(SDF_REC_DWORDS == 16 ? 64 : 16) Rec {
+constexpr int kRecDwords = 16;   // 64-byte records: one s_load_dwordx16 each, and room for a fused leaf (OPX_LEAF)
+struct alignas(4 * kRecDwords) Rec {
     uint32_t hdr;
-    float p[SDF_REC_DWORDS - 1];
+    float p[kRecDwords - 1];
 };
-static_assert(sizeof(Rec) == 4 * SDF_REC_DWORDS, "unexpected Rec size");
+static_assert(sizeof(Rec) == 4 * kRecDwords, "unexpected Rec size");
 
 
 }  // namespace sdf

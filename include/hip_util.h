@@ -446,8 +446,8 @@ int hu_tape_specialized(hu_tape t, int* out_flag);
 /* Box pruning of the tape's per-tape code (no counterpart in the reference, whose kernels evaluate every primitive for
  * every sample): *bits <- the operands of min / max that can be decided per 16^3 box of a launch (0: nothing in this tape
  * can be bounded, or it is interpreted), *words <- 32-bit words of a box's mask.  Launches over boxes run the tape's mask
- * kernel first, on their stream; HU_PRUNE=0 in the environment builds tapes without it, HU_PRUNE_RUN=0 skips the mask
- * kernel (every operand is then taken as alive).  Results are bit-identical either way. */
+ * kernel first, on their stream; HU_PRUNE=0 in the environment builds tapes without it.  Results are bit-identical either
+ * way. */
 int hu_tape_prune_info(hu_tape t, int* bits, int* words);
 /* A precompiled header for the per-tape builds (host only): hipRTC's runtime header + the op library of `include_dir`,
  * made in `dir` by the clang++ that sits next to the hipRTC in use, if there is one; the builds then skip parsing those

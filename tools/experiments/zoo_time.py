@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Run on the GPU box: dense 256^3 grids (float4 and float) of every 3D golden tape with per-tape code; run once as it is
-and once with HU_BRICKS=0 (runs of cells along z: no boxes, no tables) to see what the boxes do to each tape."""
+"""Run on the GPU box: dense 256^3 grids (float4 and float) of every 3D golden tape with per-tape code."""
 import json
 import os
 import sys

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Time the specialised dense kernels of sponge(4) at 512^3 under several HU_RTC_FLAGS settings."""
+"""Time the specialised dense kernels of sponge(4) at 512^3 under several HU_RTC_FLAGS settings: each argument is one
+setting (real compiler options: the headers have no -D switches); without arguments, the default build alone."""
 import os
 import subprocess
 import sys
@@ -26,7 +27,7 @@ for pym in (False, True):
 print("float4 %%.3f ms   float %%.3f ms" %% tuple(res))
 ''' % ROOT
 
-variants = [a for a in sys.argv[1:]] or ["", "-DSDF_FAST_CR_MATH=0", "-DSDF_WAVES_PER_EU=3", "-DSDF_WAVES_PER_EU=4"]
+variants = sys.argv[1:] or [""]
 for depth in (4,):
     for v in variants:
         env = dict(os.environ, HU_RTC_FLAGS=v)

@@ -10,7 +10,8 @@ Public layout mirrors the reference package (reference codecad/__init__.py:1-11)
 `interference(asm, resolution)` finds the overlapping instances of an assembly on the device, and
 `clearance(asm, resolution, min_gap)` the pairs closer than a gap, with how close and where (clearance.py);
 `section(asm, plane, resolution)` cuts an assembly with a `Plane`: which part owns each sample of the cut, where parts
-overlap on it, and the cut area of every part and pair (section.py);
+overlap on it, and the cut area of every part and pair (section.py); `section_outlines(asm, plane, resolution)` gives the
+same cut as vectors: closed outlines per part on the plane (section_outlines.py);
 `assembly_mass_properties(asm, resolution, densities)` weighs an assembly: volume, mass, centre of gravity and inertia of
 every part and of the whole, overlaps counted once (assembly_mass.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
@@ -30,9 +31,10 @@ from .assemblies import assembly  # noqa: F401
 from .interference import interference, InterferenceReport  # noqa: F401
 from .clearance import clearance, ClearanceReport, NearMiss  # noqa: F401
 from .section import section, Section, Plane  # noqa: F401
+from .section_outlines import section_outlines, Outlines, Loop  # noqa: F401
 from .assembly_mass import assembly_mass_properties, AssemblyMassReport, PartMass  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
-           "ClearanceReport", "NearMiss", "section", "Section", "Plane", "assembly_mass_properties",
+           "ClearanceReport", "NearMiss", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "assembly_mass_properties",
            "AssemblyMassReport", "PartMass"]

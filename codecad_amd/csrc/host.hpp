@@ -30,6 +30,7 @@ namespace hu_cells {
 hipError_t allow_big_lds(size_t bytes);                                   // instance_pairs.hip
 hipError_t allow_big_lds_rays(size_t bytes);                              // instance_rays.hip
 hipError_t allow_big_lds_section(size_t bytes);                           // instance_section.hip
+hipError_t allow_big_lds_outline(size_t bytes);                           // instance_outline.hip
 hipError_t allow_big_lds_mass(size_t bytes);                              // instance_mass.hip
 }  // namespace hu_cells
 

@@ -101,4 +101,16 @@ struct SectionArgs {
     int32_t* nearest;                //   WITH_DISTANCE: the lowest instance that attains it
 };
 
+// the outlines of an assembly's section (instance_outline.hip): what its kernels take beside Args.  There Args describes the
+// lattice of SQUARES between the section's samples and a ring around them: dims = {samples along u + 1, along v + 1, 1},
+// corner = the 3D position of the section's sample (0, 0) -- the shifted index (1, 1) --, a row is a TILE {a0 | b0 << 16,
+// unused, mask lo, mask hi} of 8^k x 8^k squares, windows (n x 6, the third index 0) the squares an instance may cross, thr the
+// radius of a child tile, and pairs n_instances + 1 uint64: the number of segments, then the number per instance.
+struct OutlineArgs {
+    Args c;
+    float u[3], v[3];                // the plane's unit vectors, as SectionArgs'
+    uint4* segments;                 // leaf: records {a | b << 16, k | e_from << 8 | e_to << 16, t_from, t_to}
+    uint32_t segment_capacity;       //   records at or past it are counted and not stored
+};
+
 }  // namespace hu_cells

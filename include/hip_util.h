@@ -283,6 +283,37 @@ int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only, uint32
                     int32_t* part_ids_dev, uint8_t* inside_count_dev, float* distance_dev, int32_t* nearest_dev,
                     void* acc_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- the outlines of an assembly's section (codecad_amd/section_outlines.py) -------------------
+ * The section's lattice with a ring of samples around it: samples carry the shifted index s = (i + 1, j + 1), 0 .. dims[0]
+ * by 0 .. dims[1], and sit at the section's formula for (i, j) = s - 1 (corner: the position of the section's sample
+ * (0, 0)).  dims counts the SQUARES between them, per axis one more than the section's samples and at most 65536; square
+ * (a, b) has the corner samples (a, b), (a + 1, b), (a, b + 1), (a + 1, b + 1) and the edges 0 bottom, 1 right, 2 top,
+ * 3 left.  A list is the section's, rows {a0 | b0 << 16, unused, mask lo, mask hi}: square tiles of squares.  windows_dev:
+ * n x 6 uint32 {lo a, lo b, 0, hi a, hi b, 0}, the squares an instance may cross, inclusive.  step finite and not
+ * negative, the frame finite.
+ * hu_outline_tiles: a tile of side 8 * child_side per parent row; each of its 8 x 8 children keeps a candidate k whose
+ *   window reaches it and whose distance w at the child's centre (shifted index a + child_side / 2 per axis) is neither
+ *   >= radius nor <= -radius, and is appended to children_dev when any remain.  child_side a power of two in 8..8192,
+ *   radius not negative.
+ * hu_outline_leaf: a tile of 8 x 8 squares per parent row.  Every candidate k is evaluated at the tile's 9 x 9 samples;
+ *   inside is w < 0.  An edge from sample p to q (lower index first) with exactly one of them inside is crossed at
+ *   t = w_p / (w_p - w_q) in correctly rounded float32, 0.5 where that is no number.  Each square appends 0-2 records of
+ *   16 bytes {a | b << 16, k | e_from << 8 | e_to << 16, float t_from, float t_to} to segments_dev, in no particular order:
+ *   a segment from edge to edge with the inside on its left (u to the right, v up); diagonal inside corners give two, each
+ *   round one inside corner.  totals_dev: n + 1 uint64, the number of records and the number per instance, added to;
+ *   records at or past segment_capacity are counted and not stored (segments_dev may be NULL for a capacity of 0).
+ * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform (samples and children
+ * past the lattice's rim not counted) to *evaluations_dev. */
+int hu_outline_tiles(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                     const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
+                     const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], float step,
+                     float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity, uint64_t* evaluations_dev,
+                     void* stream);
+int hu_outline_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
+                    const float corner[3], const float u[3], const float v[3], float step, void* segments_dev,
+                    uint32_t segment_capacity, uint64_t* totals_dev, uint64_t* evaluations_dev, void* stream);
+
 /* ---- the mass properties of an assembly (codecad_amd/assembly_mass.py) -------------------------
  * The lattice, the instance table and the [header row | rows...] lists of the interference entry points, with rows (and a
  * header) of 32 bytes: {x0 | y0 << 16, z0, cand lo, cand hi, full lo, full hi, 0, 0} -- the candidates of the cell and, a

@@ -13,7 +13,8 @@ Public layout mirrors the reference package (reference codecad/__init__.py:1-11)
 overlap on it, and the cut area of every part and pair (section.py); `section_outlines(asm, plane, resolution)` gives the
 same cut as vectors: closed outlines per part on the plane (section_outlines.py);
 `assembly_mass_properties(asm, resolution, densities)` weighs an assembly: volume, mass, centre of gravity and inertia of
-every part and of the whole, overlaps counted once (assembly_mass.py).
+every part and of the whole, overlaps counted once (assembly_mass.py); `assembly_meshes(asm, resolution)` gives the surface of
+every part as placed, one triangle mesh each on one lattice (assembly_meshes.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -33,8 +34,9 @@ from .clearance import clearance, ClearanceReport, NearMiss  # noqa: F401
 from .section import section, Section, Plane  # noqa: F401
 from .section_outlines import section_outlines, Outlines, Loop  # noqa: F401
 from .assembly_mass import assembly_mass_properties, AssemblyMassReport, PartMass  # noqa: F401
+from .assembly_meshes import assembly_meshes, Meshes, TRIANGLE  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
            "ClearanceReport", "NearMiss", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "assembly_mass_properties",
-           "AssemblyMassReport", "PartMass"]
+           "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE"]

@@ -113,4 +113,16 @@ struct OutlineArgs {
     uint32_t segment_capacity;       //   records at or past it are counted and not stored
 };
 
+// the surface meshes of an assembly's parts (instance_mesh.hip): what its kernels take beside Args.  There Args describes the
+// lattice of CUBES between the samples of interference() and a ring around them: dims = samples + 1 per axis, corner = the
+// position of the sample (0, 0, 0) -- the shifted index (1, 1, 1) --, a row is a CELL {a0 | b0 << 16, c0, mask lo, mask hi} of
+// 4^k cubes a side, windows (n x 6) the cubes an instance may cross, thr the radius of a child cell, and pairs n_instances + 1
+// uint64: the number of triangles, then the number per instance.
+struct MeshArgs {
+    Args c;
+    uint4* triangles;                // leaf: records of two uint4 {a | b << 16, c | k << 16 | which << 24, case | e0 << 8 | e1 << 16 |
+                                     //   e2 << 24, 0} {t0, t1, t2, 0}
+    uint32_t triangle_capacity;      //   records at or past it are counted and not stored
+};
+
 }  // namespace hu_cells

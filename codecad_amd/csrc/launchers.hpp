@@ -18,6 +18,7 @@
 //   instance_section.hip  the planar section of an assembly (codecad_amd/section.py), likewise;
 //   instance_outline.hip  the vector outlines of that section (codecad_amd/section_outlines.py), likewise;
 //   instance_mass.hip   the mass properties of an assembly (codecad_amd/assembly_mass.py), likewise;
+//   instance_mesh.hip   the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py), likewise;
 //   sort.hip, exchange.hip, mesh.hip  the sort of a block list, the exchange step of the multi-GPU levels, marching cubes.
 #pragma once
 

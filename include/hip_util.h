@@ -338,6 +338,37 @@ int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only, 
                           const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
                           float step, void* acc_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
+ * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
+ * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of
+ * interference()).  dims counts the CUBES between them, per axis one more than the samples and at most 65536; cube (a, b, c)
+ * has its corner m at the shifted index (a, b, c) + CORNERS[m] and the edges EDGES[e] of tools/gen_mc_table.py.  A list is
+ * the cell list of the interference entry points, rows {a0 | b0 << 16, c0, mask lo, mask hi}: cubic cells of cubes.
+ * windows_dev: n x 6 uint32 {lo a, b, c, hi a, b, c}, the cubes an instance may cross, inclusive.  step finite and not negative.
+ * hu_mesh_cells: a cell of side 4 * child_side per parent row; each of its 4^3 children keeps a candidate k whose window
+ *   reaches it and whose distance w at the child's centre (shifted index a + child_side / 2 per axis) is neither >= radius
+ *   nor <= -radius, and is appended to children_dev when any remain.  child_side a power of two in 4..16384, radius not
+ *   negative.
+ * hu_mesh_leaf_instances: a cell of 4^3 cubes per parent row.  Every candidate k is evaluated at the cell's 5^3 samples;
+ *   inside is w < 0; bit m of a cube's case is set when its corner m is inside.  An edge with exactly one end inside is
+ *   crossed at t = w_p / (w_p - w_q) in correctly rounded float32, p the end with the lower lattice index, 0.5 where that is
+ *   no number.  Each cube appends the triangles of its case (csrc/mc_table.hpp, in the table's order and winding) to
+ *   triangles_dev as records of 32 bytes {a | b << 16, c | k << 16 | which << 24, case | e0 << 8 | e1 << 16 | e2 << 24, 0,
+ *   float t0, t1, t2, 0}, in no particular order; `which` is the triangle's number within its case.  totals_dev: n + 1
+ *   uint64, the number of records and the number per instance, added to; records at or past triangle_capacity are counted
+ *   and not stored (triangles_dev may be NULL for a capacity of 0).
+ * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform (samples and children
+ * past the lattice's rim not counted) to *evaluations_dev. */
+int hu_mesh_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
+                  const uint32_t dims[3], const float corner[3], float step, float radius, uint32_t* counter_dev,
+                  void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream);
+int hu_mesh_leaf_instances(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
+                           const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
+                           uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+                           void* triangles_dev, uint32_t triangle_capacity, uint64_t* totals_dev, uint64_t* evaluations_dev,
+                           void* stream);
+
 /* ---- renderers on the same evaluate() -------------------- */
 /* rendering/ray_caster.cl:146-159, launched by rendering/ray_caster.py:93-110 with global size
  * (width, height).  origin/forward/up/right: float4 as the reference passes them (forward already

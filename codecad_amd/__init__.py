@@ -11,7 +11,9 @@ Public layout mirrors the reference package (reference codecad/__init__.py:1-11)
 `clearance(asm, resolution, min_gap)` the pairs closer than a gap, with how close and where (clearance.py);
 `section(asm, plane, resolution)` cuts an assembly with a `Plane`: which part owns each sample of the cut, where parts
 overlap on it, and the cut area of every part and pair (section.py); `section_outlines(asm, plane, resolution)` gives the
-same cut as vectors: closed outlines per part on the plane (section_outlines.py);
+same cut as vectors: closed outlines per part on the plane (section_outlines.py), and
+`layer_outlines(asm, plane, resolution, heights)` those outlines on a stack of parallel planes -- the layers of a print -- in
+one traversal of the device, `layer_heights(asm, plane, layer_height)` the heights of such a stack (layer_outlines.py);
 `assembly_mass_properties(asm, resolution, densities)` weighs an assembly: volume, mass, centre of gravity and inertia of
 every part and of the whole, overlaps counted once (assembly_mass.py); `assembly_meshes(asm, resolution)` gives the surface of
 every part as placed, one triangle mesh each on one lattice (assembly_meshes.py).
@@ -33,10 +35,12 @@ from .interference import interference, InterferenceReport  # noqa: F401
 from .clearance import clearance, ClearanceReport, NearMiss  # noqa: F401
 from .section import section, Section, Plane  # noqa: F401
 from .section_outlines import section_outlines, Outlines, Loop  # noqa: F401
+from .layer_outlines import layer_outlines, layer_heights, Layers, LAYER_SEGMENT  # noqa: F401
 from .assembly_mass import assembly_mass_properties, AssemblyMassReport, PartMass  # noqa: F401
 from .assembly_meshes import assembly_meshes, Meshes, TRIANGLE  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
-           "ClearanceReport", "NearMiss", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "assembly_mass_properties",
+           "ClearanceReport", "NearMiss", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "layer_outlines",
+           "layer_heights", "Layers", "LAYER_SEGMENT", "assembly_mass_properties",
            "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE"]

@@ -156,6 +156,7 @@ int hu_ensure_attrs()
     HU_HIP(hu_cells::allow_big_lds_rays(kMaxLds));     // (instance_rays.hip)
     HU_HIP(hu_cells::allow_big_lds_section(kMaxLds));  // (instance_section.hip)
     HU_HIP(hu_cells::allow_big_lds_outline(kMaxLds));  // (instance_outline.hip)
+    HU_HIP(hu_cells::allow_big_lds_layers(kMaxLds));   // (instance_layers.hip)
     HU_HIP(hu_cells::allow_big_lds_mass(kMaxLds));     // (instance_mass.hip)
     HU_HIP(hu_cells::allow_big_lds_mesh(kMaxLds));     // (instance_mesh.hip)
     done_for_device = dev;

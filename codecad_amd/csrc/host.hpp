@@ -31,7 +31,8 @@ hipError_t allow_big_lds(size_t bytes);                                   // ins
 hipError_t allow_big_lds_rays(size_t bytes);                              // instance_rays.hip
 hipError_t allow_big_lds_section(size_t bytes);                           // instance_section.hip
 hipError_t allow_big_lds_outline(size_t bytes);                           // instance_outline.hip
-hipError_t allow_big_lds_mass(size_t bytes);                              // instance_mass.hip
+hipError_t allow_big_lds_layers(size_t bytes);                            // instance_layers.hip
+hipError_t allow_big_lds_mass(size_t bytes);                             // instance_mass.hip
 hipError_t allow_big_lds_mesh(size_t bytes);                              // instance_mesh.hip
 }  // namespace hu_cells
 

@@ -113,6 +113,19 @@ struct OutlineArgs {
     uint32_t segment_capacity;       //   records at or past it are counted and not stored
 };
 
+// the layered outlines of an assembly (instance_layers.hip): OutlineArgs for a stack of parallel planes in one traversal.  Args
+// is the lattice of squares of OutlineArgs, shared by every layer, but word 1 of a row is the row's LAYER: a row is a TILE
+// {a0 | b0 << 16, layer, mask lo, mask hi}, and the 3D position of the section's sample (0, 0) on that layer is
+// layer_corners[layer]; c.corner is not read by the kernels.  pairs: n_instances + 1 uint64 over all layers.
+struct LayerArgs {
+    Args c;
+    float u[3], v[3];                // the planes' unit vectors, as SectionArgs'
+    const float4* layer_corners;     // n_layers x {x, y, z, unused}
+    uint32_t n_layers;               // a row whose layer is not below it is treated as absent
+    uint4* segments;                 // leaf: records {a | b << 16, k | e_from << 8 | e_to << 10 | layer << 12, t_from, t_to}
+    uint32_t segment_capacity;       //   records at or past it are counted and not stored
+};
+
 // the surface meshes of an assembly's parts (instance_mesh.hip): what its kernels take beside Args.  There Args describes the
 // lattice of CUBES between the samples of interference() and a ring around them: dims = samples + 1 per axis, corner = the
 // position of the sample (0, 0, 0) -- the shifted index (1, 1, 1) --, a row is a CELL {a0 | b0 << 16, c0, mask lo, mask hi} of

@@ -68,6 +68,8 @@ PROTOTYPES = {
     "hu_section_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f4, _f4, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "hu_outline_tiles": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f4, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
     "hu_outline_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f4, _f4, _f, _vp, _u32, _vp, _vp, _vp],
+    "hu_layer_tiles": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f4, _f4, _vp, _u32, _f, _f, _vp, _vp, _u32, _vp, _vp],
+    "hu_layer_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f4, _f4, _vp, _u32, _f, _vp, _u32, _vp, _vp, _vp],
     "hu_mesh_cells": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
     "hu_mesh_leaf_instances": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _vp, _u32, _vp, _vp, _vp],
     "hu_assembly_mass_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _i, _vp, _vp, _vp],

@@ -12,7 +12,8 @@ CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libhip_util.so")
 SOURCES = ["hip_util.hip", "tape_build.hip", "render.hip", "sort.hip", "exchange.hip", "mesh.hip", "instance_pairs.hip",
-           "instance_rays.hip", "instance_section.hip", "instance_outline.hip", "instance_mass.hip", "instance_mesh.hip"]
+           "instance_rays.hip", "instance_section.hip", "instance_outline.hip", "instance_layers.hip", "instance_mass.hip",
+           "instance_mesh.hip"]
 
 
 def headers():
@@ -36,8 +37,8 @@ HIPCC_FLAGS = [
 #   arithmetic, stores and the ballot compaction -- no divergent loop with more than one exit;
 # every other kernel -- ray caster, bitmap, 2D contouring, mass integrals, self-test (render.hip), the exchange step,
 # the sort, marching cubes, the interference and clearance checks (instance_pairs.hip), the ray caster over instances
-# (instance_rays.hip), the section of an assembly (instance_section.hip), its outlines (instance_outline.hip), its mass
-# properties (instance_mass.hip) and the meshes of its parts (instance_mesh.hip) -- is
+# (instance_rays.hip), the section of an assembly (instance_section.hip), its outlines (instance_outline.hip) and their layers
+# (instance_layers.hip), its mass properties (instance_mass.hip) and the meshes of its parts (instance_mesh.hip) -- is
 # built without it, each unit with the entry points of its kernels; so is tape_build.hip, the host-only build of a tape's
 # own kernels (hipRTC, the on-disk cache, the precompiled header), which holds no kernel at all.
 # tests/test_hip_util_host.py checks both halves of that from the ISA: which kernels the flagged object holds, and that

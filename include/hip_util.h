@@ -314,6 +314,27 @@ int hu_outline_leaf(const void* table_dev, uint32_t n, int distance_only, uint32
                     const float corner[3], const float u[3], const float v[3], float step, void* segments_dev,
                     uint32_t segment_capacity, uint64_t* totals_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- the layered outlines of an assembly (codecad_amd/layer_outlines.py) -----------------------
+ * The outlines above on a stack of n_layers parallel planes, every layer in one traversal.  The layers share the table, the
+ * frame (u, v), step, dims and windows_dev; word 1 of a row is the row's layer, {a0 | b0 << 16, layer, mask lo, mask hi}, and
+ * layer_corners_dev holds n_layers records of four floats {x, y, z, unused}: the position of the section's sample (0, 0) on
+ * that layer, which takes the place of `corner` in the position formula.  `corner` is checked to be finite and otherwise
+ * unused.  A row whose layer is not below n_layers is treated as absent.  1 <= n_layers <= 2^20.
+ * hu_layer_tiles: hu_outline_tiles on the row's layer; a child carries its parent's layer.
+ * hu_layer_leaf: hu_outline_leaf on the row's layer, with records {a | b << 16, k | e_from << 8 | e_to << 10 | layer << 12,
+ *   float t_from, float t_to}; totals_dev counts over all layers.
+ * Every other argument, check and count is that of the outline entry points. */
+int hu_layer_tiles(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
+                   const uint32_t dims[2], const float corner[3], const float u[3], const float v[3],
+                   const float* layer_corners_dev, uint32_t n_layers, float step, float radius, uint32_t* counter_dev,
+                   void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream);
+int hu_layer_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
+                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
+                  const float corner[3], const float u[3], const float v[3], const float* layer_corners_dev,
+                  uint32_t n_layers, float step, void* segments_dev, uint32_t segment_capacity, uint64_t* totals_dev,
+                  uint64_t* evaluations_dev, void* stream);
+
 /* ---- the mass properties of an assembly (codecad_amd/assembly_mass.py) -------------------------
  * The lattice, the instance table and the [header row | rows...] lists of the interference entry points, with rows (and a
  * header) of 32 bytes: {x0 | y0 << 16, z0, cand lo, cand hi, full lo, full hi, 0, 0} -- the candidates of the cell and, a

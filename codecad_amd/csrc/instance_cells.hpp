@@ -161,6 +161,8 @@ int cells_launch(void (*kernel)(K), K& k, Args& a, uint32_t lane_bytes, size_t e
     uint32_t block;
     size_t lds;
     int rc;
+    // the scalar slots and every area after the register file are read as 4-byte words at lane_bytes * block
+    if (lane_bytes % 4u) return hu_fail(HU_ERR_BAD_ARG, "lane_bytes must be a multiple of 4");
     if ((rc = hu_workgroup((size_t)lane_bytes + extra_lane_bytes, block, lds))) return rc;
     if ((rc = hu_ensure_attrs())) return rc;
     a.scratch_offset = lane_bytes * block;

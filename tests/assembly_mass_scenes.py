@@ -21,6 +21,7 @@ from codecad_amd import shapes, nodes, _instance_cells
 import oracle
 
 from test_gpu_interference import _random_assembly, _gear_train
+import heavy_instances
 
 Reference = collections.namedtuple("Reference", "w sums owned boxes traversal_sums traversal_owned evaluations levels leaf "
                                                 "premise_broken union_count")
@@ -279,6 +280,7 @@ for _order in OWNERSHIP_ORDERS:
     SCENES["ownership_%d%d%d" % _order] = Scene(functools.partial(_ownership, _order), 0.08)
 for _seed, _k, _blended in RANDOM:
     SCENES["random_%d" % _seed] = Scene(_random(_seed, _k, _blended), None)
+SCENES.update(heavy_instances.mass_scenes(Scene))        # parts with wide register files among light ones
 
 
 def forced_top_cells(dims, side):

@@ -23,6 +23,7 @@ from codecad_amd.assembly_meshes import (TRIANGLE, CORNERS, EDGES, Meshes, sort_
 import oracle
 
 import assembly_mass_scenes as mass_scenes
+import heavy_instances
 import test_section_host as tsh
 from test_gpu_interference import _gear_train
 from test_section_outlines_host import diagonal
@@ -344,6 +345,7 @@ SCENES = {
     "coarse_256": Scene(mass_scenes._coarse, 0.0625, 256),
     "gears": Scene(_gear_train, 0.3),
 }
+SCENES.update(heavy_instances.mass_scenes(Scene))        # parts with wide register files among light ones
 forced_top_cells = mass_scenes.forced_top_cells
 
 

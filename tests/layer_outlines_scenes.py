@@ -20,6 +20,7 @@ from codecad_amd.layer_outlines import LAYER_SEGMENT, layer_heights
 import oracle
 
 import test_section_host as tsh
+import heavy_instances
 import test_section_outlines_host as tso
 
 Reference = collections.namedtuple("Reference", "instances plane heights planes corners step dims first w segments counts layer_counts")
@@ -170,6 +171,7 @@ SCENARIOS = {
     "boxes_and_ball": _boxes_and_ball,
     "far": _far,
 }
+SCENARIOS.update(heavy_instances.layer_scenarios())      # parts with wide register files among light ones, three layers
 NAMED = ["two_boxes", "diagonal", "bar_64_9", "grid_64"]
 
 

@@ -28,6 +28,7 @@ import oracle
 
 from test_gpu_interference import dense_pairs
 from test_gpu_clearance import dense_near, RANDOM, _random_assembly, _gear_train
+import heavy_instances
 
 
 # ---- the references ---------------------------------------------------------------------------------------------------
@@ -238,6 +239,7 @@ SCENARIOS = {
     "far_random": Scenario(lambda gap: _random_far(), FAR_RANDOM_RESOLUTION, (0.0, 4 * FAR_RANDOM_RESOLUTION), 16, False),
     "far_gears": Scenario(lambda gap: _gears_far(), FAR_GEARS_RESOLUTION, (0.0, 0.5), 16, False),
 }
+SCENARIOS.update(heavy_instances.pair_scenarios(Scenario))       # parts with wide register files among light ones
 
 
 # the cases of the forced-depth runs: the random assemblies, two spheres and two boxes, on lattices of 65 to 128 samples

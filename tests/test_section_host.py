@@ -29,6 +29,7 @@ import oracle
 from test_gpu_interference import _plate_and_shaft, _gear_train, _random_assembly
 from test_gpu_assembly_picture import _grid
 from test_instance_cells_reference_host import far_translation
+import heavy_instances
 
 
 # ---- the reference ----------------------------------------------------------------------------------------------------
@@ -152,6 +153,7 @@ SCENARIOS = {
 for _seed, _k, _blended in RANDOM:
     for _kind in ("named", "oblique", "missing"):
         SCENARIOS["random_%d_%s" % (_seed, _kind)] = functools.partial(random_case, _seed, _k, _blended, _kind)
+SCENARIOS.update(heavy_instances.plane_scenarios())      # parts with wide register files among light ones
 
 
 @functools.lru_cache(maxsize=None)

@@ -32,6 +32,7 @@ import oracle
 
 so = sys.modules["codecad_amd.section_outlines"]       # (the package's attribute of that name is the function)
 
+import heavy_instances
 import test_section_host as tsh
 from test_gpu_interference import _gear_train
 
@@ -204,6 +205,7 @@ SCENARIOS = {
     "random_2_named": functools.partial(tsh.random_case, 2, 9, False, "named"),
     "gear_train": gear_train_cut,
 }
+SCENARIOS.update(heavy_instances.plane_scenarios())      # parts with wide register files among light ones
 
 
 @functools.lru_cache(maxsize=None)

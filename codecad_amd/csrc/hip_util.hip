@@ -197,7 +197,8 @@ int check_dims(const uint32_t dims[3], uint64_t& cells)
 }
 
 // The flags a per-tape kernel is launched with: kFlagInRange when no sample coordinate of the launch can exceed the
-// tape's limit (HU_INRANGE=0 never sets it: measurements)
+// tape's limit (HU_INRANGE=0 never sets it: measurements).  A tape of one primitive has a limit too and runs in the plain form,
+// which reads no flags: the flag may be set for code that ignores it.
 uint32_t spec_flags(const hu_tape_s* t, double max_abs_coordinate)
 {
     static const bool off = [] { const char* e = getenv("HU_INRANGE"); return e && e[0] == '0'; }();

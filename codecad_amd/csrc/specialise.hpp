@@ -1285,7 +1285,6 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     if (!build_graph(p.full, nodes, root)) return false;
     std::vector<Path> paths;
     if (!collect_paths(nodes, root, Path(), paths, max_paths)) return false;
-    if (paths.size() < 2) return false;   // a single primitive: nothing to defer
 
     // ---- phase 1: distances; what phase 2 wants from it: the comparison at every select on a path, the distance that
     // entered an op whose direction reads it
@@ -1299,6 +1298,7 @@ inline bool emit_deferred(std::ostringstream& o, const SpecProgram& p, size_t ma
     std::vector<std::array<int, 3>> pt(nodes.size(), {{-1, -1, -1}});   // local coordinates by (point) node
     if (!symbolic_phase1(p, nodes, root, is_choice, keep_w, ph, &pt)) return false;
     if (meta) meta->coord_limit = coordinate_limit(ph);
+    if (paths.size() < 2) return false;   // a single primitive: nothing to defer (its limit is known all the same: the plain form reads no flags)
     ph.n_phase1 = (int)ph.e.st.size();
     // box pruning: which operands of which selects can be decided per box (HU_PRUNE=0: none)
     static const bool prune_off = [] { const char* e = std::getenv("HU_PRUNE"); return e && e[0] == '0'; }();
@@ -1654,7 +1654,7 @@ inline std::string specialised_source(const SpecProgram& p, SpecMeta* meta = nul
     // in 1.0 ms where the plain form takes 4.7)
     static const size_t max_paths = [] { const char* e = std::getenv("HU_MAX_PATHS"); return e && *e ? (size_t)std::atoi(e) : (size_t)400; }();
     const bool ok = emit_deferred(d, p, max_paths, &m);
-    if (!ok) m = SpecMeta();
+    if (!ok) { const double limit = m.coord_limit; m = SpecMeta(); m.coord_limit = limit; }   // (0 unless the analysis ran: a single primitive)
     m.deferred = ok;
     if (meta) *meta = m;
     o << "#include \"kernels.hpp\"\nnamespace sdfk {\nusing sdf::Rec;\n";

@@ -633,6 +633,21 @@ int hu_tape_listing(const float* tape, size_t n, int which, char* buf, size_t ca
     return HU_OK;
 }
 
+int hu_tape_coordinate_limit(const float* tape, size_t n, double* out_limit)
+{
+    if (!tape || !out_limit) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    sdf::DecodedTape d;
+    const std::string err = sdf::decode_tape(tape, n, d);
+    if (!err.empty()) return hu_fail(HU_ERR_BAD_TAPE, "malformed tape: " + err);
+    hu_tape_s t;  // host fields only: nothing touches a device
+    t.n_slots = d.n_slots;
+    keep_programs(&t, d);
+    sdf::SpecMeta meta;   // (what hu_tape_specialize keeps beside the source, and load_specialised hands to the launches)
+    (void)generate_source(&t, &meta);
+    *out_limit = meta.coord_limit;
+    return HU_OK;
+}
+
 int hu_tape_prune_info(hu_tape t, int* bits, int* words)
 {
     if (!t) return hu_fail(HU_ERR_BAD_ARG, "tape is NULL");

@@ -98,6 +98,7 @@ PROTOTYPES = {
     "hu_selftest_minmax3": [_c.POINTER(_c.c_uint64)],
     "hu_tape_source": [_f4, _sz, _c.c_char_p, _sz, _c.POINTER(_sz)],
     "hu_tape_listing": [_f4, _sz, _i, _c.c_char_p, _sz, _c.POINTER(_sz)],
+    "hu_tape_coordinate_limit": [_f4, _sz, _c.POINTER(_d)],
 }
 
 # hu_spec_group (include/hip_util.h): the kernel families of per-tape code

@@ -549,6 +549,11 @@ int hu_tape_source(const float* tape, size_t n_floats, char* buf, size_t capacit
  * full program, 1 the distance-only program (empty for tapes with a rounded blend), 2 / 3 the same as the
  * interpreter runs them, transformed primitives fused into single records.  Same calling convention. */
 int hu_tape_listing(const float* tape, size_t n_floats, int which, char* buf, size_t capacity, size_t* needed);
+/* The tape's coordinate limit (host only, no device needed): per-tape code launched on samples whose |coordinates| all
+ * stay below it skips the range tests of the fast square root in its rectangle and extrusion corners (a handle that
+ * hu_tape_specialize made holds the same number, from the same analysis).  +inf: the tape has no such corner; 0: no
+ * launch may skip them (a half extent below 2^-25, an op the analysis does not bound, a tape it does not cover). */
+int hu_tape_coordinate_limit(const float* tape, size_t n_floats, double* out_limit);
 /* Compile that source with hipRTC without loading it (host only, no device needed): checks that the
  * op library headers in `include_dir` build under hipRTC and that all ten kernels are present.
  * `*code_bytes` (may be NULL) receives the code object size. */

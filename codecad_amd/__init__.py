@@ -16,7 +16,8 @@ same cut as vectors: closed outlines per part on the plane (section_outlines.py)
 one traversal of the device, `layer_heights(asm, plane, layer_height)` the heights of such a stack (layer_outlines.py);
 `assembly_mass_properties(asm, resolution, densities)` weighs an assembly: volume, mass, centre of gravity and inertia of
 every part and of the whole, overlaps counted once (assembly_mass.py); `assembly_meshes(asm, resolution)` gives the surface of
-every part as placed, one triangle mesh each on one lattice (assembly_meshes.py).
+every part as placed, one triangle mesh each on one lattice (assembly_meshes.py); `assembly_voxels(asm, resolution)` gives the
+lattice itself: a uint8 volume with the index of the part that owns each sample, filled on the device (assembly_voxels.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -38,9 +39,10 @@ from .section_outlines import section_outlines, Outlines, Loop  # noqa: F401
 from .layer_outlines import layer_outlines, layer_heights, Layers, LAYER_SEGMENT  # noqa: F401
 from .assembly_mass import assembly_mass_properties, AssemblyMassReport, PartMass  # noqa: F401
 from .assembly_meshes import assembly_meshes, Meshes, TRIANGLE  # noqa: F401
+from .assembly_voxels import assembly_voxels, AssemblyVoxels  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
            "ClearanceReport", "NearMiss", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "layer_outlines",
            "layer_heights", "Layers", "LAYER_SEGMENT", "assembly_mass_properties",
-           "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE"]
+           "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels"]

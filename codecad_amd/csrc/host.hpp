@@ -34,6 +34,7 @@ hipError_t allow_big_lds_outline(size_t bytes);                           // ins
 hipError_t allow_big_lds_layers(size_t bytes);                            // instance_layers.hip
 hipError_t allow_big_lds_mass(size_t bytes);                             // instance_mass.hip
 hipError_t allow_big_lds_mesh(size_t bytes);                              // instance_mesh.hip
+hipError_t allow_big_lds_voxels(size_t bytes);                            // instance_voxels.hip
 }  // namespace hu_cells
 
 // The workgroup of a kernel that keeps `lane_bytes` of LDS per lane (the interpreter's register file and what follows it

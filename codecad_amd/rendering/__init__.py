@@ -6,10 +6,11 @@ bill of materials as CSV (`render_bom`) and its picture with a colour per part, 
 (`render_assembly_image`, assembly_picture.py) and the picture of its section on a plane
 (`render_assembly_section_image`, assembly_section.py) or its outlines as an SVG drawing
 (`render_assembly_section_svg`, assembly_section_svg.py), a stack of parallel cuts as one drawing per layer
-(`render_assembly_layers_svg`, assembly_layers_svg.py), and its parts as one binary STL each
-(`render_assembly_stl`, assembly_stl.py).  The rest of the reference's rendering package (matplotlib viewers, animations, the CLI dispatch) is out of scope."""
+(`render_assembly_layers_svg`, assembly_layers_svg.py), its parts as one binary STL each
+(`render_assembly_stl`, assembly_stl.py), and its part-id volume as one PNG per lattice plane
+(`render_assembly_voxel_layers`, assembly_voxel_layers.py).  The rest of the reference's rendering package (matplotlib viewers, animations, the CLI dispatch) is out of scope."""
 from . import ray_caster, pictures, polygon2d, mesh, stl_renderer, bom, assembly_picture, assembly_section, assembly_section_svg, assembly_stl  # noqa: F401
-from . import assembly_layers_svg  # noqa: F401
+from . import assembly_layers_svg, assembly_voxel_layers  # noqa: F401
 from .bom import render_bom  # noqa: F401
 from .stl_renderer import render_stl  # noqa: F401
 from .pictures import render_image, render_pil_image, render_pixels  # noqa: F401
@@ -19,3 +20,4 @@ from .assembly_section import render_assembly_section_image, render_assembly_sec
 from .assembly_section_svg import render_assembly_section_svg, assembly_section_svg_document  # noqa: F401
 from .assembly_layers_svg import render_assembly_layers_svg  # noqa: F401
 from .assembly_stl import render_assembly_stl, write_assembly_stl  # noqa: F401
+from .assembly_voxel_layers import render_assembly_voxel_layers, render_assembly_voxel_pixels  # noqa: F401

@@ -359,6 +359,32 @@ int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only, 
                           const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
                           float step, void* acc_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- the part-id volume of an assembly (codecad_amd/assembly_voxels.py) -------------------------
+ * The lattice, the instance table and the [header row | rows...] lists of the interference entry points, 16-byte rows
+ * {x0 | y0 << 16, z0 | capped << 31, cand lo, cand hi}: capped says that the HIGHEST candidate of the cell has every sample
+ * of the cell inside it; nothing above a full candidate is listed.  volume_dev: uint8[dims[0]][dims[1]][pitch], aligned to 16
+ * bytes, pitch a multiple of 16 from dims[2] to 65536, filled with 255 (no part) by the caller before the first level; a
+ * sample's byte becomes the lowest instance index it is inside of.  The bytes of a z run past dims[2] are unspecified.
+ * acc_dev: n + 1 uint64, the caller's zeros: the samples each instance owns, then the bytes written for retired cells.
+ * dims at most 65536 per axis; step and thr finite and not negative; child_side a power of two.
+ * hu_assembly_voxels_cells: a cell of side 4 * child_side per parent row.  In each of its 4^3 children the candidates are
+ *   evaluated at the centre in ascending index (a capped one is inherited): dropped for w >= thr, full for w < -thr (only
+ *   with retire != 0), a boundary candidate else; candidates above a child's lowest full one are cleared.  A child whose
+ *   lowest candidate is full has its samples (clipped to dims in x and y, to pitch in z) set to that index and counted; a
+ *   child with any other candidate is appended to children_dev (counted into *counter_dev; rows past `capacity` are
+ *   dropped and counted).
+ * hu_assembly_voxels_leaf: a cell of 4^3 samples per parent row; every candidate but a capped one is evaluated at every
+ *   sample; each z run of four samples is written as one dword (255 past dims[2]).
+ * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
+int hu_assembly_voxels_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
+                             const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
+                             const float corner[3], float step, float thr, uint32_t* counter_dev, void* children_dev,
+                             uint32_t capacity, int retire, void* volume_dev, uint32_t pitch, void* acc_dev,
+                             uint64_t* evaluations_dev, void* stream);
+int hu_assembly_voxels_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
+                            const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
+                            float step, void* volume_dev, uint32_t pitch, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

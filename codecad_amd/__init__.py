@@ -9,6 +9,8 @@ Public layout mirrors the reference package (reference codecad/__init__.py:1-11)
 `mass_properties`, `assembly` (assemblies.py) and the renderers the package has (`rendering`);
 `interference(asm, resolution)` finds the overlapping instances of an assembly on the device, and
 `clearance(asm, resolution, min_gap)` the pairs closer than a gap, with how close and where (clearance.py);
+`separation(asm, resolution)` how far apart every pair of parts is and where they come closest, by branch and bound on the
+device (separation.py);
 `section(asm, plane, resolution)` cuts an assembly with a `Plane`: which part owns each sample of the cut, where parts
 overlap on it, and the cut area of every part and pair (section.py); `section_outlines(asm, plane, resolution)` gives the
 same cut as vectors: closed outlines per part on the plane (section_outlines.py), and
@@ -34,6 +36,7 @@ from . import assemblies  # noqa: F401
 from .assemblies import assembly  # noqa: F401
 from .interference import interference, InterferenceReport  # noqa: F401
 from .clearance import clearance, ClearanceReport, NearMiss  # noqa: F401
+from .separation import separation, SeparationReport, PairSeparation  # noqa: F401
 from .section import section, Section, Plane  # noqa: F401
 from .section_outlines import section_outlines, Outlines, Loop  # noqa: F401
 from .layer_outlines import layer_outlines, layer_heights, Layers, LAYER_SEGMENT  # noqa: F401
@@ -43,6 +46,6 @@ from .assembly_voxels import assembly_voxels, AssemblyVoxels  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
-           "ClearanceReport", "NearMiss", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "layer_outlines",
+           "ClearanceReport", "NearMiss", "separation", "SeparationReport", "PairSeparation", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "layer_outlines",
            "layer_heights", "Layers", "LAYER_SEGMENT", "assembly_mass_properties",
            "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels"]

@@ -160,6 +160,7 @@ int hu_ensure_attrs()
     HU_HIP(hu_cells::allow_big_lds_mass(kMaxLds));     // (instance_mass.hip)
     HU_HIP(hu_cells::allow_big_lds_mesh(kMaxLds));     // (instance_mesh.hip)
     HU_HIP(hu_cells::allow_big_lds_voxels(kMaxLds));   // (instance_voxels.hip)
+    HU_HIP(hu_cells::allow_big_lds_gap(kMaxLds));      // (instance_gap.hip)
     done_for_device = dev;
     return HU_OK;
 }

@@ -35,6 +35,7 @@ hipError_t allow_big_lds_layers(size_t bytes);                            // ins
 hipError_t allow_big_lds_mass(size_t bytes);                             // instance_mass.hip
 hipError_t allow_big_lds_mesh(size_t bytes);                              // instance_mesh.hip
 hipError_t allow_big_lds_voxels(size_t bytes);                            // instance_voxels.hip
+hipError_t allow_big_lds_gap(size_t bytes);                               // instance_gap.hip
 }  // namespace hu_cells
 
 // The workgroup of a kernel that keeps `lane_bytes` of LDS per lane (the interpreter's register file and what follows it

@@ -126,6 +126,17 @@ struct LayerArgs {
     uint32_t segment_capacity;       //   records at or past it are counted and not stored
 };
 
+// the least gap of every pair of instances (instance_gap.hip): what its kernels take beside Args.  There Args is the lattice
+// of interference(), thr the radius r of a child cell around the sample it is judged at, and pairs is not read: the order
+// keys (instance_pairs.hip order_key) of the least v = max(w_i, w_j) known per pair come as two arrays [n_instances^2], the
+// one a launch reads, final before it starts, and the one it lowers.
+struct GapArgs {
+    Args c;
+    const uint32_t* bound;           // cells: the keys every pair is pruned with; leaf: the keys worth lowering; witness: the final keys
+    uint32_t* next;                  // cells, leaf: a copy of `bound` made before the launch, lowered with one atomic min per pair and wavefront
+    unsigned long long* witness;     // witness: per pair the least x << 32 | y << 16 | z whose v has the final key (starts at ~0)
+};
+
 // the surface meshes of an assembly's parts (instance_mesh.hip): what its kernels take beside Args.  There Args describes the
 // lattice of CUBES between the samples of interference() and a ring around them: dims = samples + 1 per axis, corner = the
 // position of the sample (0, 0, 0) -- the shifted index (1, 1, 1) --, a row is a CELL {a0 | b0 << 16, c0, mask lo, mask hi} of

@@ -1,0 +1,341 @@
+// codecad_amd/csrc/instance_gap.hip
+//
+// The SEPARATION of every pair of instances of an assembly (codecad_amd/separation.py): per pair i < j the least
+// v = max(w_i, w_j) over the lattice samples of interference() where both values are numbers, as the order key of
+// instance_pairs.hip (unsigned comparison orders the keys as the values, either zero has the key of +0), and the
+// lexicographically smallest sample that attains it.  Bit for bit what evaluating every instance at every sample gives.
+//
+// The traversal is the one of instance_pairs.hip -- 16-byte rows {x0 | y0 << 16, z0, mask lo, mask hi}, cubic cells of 4^k
+// samples, one wavefront per cell, lane = 16 x + 4 y + z -- but no fixed threshold prunes it: a BRANCH AND BOUND.  Per level
+// boundary there is one array of keys [n][n], U_0 (all ones: nothing known) .. U_L, and the final one after the leaf.  The
+// entry point of level l copies U_l to U_{l+1} on the stream, then its kernel reads U_l only, which no launch writes any
+// more, and lowers U_{l+1}: every bound a cell is pruned with is final when it is read, so the rows, the evaluations and the
+// results do not depend on the order the wavefronts run in.
+//   k_gap_cells (child side s >= 4): a lane is a child cell.  Every candidate of the parent is evaluated at the child's
+//     lattice sample q = min(first + s / 2, dims - 1) per axis -- a sample, not the half-integer centre, so v(q) is an upper
+//     bound on the pair's least v whatever the fields are -- and waits in the wavefront's LDS area, [instance][lane].  Every
+//     sample of the child, clipped to dims, lies within (s / 2) * step * sqrt(3) of q, and a.thr = r is a little more than
+//     that (separation.py).  The pair (i, j) is DROPPED in the child iff (v(q) - U_l[i][j]) > r in binary32, strictly: with
+//     distances of Lipschitz constant at most 1 every sample of the child then has v > U_l[i][j], which a sample attains.
+//     A NaN, in v or in the bound, keeps the pair.  The child keeps the bits of its kept pairs and is listed when it has
+//     any (kernels.hpp wg_compact_slots).  Per pair the wavefront's least key of v(q) goes to U_{l+1}[i][j] with one atomic
+//     min from one lane, and only when it is below the key read.
+//   k_gap_leaf (side 4): a lane is a sample.  Every candidate is evaluated at the samples inside dims; per pair of
+//     candidates the wavefront's least key goes to the final array in the same way.
+//   k_gap_witness (side 4), launched after the leaf over the same list: evaluates again and, for every pair, its first
+//     lane whose v has the pair's final key gives one u64 atomicMin of x << 32 | y << 16 | z (k_clearance_witness's rule).
+// After the keys the accumulators hold one word per level: the entry points copy each list's length there, so that the one
+// read at the end of the traversal also brings the rows every level listed.
+// Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).  The entry points are at the
+// end of this file.
+#include "instance_cells.hpp"
+
+using namespace sdfk;
+using namespace hu_cells;
+
+namespace {
+
+// instance_pairs.hip order_key: the key of v in an order that unsigned comparison keeps, -0 and +0 with the one key of +0
+__device__ __forceinline__ uint32_t order_key(float v)
+{
+    const uint32_t b = __float_as_uint(v == 0.0f ? 0.0f : v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// ... and the float32 of a key (separation.py decodes it alike); the key of all ones, nothing known yet, is a NaN
+__device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// instance_pairs.hip wave_min_to_last_lane: minimum over the 64 lanes of a wavefront; it arrives in lane 63
+__device__ __forceinline__ uint32_t wave_min_to_last_lane(uint32_t v)
+{
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
+    return v;
+}
+
+// Every candidate of `row` evaluated at this lane's point, into the wavefront's LDS area (after the register file) at
+// wl[n * 64 + lane]; live lanes x candidates counted once per wavefront.  The one interpreter call site of a kernel.
+struct GapLane {
+    float* wl;
+    uint32_t lane;
+    // v = max(w_i, w_j) of this lane where both are numbers, else a NaN
+    __device__ __forceinline__ float v(uint32_t i, uint32_t j) const
+    {
+        const float wi = wl[i * 64u + lane], wj = wl[j * 64u + lane];
+        return ((wi == wi) & (wj == wj)) ? fmaxf(wi, wj) : __uint_as_float(0x7fc00000u);
+    }
+};
+template <bool DO>
+__device__ __forceinline__ GapLane gap_lane(const Args& a, const CellRow& row, bool live, float px, float py, float pz)
+{
+    extern __shared__ float4 lds[];
+    GapLane g;
+    g.wl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + a.scratch_offset) + (threadIdx.x >> 6) * 64u * a.n_instances;
+    g.lane = threadIdx.x & 63u;
+    const uint64_t lives = __ballot(live);
+    if (g.lane == 0u && lives) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
+    for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {      // wave-uniform
+        const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
+        g.wl[n * 64u + g.lane] = instance_dist<DO>(a, n, px, py, pz, lds);
+    }
+    return g;
+}
+
+// the wavefront's least key of a pair (this lane: `key`, all ones where it has none) into next[pair], from one lane and only
+// when it lowers the key `known` that was read for the pair
+__device__ __forceinline__ void lower_key(uint32_t* next, uint32_t pair, uint32_t key, uint32_t known, uint32_t lane)
+{
+    const uint32_t kmin = (uint32_t)__builtin_amdgcn_readlane((int)wave_min_to_last_lane(key), 63);
+    if (kmin < known && lane == 0u) atomicMin(next + pair, kmin);
+}
+
+// the child cell a lane takes: its first sample's indices, and whether it has a sample inside dims
+struct ChildLane {
+    uint32_t x, y, z;
+    bool live;
+};
+__device__ __forceinline__ ChildLane child_lane(const Args& a, const CellRow& row, uint32_t lane)
+{
+    const uint32_t s = a.child_side;
+    ChildLane q;
+    q.x = row.x0 + (lane >> 4) * s;
+    q.y = row.y0 + ((lane >> 2) & 3u) * s;
+    q.z = row.z0 + (lane & 3u) * s;
+    q.live = row.have & (q.x < a.dims[0]) & (q.y < a.dims[1]) & (q.z < a.dims[2]);
+    return q;
+}
+
+template <bool DO>
+__global__ void __launch_bounds__(256) k_gap_cells(const GapArgs g)
+{
+    extern __shared__ float4 lds[];
+    const Args& a = g.c;
+    const CellRow row = cell_row(a);
+    const uint32_t s = a.child_side;
+    GapLane c;
+    {
+        // the child's sample q, exactly kernels.hpp sample(): a lattice sample of the child, clipped as the child is
+        const ChildLane q = child_lane(a, row, threadIdx.x & 63u);
+        const uint32_t h = s >> 1;
+        c = gap_lane<DO>(a, row, q.live, sample(a.corner[0], a.step, min(q.x + h, a.dims[0] - 1u)),
+                         sample(a.corner[1], a.step, min(q.y + h, a.dims[1] - 1u)), sample(a.corner[2], a.step, min(q.z + h, a.dims[2] - 1u)));
+    }
+    // the child's indices again, from a lane the compiler takes as new: held across the interpreter they cost it a stack frame
+    uint32_t lane = c.lane;
+    asm volatile("" : "+v"(lane));
+    const ChildLane q = child_lane(a, row, lane);
+    const uint32_t x = q.x, y = q.y, z = q.z;
+    const bool live = q.live;
+    const uint32_t* bound = constant_uniform(g.bound);
+    uint64_t keep = 0ull;
+    // every pair of candidates (instance_cells.hpp for_pairs, spelled out: the lambda's closure cost this kernel a stack frame)
+    for (uint64_t mi = row.mask; mi != 0ull; mi &= mi - 1ull) {  // wave-uniform
+        const uint32_t i = uniform((uint32_t)__builtin_ctzll(mi));
+        for (uint64_t mj = mi & (mi - 1ull); mj != 0ull; mj &= mj - 1ull) {
+            const uint32_t j = uniform((uint32_t)__builtin_ctzll(mj));
+            const uint32_t pair = i * a.n_instances + j;
+            const uint32_t known = bound[pair];                   // final before this launch: a scalar load
+            const float v = c.v(i, j);
+            // the subtraction first: exact where the decision is close (Sterbenz); a NaN on either side compares false
+            if (live && !((v - key_value(known)) > a.thr)) keep |= (1ull << i) | (1ull << j);
+            lower_key(g.next, pair, live && v == v ? order_key(v) : 0xffffffffu, known, lane);
+        }
+    }
+    // after the register file: every candidate's w, [wavefront][instance][lane]; then the compaction's scratch
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds) + a.scratch_offset +
+                                                    (size_t)blockDim.x * a.n_instances * sizeof(float));
+    const bool flag[1] = {keep != 0ull};
+    uint32_t slot[1];
+    wg_compact_slots<1>(flag, a.counter, scratch, slot);         // every wavefront of the workgroup gets here (barriers)
+    if (flag[0] && slot[0] < a.capacity)
+        a.children[slot[0]] = make_uint4(x | (y << 16), z, (uint32_t)keep, (uint32_t)(keep >> 32));
+}
+
+// the sample of a finest cell this lane takes (instance_pairs.hip leaf_lane)
+struct LeafLane {
+    uint32_t x, y, z;
+    bool live;
+    float px, py, pz;
+};
+__device__ __forceinline__ LeafLane leaf_lane(const Args& a, const CellRow& row)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    LeafLane l;
+    l.x = row.x0 + (lane >> 4);
+    l.y = row.y0 + ((lane >> 2) & 3u);
+    l.z = row.z0 + (lane & 3u);
+    l.live = (l.x < a.dims[0]) & (l.y < a.dims[1]) & (l.z < a.dims[2]);
+    // exactly kernels.hpp sample() (the lattice of oracle.grid_eval)
+    l.px = sample(a.corner[0], a.step, l.x);
+    l.py = sample(a.corner[1], a.step, l.y);
+    l.pz = sample(a.corner[2], a.step, l.z);
+    return l;
+}
+
+template <bool DO>
+__global__ void __launch_bounds__(256) k_gap_leaf(const GapArgs g)
+{
+    const Args& a = g.c;
+    const CellRow row = cell_row(a);
+    if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
+    const LeafLane l = leaf_lane(a, row);
+    const GapLane c = gap_lane<DO>(a, row, l.live, l.px, l.py, l.pz);
+    const uint32_t* bound = constant_uniform(g.bound);
+    for_pairs(row.mask, l.live ? row.mask : 0ull, [&](uint32_t i, uint32_t j, bool both, uint64_t) __attribute__((always_inline)) {
+        const uint32_t pair = i * a.n_instances + j;
+        const float v = c.v(i, j);
+        lower_key(g.next, pair, both && v == v ? order_key(v) : 0xffffffffu, bound[pair], c.lane);
+    });
+}
+
+template <bool DO>
+__global__ void __launch_bounds__(256) k_gap_witness(const GapArgs g)
+{
+    const Args& a = g.c;
+    const CellRow row = cell_row(a);
+    if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
+    const LeafLane l = leaf_lane(a, row);
+    const GapLane c = gap_lane<DO>(a, row, l.live, l.px, l.py, l.pz);
+    const uint32_t* bound = constant_uniform(g.bound);
+    for_pairs(row.mask, l.live ? row.mask : 0ull, [&](uint32_t i, uint32_t j, bool both, uint64_t) __attribute__((always_inline)) {
+        const uint32_t pair = i * a.n_instances + j;
+        // the leaf launch has finished: the least key is final, and this kernel never writes it (a scalar load)
+        const uint32_t least = bound[pair];
+        const float v = c.v(i, j);
+        const uint64_t b = __ballot(both && v == v && order_key(v) == least);
+        // lanes go 16 x + 4 y + z: the wavefront's first such lane is its lexicographically smallest sample
+        if (b != 0ull && c.lane == (uint32_t)__builtin_ctzll(b))
+            atomicMin(g.witness + pair, ((unsigned long long)l.x << 32) | ((unsigned long long)l.y << 16) | l.z);
+    });
+}
+
+// [kernel][distance_only]
+void (*const kGapTable[3][2])(GapArgs) = {
+    {k_gap_cells<false>, k_gap_cells<true>},
+    {k_gap_leaf<false>, k_gap_leaf<true>},
+    {k_gap_witness<false>, k_gap_witness<true>},
+};
+
+// Where the accumulators keep what: n^2 uint64 witnesses, then the key arrays U_0 .. U_L and the final one, n^2 uint32
+// each, then L uint32: the rows each level listed.  L, the levels above the finest one, comes from the top side 16 * 4^k.
+struct GapLayout {
+    unsigned long long* witness;
+    uint32_t* keys;
+    uint32_t* rows;
+    uint32_t levels;
+    size_t n2;
+    uint32_t* key_array(uint32_t k) const { return keys + k * n2; }
+};
+int gap_layout(void* acc_dev, uint32_t n, uint32_t top_side, GapLayout& out)
+{
+    if (!acc_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    uint32_t levels = 0;
+    for (uint32_t s = 16u; s <= 65536u && !levels; s *= 4u)
+        if (s == top_side) {
+            for (uint32_t t = s; t > 4u; t /= 4u) ++levels;
+        }
+    if (!levels) return hu_fail(HU_ERR_BAD_ARG, "top_side must be 16 * 4^k, at most 65536");
+    out.n2 = (size_t)n * n;
+    out.witness = static_cast<unsigned long long*>(acc_dev);
+    out.keys = reinterpret_cast<uint32_t*>(out.witness + out.n2);
+    out.rows = out.keys + (levels + 2u) * out.n2;
+    out.levels = levels;
+    return HU_OK;
+}
+
+// What the three entry points check and fill alike: cells_args() of interference's lattice, and what the witness needs:
+// every index within 16 bits.
+int gap_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+             const uint32_t dims[3], const float corner[3], float step, uint64_t* evaluations_dev, GapArgs& g)
+{
+    int rc;
+    std::memset(&g, 0, sizeof(g));
+    if ((rc = cells_args(false, table_dev, n, nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, g.c)))
+        return rc;
+    if (dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (!std::isfinite(step) || step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    return HU_OK;
+}
+
+// a launch over the finest cells: the leaf (level rows and the copy of the keys first) or the witness
+int gap_finest(bool witness, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
+               const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+               uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+{
+    GapArgs g;
+    GapLayout at;
+    int rc;
+    if ((rc = gap_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, g))) return rc;
+    if ((rc = gap_layout(acc_dev, n, top_side, at))) return rc;
+    g.c.child_side = 1u;
+    g.witness = at.witness;
+    if (witness) {
+        g.bound = at.key_array(at.levels + 1u);
+    } else {
+        g.bound = at.key_array(at.levels);
+        g.next = at.key_array(at.levels + 1u);
+        HU_HIP(hipMemcpyAsync(at.rows + (at.levels - 1u), n_parents_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HU_HIP(hipMemcpyAsync(g.next, g.bound, at.n2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return cells_launch(kGapTable[witness ? 2 : 1][distance_only_kernel != 0], g, g.c, lane_bytes, 4u * n, stream);
+}
+
+}  // namespace
+
+hipError_t hu_cells::allow_big_lds_gap(size_t bytes)
+{
+    hipError_t e = hipSuccess;
+    for (const auto& kernel : kGapTable)
+        for (const auto variant : kernel)
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return e;
+}
+
+extern "C" {
+
+int hu_separation_cells(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
+                        const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
+                        const float corner[3], float step, float r, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
+                        uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+{
+    GapArgs g;
+    GapLayout at;
+    int rc;
+    if ((rc = gap_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, g))) return rc;
+    if ((rc = cells_children(g.c, child_side, r, counter_dev, children_dev, capacity))) return rc;
+    if ((rc = gap_layout(acc_dev, n, top_side, at))) return rc;
+    if (!std::isfinite(r) || r < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "r must be finite and not negative");
+    // the level of the cells whose children have child_side: 0 for the top side's
+    uint32_t level = at.levels;
+    for (uint32_t s = top_side / 4u, l = 0; s >= 4u; s /= 4u, ++l)
+        if (s == child_side) level = l;
+    if (level == at.levels) return hu_fail(HU_ERR_BAD_ARG, "child_side must be top_side / 4^k, at least 4");
+    g.bound = at.key_array(level);
+    g.next = at.key_array(level + 1u);
+    g.witness = at.witness;
+    if (level)
+        HU_HIP(hipMemcpyAsync(at.rows + (level - 1u), n_parents_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HU_HIP(hipMemcpyAsync(g.next, g.bound, at.n2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return cells_launch(kGapTable[0][distance_only_kernel != 0], g, g.c, lane_bytes, 4u * n, stream);
+}
+
+int hu_separation_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
+                       const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+                       uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+{
+    return gap_finest(false, table_dev, n, distance_only_kernel, lane_bytes, parents_dev, n_parents_dev, max_parents, dims, corner, step,
+                      top_side, acc_dev, evaluations_dev, stream);
+}
+
+int hu_separation_witness(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
+                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
+                          uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+{
+    return gap_finest(true, table_dev, n, distance_only_kernel, lane_bytes, parents_dev, n_parents_dev, max_parents, dims, corner, step,
+                      top_side, acc_dev, evaluations_dev, stream);
+}
+
+}  // extern "C"

@@ -74,6 +74,9 @@ PROTOTYPES = {
     "hu_mesh_leaf_instances": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _vp, _u32, _vp, _vp, _vp],
     "hu_assembly_mass_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _i, _vp, _vp, _vp],
     "hu_assembly_mass_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _vp, _vp, _vp],
+    "hu_separation_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
+    "hu_separation_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _u32, _vp, _vp, _vp],
+    "hu_separation_witness": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _u32, _vp, _vp, _vp],
     "hu_assembly_voxels_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _i, _vp, _u32, _vp, _vp, _vp],
     "hu_assembly_voxels_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _vp, _u32, _vp, _vp, _vp],
     "hu_ray_caster": [_vp, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp],

@@ -359,6 +359,33 @@ int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only, 
                           const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
                           float step, void* acc_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- the least gap of every pair of instances (codecad_amd/separation.py) -----------------------
+ * The lattice, the instance table and the 16-byte rows of the interference entry points, every index within 16 bits; step
+ * finite and not negative.  Per pair i < j the least v = max(w_i, w_j) over the samples where both are numbers, as the key
+ * of hu_clearance_leaf_indirect, by branch and bound from cells of top_side = 16 * 4^k samples down; L = k + 1 levels lie
+ * above the finest one.  acc_dev, filled with ones by the caller: n * n uint64 witnesses; L + 2 arrays of n * n uint32 keys
+ * (U_0 .. U_L and the final one); L uint32, the rows each level listed.
+ * hu_separation_cells: the level whose children have child_side = top_side / 4^(l + 1) >= 4.  Copies U_l to U_(l+1) on
+ *   the stream, then every child of every parent row evaluates the row's candidates at its lattice sample
+ *   min(first + child_side / 2, dims - 1) per axis, drops the pair (i, j) iff (v - U_l[i][j]) > r in float32 (a NaN keeps it),
+ *   keeps the bits of its kept pairs and is appended to children_dev when it has any (counted into *counter_dev; rows past
+ *   `capacity` are dropped and counted); U_(l+1)[i][j] takes the least key of v met.  r finite and not negative.
+ * hu_separation_leaf: a cell of 4^3 samples per parent row; copies U_L to the final array, which takes the least key of
+ *   every pair of candidates over the samples inside dims.
+ * hu_separation_witness: after the leaf launch, over the same list: each pair's witness becomes the least
+ *   x << 32 | y << 16 | z of the samples whose v has the pair's final key.
+ * All read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
+int hu_separation_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
+                        const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
+                        const float corner[3], float step, float r, uint32_t* counter_dev, void* children_dev,
+                        uint32_t capacity, uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+int hu_separation_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
+                       const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
+                       float step, uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+int hu_separation_witness(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
+                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
+                          float step, uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+
 /* ---- the part-id volume of an assembly (codecad_amd/assembly_voxels.py) -------------------------
  * The lattice, the instance table and the [header row | rows...] lists of the interference entry points, 16-byte rows
  * {x0 | y0 << 16, z0 | capped << 31, cand lo, cand hi}: capped says that the HIGHEST candidate of the cell has every sample

@@ -19,7 +19,10 @@ one traversal of the device, `layer_heights(asm, plane, layer_height)` the heigh
 `assembly_mass_properties(asm, resolution, densities)` weighs an assembly: volume, mass, centre of gravity and inertia of
 every part and of the whole, overlaps counted once (assembly_mass.py); `assembly_meshes(asm, resolution)` gives the surface of
 every part as placed, one triangle mesh each on one lattice (assembly_meshes.py); `assembly_voxels(asm, resolution)` gives the
-lattice itself: a uint8 volume with the index of the part that owns each sample, filled on the device (assembly_voxels.py).
+lattice itself: a uint8 volume with the index of the part that owns each sample, filled on the device (assembly_voxels.py);
+`cavities(asm, resolution)` finds the voids of that volume that no path joins to the outside, and
+`assembly_components(asm, resolution, of)` its connected components of empty space or of solid, labelled on the device
+(assembly_components.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -43,9 +46,12 @@ from .layer_outlines import layer_outlines, layer_heights, Layers, LAYER_SEGMENT
 from .assembly_mass import assembly_mass_properties, AssemblyMassReport, PartMass  # noqa: F401
 from .assembly_meshes import assembly_meshes, Meshes, TRIANGLE  # noqa: F401
 from .assembly_voxels import assembly_voxels, AssemblyVoxels  # noqa: F401
+from .assembly_components import (assembly_components, cavities, ComponentsReport, CavityReport, Component, Cavity,  # noqa: F401
+                                  EMPTY_SPACE, SOLID)
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
            "ClearanceReport", "NearMiss", "separation", "SeparationReport", "PairSeparation", "section", "Section", "Plane", "section_outlines", "Outlines", "Loop", "layer_outlines",
            "layer_heights", "Layers", "LAYER_SEGMENT", "assembly_mass_properties",
-           "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels"]
+           "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels",
+           "assembly_components", "cavities", "ComponentsReport", "CavityReport", "Component", "Cavity", "EMPTY_SPACE", "SOLID"]

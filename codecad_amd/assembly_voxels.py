@@ -82,13 +82,14 @@ class AssemblyVoxels(collections.namedtuple("AssemblyVoxels", "instances corner 
         return numpy.array(self.counts, dtype=numpy.float64) * float(self.step) ** 3
 
 
-def volume_shape(dims, max_bytes):
-    """(nx, ny, pz) of the device buffer over a lattice of `dims`; ValueError when it has more than `max_bytes` bytes."""
+def volume_shape(dims, max_bytes, sample_bytes=1):
+    """(nx, ny, pz) of the device buffer over a lattice of `dims`; ValueError when it has more than `max_bytes` bytes at
+    `sample_bytes` a sample (a caller that keeps further volumes of that shape beside the ids counts them in)."""
     nx, ny, nz = (int(d) for d in dims)
     pz = -(-nz // _RUN) * _RUN
-    if nx * ny * pz > max_bytes:
+    if nx * ny * pz * sample_bytes > max_bytes:
         raise ValueError("a lattice of %s samples needs a volume of %d bytes, more than max_bytes = %d; use a coarser resolution"
-                         % ([nx, ny, nz], nx * ny * pz, max_bytes))
+                         % ([nx, ny, nz], nx * ny * pz * sample_bytes, max_bytes))
     return nx, ny, pz
 
 
@@ -109,14 +110,27 @@ def assembly_voxels(asm, resolution, initial_capacity=None, retire=True, max_byt
     `retire=False` retires no cell: every sample a part may own is evaluated at the finest level (the same volume,
     slower).  `initial_capacity` caps the first guess of every cell list, as in interference().  Raises ValueError for
     what interference() refuses and for a volume of more than `max_bytes` bytes."""
+    voxels, volume = _device_volume(asm, resolution, initial_capacity, retire, max_bytes)
+    if volume is not None:
+        volume.release()
+    return voxels
+
+
+def _device_volume(asm, resolution, initial_capacity, retire, max_bytes, sample_bytes=1, check_dims=None):
+    """assembly_voxels() for a caller that goes on with the volume on the device (assembly_components.py) ->
+    (AssemblyVoxels, the uint8[nx, ny, pz] Buffer, still the caller's to release -- or None when nothing was launched).
+    `sample_bytes`: what the caller keeps per sample of that shape, the ids included, against `max_bytes`;
+    `check_dims(dims)`: the caller's own refusals, before anything is launched."""
     instances = cells.visible(asm, resolution)
     corner, step, dims = cells.checked_lattice(instances, resolution)
-    nx, ny, pz = volume_shape(dims, max_bytes)
+    nx, ny, pz = volume_shape(dims, max_bytes, sample_bytes)
+    if check_dims is not None:
+        check_dims(dims)
     n = len(instances)
     side = cells.top_side(dims)
     top = top_rows(instances, corner, step, dims, side) if n else ()
     if len(top) == 0:
-        return _voxels(instances, corner, step, dims, numpy.full(tuple(int(d) for d in dims), EMPTY, numpy.uint8), [0] * n, 0, 0)
+        return _voxels(instances, corner, step, dims, numpy.full(tuple(int(d) for d in dims), EMPTY, numpy.uint8), [0] * n, 0, 0), None
     queue = hip_manager.queue
     volume = hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue)
     check(hip_manager.lib.hu_memset(volume.device_ptr, EMPTY, volume.size, queue.handle), "hu_memset")
@@ -126,5 +140,4 @@ def assembly_voxels(asm, resolution, initial_capacity=None, retire=True, max_byt
         thr=lambda child: threshold(child, step), cells="hu_assembly_voxels_cells", finest=[("hu_assembly_voxels_leaf", where)],
         cells_extra=(int(bool(retire)),) + where, accumulators=n + 1)
     part_ids = volume.read()[:, :, :int(dims[2])]
-    volume.release()
-    return _voxels(instances, corner, step, dims, part_ids, acc[:n], evaluations, traversals)
+    return _voxels(instances, corner, step, dims, part_ids, acc[:n], evaluations, traversals), volume

@@ -412,6 +412,39 @@ int hu_assembly_voxels_leaf(const void* table_dev, uint32_t n, int distance_only
                             const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
                             float step, void* volume_dev, uint32_t pitch, void* acc_dev, uint64_t* evaluations_dev, void* stream);
 
+/* ---- connected components of the part-id volume (codecad_amd/assembly_components.py) -----------
+ * volume_dev: the uint8[dims[0]][dims[1]][pitch] volume of the entry points above, still on the device.  S is its samples
+ * z < dims[2] with id != 255 (solid != 0) or id == 255 (solid == 0); two samples of S are connected when they differ by one
+ * step along one axis.  labels_dev: uint32[dims[0]][dims[1]][pitch], aligned to 4 bytes; dims[0] * dims[1] * pitch at most
+ * 2^31.  Between hu_components_local and hu_components_finish an entry of a sample of S is the index INTO THE BUFFER,
+ * (x * dims[1] + y) * pitch + z, of a sample of its component that is not above its own, and no call raises an entry;
+ * 0xffffffff outside S and in the padding.  The calls are made in this order on one stream:
+ * hu_components_local: local != 0: every workgroup labels a tile of HU_COMPONENTS_TILE_X x _Y x _Z samples in LDS and writes
+ *   the index of the tile-local root; local == 0: every sample of S gets its own index.
+ * hu_components_merge: unites the two sides of every connected pair across a tile face (local != 0) or of every pair at
+ *   all (local == 0), union-find with atomicMin.
+ * hu_components_flatten: every entry becomes the index of its root, the least of its component.
+ * hu_components_stats: assign_slots != 0 (the first call): every root adds one to *counter_dev (the caller's zero) and
+ *   keeps 0x80000000 | slot in its own entry.  Then every sample adds to row `slot` of table_dev, `capacity` zeroed rows of
+ *   HU_COMPONENTS_ROW_BYTES, aligned to 8:
+ *     uint64 count, sum x, sum y, sum z, parts; uint32 ~lo[3], hi[3], label, flags
+ *   -- the lowest index per axis complemented (a zeroed row is empty), label the LINEAR index (x * dims[1] + y) * dims[2] + z
+ *   of the root, flags bit 0: a sample has an index 0 or dims - 1; parts the mask of the ids of the component's samples
+ *   (solid != 0) or of the in-lattice 6-neighbours of its samples (solid == 0).  Rows of slots >= capacity are not touched:
+ *   with *counter_dev > capacity the caller calls again with a larger zeroed table and assign_slots == 0.
+ * hu_components_finish: every entry becomes the LINEAR index of its root. */
+#define HU_COMPONENTS_TILE_X 8
+#define HU_COMPONENTS_TILE_Y 8
+#define HU_COMPONENTS_TILE_Z 16
+#define HU_COMPONENTS_ROW_BYTES 72
+int hu_components_local(const void* volume_dev, void* labels_dev, const uint32_t dims[3], uint32_t pitch, int solid, int local,
+                        void* stream);
+int hu_components_merge(void* labels_dev, const uint32_t dims[3], uint32_t pitch, int local, void* stream);
+int hu_components_flatten(void* labels_dev, const uint32_t dims[3], uint32_t pitch, void* stream);
+int hu_components_stats(const void* volume_dev, void* labels_dev, const uint32_t dims[3], uint32_t pitch, int solid,
+                        int assign_slots, uint32_t* counter_dev, void* table_dev, uint32_t capacity, void* stream);
+int hu_components_finish(void* labels_dev, const uint32_t dims[3], uint32_t pitch, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

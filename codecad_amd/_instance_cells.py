@@ -247,6 +247,33 @@ def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dt
     return evaluations, acc, runs
 
 
+def traverse_records(instances, top, side, corner, step, dims, initial_capacity, capacity, words, thr, cells, leaf, wins, factor,
+                     frame=(), too_many=None):
+    """traverse() for a finest level that writes RECORDS of `words` uint32 (segments, triangles) into a buffer of `capacity`
+    of them and counts them in n + 1 uint64 accumulators, all of them and per instance; `leaf` is its entry point.  Run
+    again with int(count * 1.125) + 16 records while they did not fit -- a ValueError(too_many % count) where that is
+    given and the new capacity is past 2^32 - 1 -> (evaluations, totals uint64[n + 1], runs of traverse() in all, the
+    records written uint32[count, words])."""
+    runs = 0
+    while True:
+        records = hip_util.Buffer(numpy.uint32, (capacity, words), queue=hip_manager.queue)
+        try:
+            evaluations, totals, ran = traverse(
+                instances, top, side, corner, step, dims, initial_capacity, pair_dtype=numpy.dtype(numpy.uint64), pair_init={}, thr=thr,
+                cells=cells, finest=[(leaf, (records.device_ptr, capacity))], wins=wins, factor=factor, frame=frame,
+                accumulators=len(instances) + 1)
+            runs += ran
+            total = int(totals[0])
+            if total <= capacity:
+                rows = records.read()[:total].copy() if total else numpy.zeros((0, words), dtype=numpy.uint32)
+                return evaluations, totals, runs, rows
+        finally:
+            records.release()
+        capacity = int(total * 1.125) + 16
+        if too_many is not None and capacity > 0xffffffff:
+            raise ValueError(too_many % total)
+
+
 def index_position(corner, step, index):
     """The position of the sample at `index`, as the kernels compute it (float32 per axis)."""
     return util.Vector(*(float(corner[k] + step * numpy.float32(index[k])) for k in range(3)))

@@ -34,8 +34,6 @@ import math
 import numpy
 
 from . import _instance_cells as cells
-from . import hip_util
-from .hip_util import manager as hip_manager
 from ._instance_cells import Instance
 
 _CELL = 4
@@ -172,21 +170,8 @@ def assembly_meshes(asm, resolution, cull=True, initial_capacity=None, triangle_
     top = top_cells(wins, cubes, side, everywhere=not cull)
     if len(top) == 0:
         return empty
-    queue = hip_manager.queue
     capacity = first_capacity(wins) if triangle_capacity is None else max(1, int(triangle_capacity))
-    runs = 0
-    while True:
-        records = hip_util.Buffer(numpy.uint32, (capacity, 8), queue=queue)
-        evaluations, totals, ran = cells.traverse(
-            instances, top, side, corner, step, cubes, initial_capacity, pair_dtype=numpy.dtype(numpy.uint64), pair_init={},
-            thr=lambda child: radius(child, step), cells="hu_mesh_cells",
-            finest=[("hu_mesh_leaf_instances", (records.device_ptr, capacity))], wins=wins, factor=_CELL, accumulators=n + 1)
-        runs += ran
-        total = int(totals[0])
-        if total <= capacity:
-            break
-        records.release()
-        capacity = int(total * 1.125) + 16
-    got = records.read()[:total].copy().view(TRIANGLE).reshape(-1) if total else numpy.zeros(0, dtype=TRIANGLE)
-    records.release()
-    return Meshes(named, corner, step, dims, sort_triangles(got), totals[1:].astype(numpy.int64), evaluations, runs)
+    evaluations, totals, runs, rows = cells.traverse_records(
+        instances, top, side, corner, step, cubes, initial_capacity, capacity, 8, thr=lambda child: radius(child, step),
+        cells="hu_mesh_cells", leaf="hu_mesh_leaf_instances", wins=wins, factor=_CELL)
+    return Meshes(named, corner, step, dims, sort_triangles(rows.view(TRIANGLE).reshape(-1)), totals[1:].astype(numpy.int64), evaluations, runs)

@@ -174,4 +174,16 @@ int cells_launch(void (*kernel)(K), K& k, Args& a, uint32_t lane_bytes, size_t e
     return HU_OK;
 }
 
+// What a unit's allow_big_lds_* hook (host.hpp) does with its [kernel][distance_only] table: every kernel of it may take
+// `bytes` of dynamic LDS.
+template <class K, size_t N>
+hipError_t allow_big_lds_table(void (*const (&table)[N][2])(K), size_t bytes)
+{
+    hipError_t e = hipSuccess;
+    for (const auto& level : table)
+        for (const auto variant : level)
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return e;
+}
+
 }  // namespace hu_cells

@@ -287,11 +287,7 @@ int gap_finest(bool witness, const void* table_dev, uint32_t n, int distance_onl
 
 hipError_t hu_cells::allow_big_lds_gap(size_t bytes)
 {
-    hipError_t e = hipSuccess;
-    for (const auto& kernel : kGapTable)
-        for (const auto variant : kernel)
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
+    return allow_big_lds_table(kGapTable, bytes);
 }
 
 extern "C" {

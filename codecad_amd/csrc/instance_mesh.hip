@@ -206,11 +206,7 @@ void (*const kMeshTable[2][2])(MeshArgs) = {
 
 hipError_t hu_cells::allow_big_lds_mesh(size_t bytes)
 {
-    hipError_t e = hipSuccess;
-    for (const auto& level : kMeshTable)
-        for (const auto variant : level)
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
+    return allow_big_lds_table(kMeshTable, bytes);
 }
 
 extern "C" {

@@ -262,11 +262,7 @@ int voxel_args(const void* table_dev, uint32_t n, const void* parents_dev, const
 
 hipError_t hu_cells::allow_big_lds_voxels(size_t bytes)
 {
-    hipError_t e = hipSuccess;
-    for (const auto& kernel : kVoxelTable)
-        for (const auto variant : kernel)
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
+    return allow_big_lds_table(kVoxelTable, bytes);
 }
 
 extern "C" {

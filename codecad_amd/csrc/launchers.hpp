@@ -18,6 +18,7 @@
 //   instance_section.hip  the planar section of an assembly (codecad_amd/section.py), likewise;
 //   instance_outline.hip  the vector outlines of that section (codecad_amd/section_outlines.py), likewise;
 //   instance_layers.hip   those outlines on a stack of parallel planes in one traversal (codecad_amd/layer_outlines.py), likewise;
+//                 both wrap the one kernel body of outline_kernels.hpp, each with its own Args type;
 //   instance_mass.hip   the mass properties of an assembly (codecad_amd/assembly_mass.py), likewise;
 //   instance_mesh.hip   the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py), likewise;
 //   sort.hip, exchange.hip, mesh.hip  the sort of a block list, the exchange step of the multi-GPU levels, marching cubes.

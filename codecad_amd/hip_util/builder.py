@@ -38,7 +38,7 @@ HIPCC_FLAGS = [
 # every other kernel -- ray caster, bitmap, 2D contouring, mass integrals, self-test (render.hip), the exchange step,
 # the sort, marching cubes, the interference and clearance checks (instance_pairs.hip), the ray caster over instances
 # (instance_rays.hip), the section of an assembly (instance_section.hip), its outlines (instance_outline.hip) and their layers
-# (instance_layers.hip), its mass properties (instance_mass.hip), the meshes of its parts (instance_mesh.hip), its
+# (instance_layers.hip; both compile the one body of outline_kernels.hpp, each in its own unit), its mass properties (instance_mass.hip), the meshes of its parts (instance_mesh.hip), its
 # part-id volume (instance_voxels.hip), the least gap of its pairs (instance_gap.hip) and the connected components of the
 # volume (instance_components.hip) -- is built without it, each unit with the entry points of its kernels; so is tape_build.hip, the host-only build of a tape's
 # own kernels (hipRTC, the on-disk cache, the precompiled header), which holds no kernel at all.

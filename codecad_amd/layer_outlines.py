@@ -33,7 +33,6 @@ the outline kernels with the plane's corner read from a table by the row's layer
 is -- one table, one set of lists, one synchronisation.
 """
 import collections
-import ctypes
 
 import numpy
 
@@ -42,7 +41,7 @@ from . import hip_util
 from .hip_util import manager as hip_manager
 from ._instance_cells import Instance
 from .section import Plane, lattice, windows, _projected
-from .section_outlines import SEGMENT, Outlines, MAX_SAMPLES_PER_AXIS, square_windows, radius, stitch
+from .section_outlines import SEGMENT, Outlines, checked_samples, square_windows, radius, stitch
 
 _TILE = 8
 MAX_LAYERS = 1 << 20                # a record keeps the layer in the 20 bits above bit 12
@@ -236,8 +235,7 @@ def seed(instances, plane, resolution, heights, cull=True):
     `planes` and `corners`, the windows of squares `wins`, the lattice of `squares`, the `side` of the top tiles and the `top`
     rows."""
     _, step, dims, first, projected = lattice(instances, plane, resolution)
-    if dims[0] > MAX_SAMPLES_PER_AXIS or dims[1] > MAX_SAMPLES_PER_AXIS:
-        raise ValueError("resolution %g gives a section of %s samples: outlines take at most 65535 per axis" % (resolution, dims.tolist()))
+    checked_samples(resolution, dims)
     planes, corners = layer_planes(plane, heights, first)
     flat = projected.copy()
     flat[:, :, 2] = 0.0                                  # the windows along u and v alone: every layer has its own test
@@ -265,33 +263,20 @@ def layer_outlines(asm, plane, resolution, heights, cull=True, initial_capacity=
     empty = numpy.zeros(0, dtype=LAYER_SEGMENT)
     if len(top) == 0:
         return _result(named, plane, heights, planes, corners, step, dims, empty, numpy.zeros(n, dtype=numpy.int64), 0, 0)
-    queue = hip_manager.queue
     if segment_capacity is None:
         capacity = min((8 * int(squares[0] + squares[1]) + 64) * len(numpy.unique(top[:, 1])), 1 << 22)
     else:
         capacity = max(1, int(segment_capacity))
     table = numpy.zeros((n_layers, 4), dtype=numpy.float32)
     table[:, :3] = corners
-    table_dev = hip_util.Buffer(numpy.float32, table.shape, queue=queue)
+    table_dev = hip_util.Buffer(numpy.float32, table.shape, queue=hip_manager.queue)
     table_dev.enqueue_write(table)
-    frame = tuple((ctypes.c_float * 3)(*(float(c) for c in x)) for x in (plane.u, plane.v)) + (table_dev.device_ptr, n_layers)
-    runs = 0
-    while True:
-        records = hip_util.Buffer(numpy.uint32, (capacity, 4), queue=queue)
-        evaluations, totals, ran = cells.traverse(
-            instances, top, side, corners[0], step, squares, initial_capacity, pair_dtype=numpy.dtype(numpy.uint64), pair_init={},
-            thr=lambda child: radius(child, step), cells="hu_layer_tiles", finest=[("hu_layer_leaf", (records.device_ptr, capacity))],
-            wins=wins, factor=_TILE, frame=frame, accumulators=n + 1)
-        runs += ran
-        total = int(totals[0])
-        if total <= capacity:
-            break
-        records.release()
-        capacity = int(total * 1.125) + 16
-        if capacity > 0xffffffff:
-            table_dev.release()
-            raise ValueError("%d segments: more than one buffer of 2^32 records holds" % total)
-    got = records.read()[:total].copy().view(LAYER_SEGMENT).reshape(-1) if total else empty
-    records.release()
-    table_dev.release()
-    return _result(named, plane, heights, planes, corners, step, dims, sort_records(got), totals[1:].astype(numpy.int64), evaluations, runs)
+    try:
+        evaluations, totals, runs, rows = cells.traverse_records(
+            instances, top, side, corners[0], step, squares, initial_capacity, capacity, 4, thr=lambda child: radius(child, step),
+            cells="hu_layer_tiles", leaf="hu_layer_leaf", wins=wins, factor=_TILE, frame=plane.frame() + (table_dev.device_ptr, n_layers),
+            too_many="%d segments: more than one buffer of 2^32 records holds")
+    finally:
+        table_dev.release()
+    records = sort_records(rows.view(LAYER_SEGMENT).reshape(-1))
+    return _result(named, plane, heights, planes, corners, step, dims, records, totals[1:].astype(numpy.int64), evaluations, runs)

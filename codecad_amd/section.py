@@ -102,6 +102,10 @@ class Plane(collections.namedtuple("Plane", "origin u v normal")):
         """u = +y, v = +z, seen from +x."""
         return cls((x, 0, 0), (1, 0, 0), (0, 1, 0))
 
+    def frame(self):
+        """(u, v) as the entry points of the section and of its outlines take them: two float[3]."""
+        return tuple((ctypes.c_float * 3)(*(float(c) for c in x)) for x in (self.u, self.v))
+
 
 # the samples inside one instance (`parts`) or inside both of a pair (`overlaps`)
 Cut = collections.namedtuple("Cut", "i j count area centroid index_box bounding_box index_sums")
@@ -250,7 +254,7 @@ def section(asm, plane, resolution, distance=False, cull=True, initial_capacity=
     maps = [part_ids, inside_count]
     if distance:        # (every sample lies in a surviving tile)
         maps += [hip_util.Buffer(numpy.float32, shape, queue=queue), hip_util.Buffer(numpy.int32, shape, queue=queue)]
-    frame = tuple((ctypes.c_float * 3)(*(float(c) for c in x)) for x in (plane.u, plane.v)) + (int(bool(distance)),)
+    frame = plane.frame() + (int(bool(distance)),)
     pointers = tuple(m.device_ptr for m in maps) + ((None, None) if not distance else ())
     evaluations, acc, runs = cells.traverse(
         instances, top, side, corner, step, dims3, initial_capacity, pair_dtype=_PAIR, pair_init={"lo": 0xffffffff},

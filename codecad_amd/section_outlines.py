@@ -25,15 +25,12 @@ r = `radius(S, step)`; a NaN keeps its candidate.  The finest tiles (8 x 8 squar
 `cull=False` takes every square with every instance, on one level.  The culling assumes what `section()` assumes.
 """
 import collections
-import ctypes
 import math
 
 import numpy
 
 from . import _instance_cells as cells
-from . import hip_util
 from . import section as _section
-from .hip_util import manager as hip_manager
 from ._instance_cells import Instance
 from .section import Plane
 
@@ -153,6 +150,12 @@ def stitch(segments, n, first=(0.0, 0.0), step=1.0):
     return loops
 
 
+def checked_samples(resolution, dims):
+    """ValueError for a section of more than MAX_SAMPLES_PER_AXIS samples along u or v."""
+    if dims[0] > MAX_SAMPLES_PER_AXIS or dims[1] > MAX_SAMPLES_PER_AXIS:
+        raise ValueError("resolution %g gives a section of %s samples: outlines take at most 65535 per axis" % (resolution, dims.tolist()))
+
+
 def _empty(named, plane, corner, step, dims, n):
     return Outlines(named, plane, corner, step, tuple(int(d) for d in dims), numpy.zeros(0, dtype=SEGMENT), [[] for _ in range(n)],
                     numpy.zeros(n, dtype=numpy.int64), 0, 0)
@@ -169,8 +172,7 @@ def section_outlines(asm, plane, resolution, cull=True, initial_capacity=None, s
         raise ValueError("section_outlines takes a codecad_amd.Plane, not %r" % (plane,))
     instances = cells.visible(asm, resolution)
     corner, step, dims, first, projected = _section.lattice(instances, plane, resolution)
-    if dims[0] > MAX_SAMPLES_PER_AXIS or dims[1] > MAX_SAMPLES_PER_AXIS:
-        raise ValueError("resolution %g gives a section of %s samples: outlines take at most 65535 per axis" % (resolution, dims.tolist()))
+    checked_samples(resolution, dims)
     n = len(instances)
     named = [Instance(i.name, i) for i in instances]
     wins = square_windows(_section.windows(projected, first, step, dims))
@@ -179,24 +181,10 @@ def section_outlines(asm, plane, resolution, cull=True, initial_capacity=None, s
     top = _section.top_tiles(wins, squares[:2], side, everywhere=not cull) if n else []
     if len(top) == 0:
         return _empty(named, plane, corner, step, dims, n)
-    queue = hip_manager.queue
     capacity = 8 * int(squares[0] + squares[1]) + 64 if segment_capacity is None else max(1, int(segment_capacity))
-    frame = tuple((ctypes.c_float * 3)(*(float(c) for c in x)) for x in (plane.u, plane.v))
-    runs = 0
-    while True:
-        records = hip_util.Buffer(numpy.uint32, (capacity, 4), queue=queue)
-        evaluations, totals, ran = cells.traverse(
-            instances, top, side, corner, step, squares, initial_capacity, pair_dtype=numpy.dtype(numpy.uint64), pair_init={},
-            thr=lambda child: radius(child, step), cells="hu_outline_tiles", finest=[("hu_outline_leaf", (records.device_ptr, capacity))],
-            wins=wins, factor=_TILE, frame=frame, accumulators=n + 1)
-        runs += ran
-        total = int(totals[0])
-        if total <= capacity:
-            break
-        records.release()
-        capacity = int(total * 1.125) + 16
-    got = records.read()[:total].copy().view(SEGMENT).reshape(-1) if total else numpy.zeros(0, dtype=SEGMENT)
-    records.release()
-    segments = sort_segments(got)
+    evaluations, totals, runs, rows = cells.traverse_records(
+        instances, top, side, corner, step, squares, initial_capacity, capacity, 4, thr=lambda child: radius(child, step),
+        cells="hu_outline_tiles", leaf="hu_outline_leaf", wins=wins, factor=_TILE, frame=plane.frame())
+    segments = sort_segments(rows.view(SEGMENT).reshape(-1))
     return Outlines(named, plane, corner, step, tuple(int(d) for d in dims), segments, stitch(segments, n, first, float(step)),
                     totals[1:].astype(numpy.int64), evaluations, runs)

@@ -131,8 +131,19 @@ def kernel_extras(n):
         "interference cells": 0, "interference leaf": 0, "clearance cells": 0, "clearance leaf": 4 * n, "clearance witness": 4 * n,
         "section tiles": 0, "section tiles with distance": 4 * n, "section leaf": 0, "section leaf with distance": 0,
         "outline tiles": 0, "outline leaf": 8, "layer tiles": 0, "layer leaf": 8, "mesh cells": 0, "mesh leaf": 8,
-        "mass cells": 0, "mass leaf": 0,
+        "mass cells": 0, "mass leaf": 0, "voxel cells": 0, "voxel leaf": 0,
+        "separation cells": 4 * n, "separation leaf": 4 * n, "separation witness": 4 * n,
     }
+
+
+REGIMES = ["128 lanes", "64 lanes", "64 lanes above 64 KiB", "the largest LDS"]
+
+
+def regimes_of(lane_bytes, extra_per_lane=0):
+    """The regimes of REGIMES that a larger `lane_bytes` can still take a kernel to, from the rule: the ones its unpadded
+    workgroup is not in already (256 lanes reach all four; 128 lanes, as solids64's separation has them, the last three)."""
+    lanes, per_lane = cells_lanes(lane_bytes, extra_per_lane), lane_bytes + extra_per_lane
+    return [regime for regime, there in zip(REGIMES, (lanes == 256, lanes > 64, per_lane * 64 + 128 <= 64 * 1024, True)) if there]
 
 
 def lanes_table(instances):
@@ -214,6 +225,7 @@ def without_heavy(name):
 
 def without_heavy_references(name):
     """What each family's reference gives for the scene without its heavy parts, by the family's own functions."""
+    import assembly_voxels_scenes as avs
     import test_section_host as tsh
     import test_section_outlines_host as tso
     import layer_outlines_scenes as los
@@ -231,7 +243,9 @@ def without_heavy_references(name):
             "outlines": tso.reference_outlines(asm, plane_of(name), resolution).counts.tolist(),
             "layers": los.reference_layers(asm, plane, resolution, heights).layer_counts.tolist(),
             "meshes": ams.reference_meshes(visible, *lattice).counts.tolist(),
-            "mass": mass.reference_mass(visible, *lattice, True).sums}
+            "mass": mass.reference_mass(visible, *lattice, True).sums,
+            "separation": separation_of(visible, lattice[2], lattice[1], mass.dense_fields(visible, *lattice)),
+            "voxels": avs.reference_voxels(visible, *lattice, True).counts}
 
 
 @functools.lru_cache(maxsize=None)
@@ -289,6 +303,27 @@ def meshes_traversal(name):
 def mass_reference(name, retire=True):
     import assembly_mass_scenes as mass
     return mass.reference(name, retire)
+
+
+def separation_of(instances, dims, step, w):
+    """(Dense, Traversal) of separation_scenes.py over the dense fields `w`."""
+    import separation_scenes as sep
+    return sep.dense(w), sep.traverse(sep.field_values(w), len(instances), dims, step)
+
+
+@functools.lru_cache(maxsize=None)
+def separation_reference(name):
+    """(Dense, Traversal) of a scene, over the fields its mass reference evaluates."""
+    import assembly_mass_scenes as mass
+    instances, corner, step, dims = lattice3(name)
+    return separation_of(instances, dims, step, mass._fields(name))
+
+
+def voxels_reference(name, retire=True):
+    """The Reference of assembly_voxels_scenes.py for a scene, which registers the heavy scenes itself (through the mass
+    scenes' table) and caches every reference per session: nothing is kept here."""
+    import assembly_voxels_scenes as avs
+    return avs.reference(name, retire)
 
 
 # ---- what each family's own scenario table takes (the family modules register these entries themselves) --------------------

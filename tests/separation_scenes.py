@@ -1,5 +1,6 @@
 """The scenarios of the separation tests (test_separation_host.py holds the traversal to the dense definition on the CPU;
-test_gpu_separation.py holds the device to both) and their CPU reference, written from codecad_amd/separation.py's
+test_gpu_separation.py holds the device to both; test_separation_edges_host.py and test_gpu_separation_edges.py do the
+same for the scenarios at the edges of the branch and bound, at the end of this file) and their CPU reference, written from codecad_amd/separation.py's
 definitions over the oracle:
   * the DENSE half (`dense`) evaluates every instance over the whole lattice (oracle.grid_eval) and gives, per pair, the
     order key of the least v = max(w_i, w_j) over the samples where both are numbers and the first sample, in (x, y, z)
@@ -120,7 +121,11 @@ def _pairs_of(mask, n):
                 yield i, j, both
 
 
-def traverse(values, n, dims, step, side=None, max_top_cells=512):
+def traverse(values, n, dims, step, side=None, max_top_cells=512, dropped=numpy.greater, watch=None, listed=None):
+    """`dropped(difference, r)` is the drop rule, strictly greater as the kernels have it (the edge tests show what another
+    one would change); `watch(level, i, j, first, at, v, bound, difference, r)` sees every pair of every level: the first
+    indices [m, 64, 3] of the children, which of them are live children of rows with both bits, and the float32 operands;
+    `listed`, a list, gets the origins [m, 3] of the rows every level lists."""
     dims = numpy.asarray(dims, dtype=numpy.int64)
     side = top_side(dims, max_top_cells) if side is None else side
     counts = [int(-(-d // side)) for d in dims]
@@ -142,12 +147,16 @@ def traverse(values, n, dims, step, side=None, max_top_cells=512):
                 v = pair_value(w[i], w[j])
                 difference = v - key_value(keys[i, j])                        # float32 - float32, rounded once
                 assert difference.dtype == numpy.float32
-                kept = at & ~(difference > r)                                 # (a NaN keeps the pair)
+                kept = at & ~dropped(difference, r)                           # (a NaN keeps the pair)
+                if watch is not None:
+                    watch(len(level_rows), i, j, first, at, v, key_value(keys[i, j]), difference, r)
                 keep[kept] |= (one << numpy.uint64(i)) | (one << numpy.uint64(j))
                 lowered[i, j] = min(lowered[i, j], order_keys(v[at]).min())
             going = keep != 0
             origin, mask, keys = first[going], keep[going], lowered
             level_rows.append(len(origin))
+            if listed is not None:
+                listed.append(origin)
             side = child
         # the finest cells, twice: the least keys, then the witnesses
         first, live, w, count = _cells(values, n, origin, mask, 1, dims)
@@ -238,6 +247,106 @@ def fine_spheres():
     instances = _instance_cells.visible(asm, FINE_RESOLUTION)
     corner, step, dims = _instance_cells.checked_lattice(instances, FINE_RESOLUTION)
     return asm, FINE_RESOLUTION, dims, traverse(point_values(instances, corner, step), 2, dims, step)
+
+
+# ---- the scenarios at the edges of the branch and bound (test_separation_edges_host.py proves each holds its edge) ------
+
+DEEP_SIDES = (1024, 4096, 65536)            # forced on `spheres` and `rims`: 4, 5 and 7 levels, the last all gap_layout() takes
+LONG_RESOLUTION = 2.0 ** -6
+LONG_RADII = (0.26, 0.25)                   # the larger ball first: the least v lies past the middle, at index 32768
+LONG_DISTANCE = 1023.485                    # (0.26 + 1023.485 + 0.25) * 64 = 65535.68: 65536 samples
+FAR = (1000, -2000, 500)
+ZERO_STEP = 2.0 ** -4
+# near_r: the small ball's y; found once by bisection over the binary32 numbers between 0.1 and 0.11 on the child at
+# (36, 28, 16) of the level of side 4 (test_separation_edges_host.py measures what they give)
+NEAR_R_EQUAL = 0.10416899621486664          # v(q) - U_1 == r: kept, strictly
+NEAR_R_DROPPED = 0.10416898876428604        # the binary32 number before it: four ulps above r, dropped
+NEAR_R_SIDE = 64
+
+
+def _long(axis, extra=0.0):
+    """Two small balls 1023.485 apart along `axis`: 65536 samples on it, 34 on the other two (`extra` lengthens it)."""
+    at = [0.0, 0.0, 0.0]
+    at[axis] = LONG_DISTANCE + extra
+    return cc.assembly("long", [shapes.sphere(r=LONG_RADII[0]).make_part("big"), shapes.sphere(r=LONG_RADII[1]).make_part("small").translated(*at)])
+
+
+def _touching():
+    """Two boxes with the face x = 0 in common, on a plane of samples (corner x = -1 exactly, step 2^-4).  The right one
+    is a plain box where y > 0 and a large box cut off at x = 0 by a difference where y < 0: its w on the plane
+    is +0.0 there and -(+0.0) = -0.0 here, the left one's is +0.0."""
+    wide = 1 + ZERO_STEP / 2
+    left = shapes.box(wide, 1, 1).translated_x(-wide / 2)
+    plain = shapes.box(wide, 0.5, 1).translated(wide / 2, 0.25, 0)
+    cut = (shapes.box(2 * wide, 0.5, 1).translated(0, -0.25, 0) - shapes.box(2, 2, 2).translated_x(-1))
+    return cc.assembly("touching", [left.make_part("left"), shapes.union([plain, cut]).make_part("right")])
+
+
+def _near_r(t):
+    """A ball of radius 1 and one of radius 0.5 beside it, 0.05 apart at t = 0, moved along y by t: inside the large ball's
+    extent, so the lattice does not move with it."""
+    return cc.assembly("near_r", [shapes.sphere(r=1).make_part("a"), shapes.sphere(r=0.5).make_part("b").translated(1.55, float(t), 0)])
+
+
+NAN_SCALES = (1e-39, 1e-46)                 # a binary32 denormal; a scale that rounds to 0 in binary32
+NAN_SIDE = 64
+
+
+def _nans():
+    """Four parts: a unit ball placed so that the lattice's corner is -0.875 exactly (step 2^-4: index 14 of every axis is
+    the coordinate 0.0, and index 14 is the sample q of a child of side 4); a ball scaled by a denormal, whose field is a NaN
+    on the three planes through the origin (0 / denormal times infinity) and +inf elsewhere; a ball scaled by what rounds to
+    0, whose field is a NaN everywhere; a small ball beside them.  The pairs of `ghost` have no sample with two numbers,
+    those of `speck` have numbers (+inf) at some samples only, and (ball, bead) is an ordinary pair."""
+    return cc.assembly("nans", [shapes.sphere(r=1).make_part("ball").translated(3 / 32, 3 / 32, 3 / 32),
+                                shapes.sphere(r=1).scaled(NAN_SCALES[0]).make_part("speck"),
+                                shapes.sphere(r=1).scaled(NAN_SCALES[1]).make_part("ghost"),
+                                shapes.sphere(r=0.5).make_part("bead").translated(1.8, 0, 0)])
+
+
+Edge = collections.namedtuple("Edge", "build resolution side dense", defaults=(None, True))
+EDGES = {
+    "long_x": Edge(functools.partial(_long, 0), LONG_RESOLUTION, None, False),
+    "long_y": Edge(functools.partial(_long, 1), LONG_RESOLUTION, None, False),
+    "long_z": Edge(functools.partial(_long, 2), LONG_RESOLUTION, None, False),
+    "near_r_equal": Edge(functools.partial(_near_r, NEAR_R_EQUAL), 0.05, NEAR_R_SIDE),
+    "near_r_dropped": Edge(functools.partial(_near_r, NEAR_R_DROPPED), 0.05, NEAR_R_SIDE),
+    "touching": Edge(_touching, ZERO_STEP),
+    "far_boxes": Edge(lambda: _boxes().translated(*FAR), 0.05),
+    "far_random_2": Edge(lambda: mass_scenes.scene("random_2")[0].translated(*FAR), None),      # (at random_2's own resolution)
+    "nans": Edge(_nans, ZERO_STEP),
+    "nans_64": Edge(_nans, ZERO_STEP, NAN_SIDE),            # a second level: NaNs against a bound that is a number
+}
+
+
+@functools.lru_cache(maxsize=None)
+def edge_scene(name):
+    """(assembly, resolution, visible instances, corner, step, dims) of an edge scenario."""
+    asm = EDGES[name].build()
+    resolution = EDGES[name].resolution if EDGES[name].resolution is not None else mass_scenes.scene("random_2")[1]
+    instances = _instance_cells.visible(asm, resolution)
+    return (asm, resolution, instances) + tuple(_instance_cells.checked_lattice(instances, resolution))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_fields(name):
+    asm, resolution, instances, corner, step, dims = edge_scene(name)
+    return mass_scenes.dense_fields(instances, corner, step, dims)
+
+
+def edge_values(name):
+    """The values the reference traversal of an edge scenario reads: its dense fields, or the oracle at the samples where
+    the lattice is too long to evaluate densely."""
+    asm, resolution, instances, corner, step, dims = edge_scene(name)
+    return field_values(edge_fields(name)) if EDGES[name].dense else point_values(instances, corner, step)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(name):
+    """(Dense or None, Traversal) of an edge scenario, computed once and shared; nobody changes it."""
+    asm, resolution, instances, corner, step, dims = edge_scene(name)
+    traversal = traverse(edge_values(name), len(instances), dims, step, EDGES[name].side)
+    return (dense(edge_fields(name)) if EDGES[name].dense else None), traversal
 
 
 def report_keys(report):

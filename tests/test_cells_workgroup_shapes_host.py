@@ -51,14 +51,23 @@ def test_the_workgroup_rule():
         hi.cells_lds(2560)
 
 
-# scene -> (distance_only, lane_bytes, lanes of every kernel but the three with 4 bytes per instance, lanes of those three)
+# scene -> (distance_only, lane_bytes, lanes of every kernel but the six with 4 bytes per instance, lanes of those six)
 FIGURES = {
     "heavy_pair": (0, 208, L128, L128),
     "heavy_plain": (1, 216, L128, L128),
     "heavy_pair25": (0, 400, L64, L64),
     "heavy_64": (0, 208, L128, L64),
 }
-PER_INSTANCE = {"clearance leaf", "clearance witness", "section tiles with distance"}
+PER_INSTANCE = {"clearance leaf", "clearance witness", "section tiles with distance",
+                "separation cells", "separation leaf", "separation witness"}
+# the kernels of separation() and assembly_voxels(), spelled out for every scene from the rule (208 + 16 and 216 + 16 B per
+# lane: 128 lanes; 208 + 256: 64; 400 and more: 64)
+NEW_KERNELS = {
+    "heavy_pair": {"separation cells": L128, "separation leaf": L128, "separation witness": L128, "voxel cells": L128, "voxel leaf": L128},
+    "heavy_plain": {"separation cells": L128, "separation leaf": L128, "separation witness": L128, "voxel cells": L128, "voxel leaf": L128},
+    "heavy_pair25": {"separation cells": L64, "separation leaf": L64, "separation witness": L64, "voxel cells": L64, "voxel leaf": L64},
+    "heavy_64": {"separation cells": L64, "separation leaf": L64, "separation witness": L64, "voxel cells": L128, "voxel leaf": L128},
+}
 
 
 def expected_lanes(name):
@@ -73,7 +82,10 @@ def test_lanes_of_every_kernel(name):
     assert hi.table_figures(instances) == FIGURES[name][:2]
     assert len(instances) == (64 if name == "heavy_64" else 4)
     assert hi.lanes_table(instances) == expected_lanes(name)
-    assert set(hi.kernel_extras(len(instances))) == set(expected_lanes(name)) and len(expected_lanes(name)) == 17
+    assert set(hi.kernel_extras(len(instances))) == set(expected_lanes(name)) and len(expected_lanes(name)) == 22
+    assert {k: expected_lanes(name)[k] for k in NEW_KERNELS[name]} == NEW_KERNELS[name]
+    extras = hi.kernel_extras(len(instances))
+    assert [extras[k] for k in sorted(NEW_KERNELS[name])] == [4 * len(instances)] * 3 + [0, 0]
 
 
 def test_every_kernel_reaches_128_and_64_lanes_through_a_genuine_register_file():
@@ -145,6 +157,52 @@ def test_removing_the_heavy_parts_changes_every_reference(name):
     assert light["layers"] != hi.layers_reference(name).layer_counts.tolist()
     assert light["meshes"] != hi.meshes_reference(name).counts.tolist()
     assert light["mass"] != hi.mass_reference(name).sums
+    assert light["voxels"] != hi.voxels_reference(name).counts
+    (light_dense, light_traversal), (dense, traversal) = light["separation"], hi.separation_reference(name)
+    assert not numpy.array_equal(light_dense.keys, dense.keys) and not numpy.array_equal(light_traversal.keys, traversal.keys)
+    assert light_traversal.evaluations != traversal.evaluations
+
+
+@pytest.mark.parametrize("name", sorted(hi.SCENES))
+def test_the_separation_traversal_of_a_heavy_scene_is_the_dense_minimum(name):
+    """The branch and bound assumes distances of Lipschitz constant at most 1 (codecad_amd/separation.py): the scaled knots
+    keep it, on every scene the traversal loses no minimum and no witness, and a heavy part's pairs are among them."""
+    dense, traversal = hi.separation_reference(name)
+    n = len(hi.instances_of(name))
+    assert numpy.array_equal(dense.keys, traversal.keys) and dense.witness == traversal.witness
+    assert set(dense.witness) == {(i, j) for i in range(n) for j in range(i + 1, n)}
+    heavy = set(hi.HEAVY_INDEX[name])
+    mixed = [pair for pair in dense.witness if (pair[0] in heavy) != (pair[1] in heavy)]
+    assert any(dense.keys[pair] < 0x80000000 for pair in mixed) and any(dense.keys[pair] > 0x80000000 for pair in mixed)   # overlapping, apart
+    assert traversal.level_rows[-1] > 0 and traversal.evaluations > 0
+
+
+def test_the_voxel_references_of_the_heavy_scenes_write_the_dense_volume():
+    for name in sorted(hi.SCENES):
+        for retire in (True, False):
+            ref = hi.voxels_reference(name, retire)
+            assert numpy.array_equal(ref.written, ref.ids) and ref.traversal_counts == ref.counts and ref.premise_broken == 0
+            assert all(ref.counts[k] > 0 for k in hi.HEAVY_INDEX[name])
+
+
+def test_the_regimes_a_larger_register_file_reaches():
+    """random_5 (12 instances, 32 B per lane) starts at 256 lanes and reaches all four; solids64's separation (64 instances:
+    20 + 256 B per lane) starts at 128 lanes and reaches the three below it; the mass scene `blend` all four."""
+    import separation_scenes
+    # neither scene of few instances lists two levels above the finest one from its own top side, 16: the padded run forces 256
+    for name in ("random_5", "gears"):
+        assert separation_scenes.traversal_reference(name).side == 16 and len(separation_scenes.traversal_reference(name).level_rows) == 1
+    forced = separation_scenes.traversal_reference("random_5", 256)
+    assert len(forced.level_rows) == 3 and all(rows > 0 for rows in forced.level_rows)
+    five, solids, blend = (mass_scenes.scene(name)[2] for name in ("random_5", "solids64", "blend"))
+    assert hi.table_figures(five) == (0, 32) and len(five) == 12 and hi.regimes_of(32, 48) == hi.REGIMES
+    assert hi.table_figures(solids) == (1, 20) and len(solids) == 64 and hi.cells_lanes(20, 256) == 128
+    assert hi.regimes_of(20, 256) == ["64 lanes", "64 lanes above 64 KiB", "the largest LDS"]
+    assert hi.cells_lds(2292, 256) == 64 * 2548 + 128 <= hi.MAX_LDS        # solids64's largest: 20 + 2272 B of registers per lane
+    with pytest.raises(ValueError):
+        hi.cells_lds(2308, 256)
+    assert hi.table_figures(blend) == (0, 32) and hi.regimes_of(32, 0) == hi.REGIMES
+    assert hi.regimes_of(400, 0) == ["64 lanes above 64 KiB", "the largest LDS"] and hi.regimes_of(1600, 0) == ["the largest LDS"]
 
 
 def test_lane_bytes_that_are_no_multiple_of_four_are_refused():

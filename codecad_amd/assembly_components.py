@@ -128,10 +128,17 @@ def assembly_components(asm, resolution, of=EMPTY_SPACE, local=True, initial_com
 
     if volume is None:
         return report(numpy.full(shape, NONE, numpy.uint32), [], 0)
+    labels, rows, runs = _label_volume(volume, shape, int(of == SOLID), local, initial_components)
+    return report(labels, _components(rows, voxels.corner, voxels.step), runs)
+
+
+def _label_volume(volume, shape, solid, local, initial_components):
+    """The labelling from a uint8[nx, ny, pz] volume on the device on, for every caller that has one (thin_walls.py labels its
+    thin ids with it): S is the samples != 255 (`solid` = 1) or == 255 of the lattice `shape` -> (labels uint32[nx, ny, nz],
+    the table's used rows, how often the statistics pass ran).  `volume` is released here, as soon as no kernel reads it."""
     lib, queue = hip_manager.lib, hip_manager.queue
     nx, ny, pz = volume.shape
     dims = (ctypes.c_uint32 * 3)(*shape)
-    solid = int(of == SOLID)
     labels = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
     check(lib.hu_components_local(volume.device_ptr, labels.device_ptr, dims, pz, solid, int(bool(local)), queue.handle),
           "hu_components_local")
@@ -156,7 +163,7 @@ def assembly_components(asm, resolution, of=EMPTY_SPACE, local=True, initial_com
     check(lib.hu_components_finish(labels.device_ptr, dims, pz, queue.handle), "hu_components_finish")
     out = numpy.ascontiguousarray(labels.read()[:, :, :shape[2]])
     labels.release()
-    return report(out, _components(rows[1:1 + count], voxels.corner, voxels.step), runs)
+    return out, rows[1:1 + count], runs
 
 
 def cavities(asm, resolution, **kw):

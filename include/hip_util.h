@@ -445,6 +445,34 @@ int hu_components_stats(const void* volume_dev, void* labels_dev, const uint32_t
                         int assign_slots, uint32_t* counter_dev, void* table_dev, uint32_t capacity, void* stream);
 int hu_components_finish(void* labels_dev, const uint32_t dims[3], uint32_t pitch, void* stream);
 
+/* ---- capped squared distance transforms of the part-id volume (codecad_amd/thin_walls.py) ------
+ * A pass of the separable transform over uint16[dims[0]][dims[1]][pitch] volumes of the pitch of the id volume ids_dev (still
+ * on the device), a capped min-plus stencil along one axis:
+ *     out(i) = min(cap, min over |k| <= K of in(i + k) + k * k),
+ * a tap outside the lattice counting as `outside`.  S is the samples with id != 255 (of == HU_THICKNESS_SOLID) or id == of
+ * (of <= 63).  The padding z in [dims[2], pitch) of any volume is neither read nor written.  lds != 0 stages the inputs of a
+ * workgroup in LDS, lds == 0 reads every tap from global memory: the same bytes.  Asynchronous; in and out must not overlap.
+ * hu_thickness_pass_z: along z.  depth_dev == NULL (transform 1): in = S ? cap : 0 from ids_dev, outside = 0.  Else
+ *   (transform 2): in = depth_dev[...] > radius_sq ? 0 : cap, outside = cap; ids_dev is not read.
+ * hu_thickness_pass_axis: along y (axis 1) or x (axis 0), in_dev -> out_dev.  A workgroup takes 64 consecutive z (along x: 64
+ *   consecutive entries of a (y, z) plane) times `tile` positions along the axis; with lds != 0, tile + 2 K must not exceed
+ *   HU_THICKNESS_LDS_ROWS rows of 128 bytes.  finish == 1: also adds to counts_dev[p] (64 uint64, the caller's zeros) the
+ *   samples of id p whose result reaches the cap -- the core, after the x pass of transform 1 (cap = R2 + 1).  finish == 2:
+ *   out_dev is not written; thin_dev (uint8, the layout of ids_dev) <- the id of a sample of S whose result reaches the cap
+ *   (cap = C2 + 1: no core within C2), 255 elsewhere, counted into counts_dev[p] likewise.  One atomic per accumulator and
+ *   wavefront.
+ * Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL pointers, a pitch that is no multiple of 16 or
+ * below dims[2], dims of 0 or above 65536, cap above 65535, K above HU_THICKNESS_MAX_K, an `of` above 63 that is not
+ * HU_THICKNESS_SOLID. */
+#define HU_THICKNESS_SOLID 255
+#define HU_THICKNESS_MAX_K 255
+#define HU_THICKNESS_LDS_ROWS 256
+int hu_thickness_pass_z(const void* ids_dev, const void* depth_dev, void* out_dev, const uint32_t dims[3], uint32_t pitch,
+                        uint32_t of, uint32_t radius_sq, uint32_t K, uint32_t cap, int lds, void* stream);
+int hu_thickness_pass_axis(const void* in_dev, void* out_dev, const void* ids_dev, void* thin_dev, uint64_t* counts_dev,
+                           const uint32_t dims[3], uint32_t pitch, int axis, uint32_t of, uint32_t K, uint32_t cap,
+                           uint32_t outside, int finish, uint32_t tile, int lds, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

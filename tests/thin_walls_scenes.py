@@ -1,0 +1,241 @@
+"""The scenarios and the CPU reference of the thin-wall tests (test_thin_walls_host.py proves on the CPU that each scenario
+holds the edge it is there for; test_gpu_thin_walls.py runs them on the device).
+
+`reference_thin(ids, of, r2, c2, n)` (n instances) is written from the definitions in codecad_amd/thin_walls.py alone, NOT separably: it
+starts from the dense part ids of assembly_voxels_scenes.reference_voxels, pads S by the radius with background, and
+  * E is the AND of S shifted by every offset o with |o|^2 <= R2,
+  * depth_sq is the minimum of |o|^2 over the same offsets at which the shifted S is background, R2 + 1 where there is none,
+  * O is S AND the OR of E shifted by every offset with |o|^2 <= C2,
+  * the regions come from assembly_components_scenes.reference_components' flood fill on the thin ids.
+An offset that leaves the lattice along an axis from every sample (|o_i| >= dims_i) only ever meets background: such offsets
+are clipped to |o_i| = dims_i, which meets the same background at a smaller |o|^2 -- that keeps K = 255 on a lattice of
+13 x 9 x 11 affordable and changes no minimum and no AND.
+
+`separable_thin` is the second way: three capped 1D min-plus passes in NumPy per transform.
+
+The scenarios are blocks in SAMPLE units at step 1/16, built with assembly_components_scenes._cut and _box.
+"""
+import collections
+import functools
+import itertools
+
+import numpy
+
+import codecad_amd as cc
+from codecad_amd import _instance_cells
+
+import assembly_components_scenes as comp
+import assembly_voxels_scenes as voxels
+from assembly_components_scenes import _cut, _box, STEP, SOLID, NONE, EMPTY
+
+MIXED, ALL_THIN, NONE_THIN = "mixed", "all thin", "none thin"
+
+Reference = collections.namedtuple("Reference", "ids in_set depth_sq core cover thin_ids core_counts thin_counts regions labels")
+Case = collections.namedtuple("Case", "name scene of r2 c2 expect")
+
+
+# ---- the reference ----------------------------------------------------------------------------------------------------
+
+def offsets(limit_sq, dims):
+    """int64[m, 3]: every offset with |o|^2 <= limit_sq, |o_i| clipped to dims_i (the module's docstring), and their |o|^2."""
+    k = int(numpy.floor(numpy.sqrt(limit_sq)))
+    while (k + 1) ** 2 <= limit_sq:
+        k += 1
+    while k * k > limit_sq:
+        k -= 1
+    axes = [numpy.arange(-min(k, int(d)), min(k, int(d)) + 1, dtype=numpy.int64) for d in dims]
+    o = numpy.stack(numpy.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+    sq = (o * o).sum(axis=1)
+    keep = sq <= limit_sq
+    return o[keep], sq[keep]
+
+
+def _shifted(padded, pad, o, shape):
+    """padded[p + o] for every p of the lattice."""
+    return padded[tuple(slice(int(pad[a] + o[a]), int(pad[a] + o[a]) + shape[a]) for a in range(3))]
+
+
+def in_set_of(ids, of):
+    return (ids != EMPTY) if of == SOLID else (ids == of)
+
+
+def reference_thin(ids, of, r2, c2, n):
+    shape = ids.shape
+    s = in_set_of(ids, of)
+    pad = [min(int(numpy.sqrt(c2)) + 1, d) for d in shape]
+    padded = numpy.pad(s, [(p, p) for p in pad])                                  # background all around
+    core = s.copy()
+    depth = numpy.full(shape, r2 + 1, dtype=numpy.int64)
+    for o, sq in zip(*offsets(r2, shape)):
+        there = _shifted(padded, pad, o, shape)
+        core &= there
+        depth = numpy.where(there, depth, numpy.minimum(depth, sq))
+    depth = numpy.where(s, depth, 0)
+    assert numpy.array_equal(core, depth > r2)                                    # the two statements of E agree
+    padded_core = numpy.pad(core, [(p, p) for p in pad])
+    reached = numpy.zeros(shape, dtype=bool)
+    for o, sq in zip(*offsets(c2, shape)):
+        reached |= _shifted(padded_core, pad, o, shape)
+    cover = s & reached
+    thin = s & ~cover
+    thin_ids = numpy.where(thin, ids, EMPTY).astype(numpy.uint8)
+    found = comp.reference_components(thin_ids, SOLID)
+    for a in (depth, core, cover, thin_ids):
+        a.setflags(write=False)
+    return Reference(ids, s, depth.astype(numpy.uint16), core, cover, thin_ids, [int((core & (ids == k)).sum()) for k in range(n)],
+                     [int((thin & (ids == k)).sum()) for k in range(n)], found.components, found.labels)
+
+
+def min_plus_1d(f, axis, K, cap, outside):
+    """out(i) = min(cap, min over |k| <= K of f(i + k) + k^2) along `axis`, `outside` beyond the ends."""
+    f = numpy.moveaxis(f.astype(numpy.int64), axis, 0)
+    n = f.shape[0]
+    reach = min(K, n)                 # a tap further out than n reads `outside` from everywhere: a nearer tap reads it too
+    padded = numpy.concatenate([numpy.full((reach,) + f.shape[1:], outside, numpy.int64), f,
+                                numpy.full((reach,) + f.shape[1:], outside, numpy.int64)])
+    out = numpy.full(f.shape, cap, dtype=numpy.int64)
+    for k in range(-reach, reach + 1):
+        out = numpy.minimum(out, padded[reach + k:reach + k + n] + k * k)
+    return numpy.moveaxis(out, 0, axis)
+
+
+def isqrt(v):
+    k = int(numpy.sqrt(v))
+    while (k + 1) ** 2 <= v:
+        k += 1
+    while k * k > v:
+        k -= 1
+    return k
+
+
+def separable_thin(ids, of, r2, c2):
+    """(depth_sq, core, thin) by three capped passes per transform."""
+    s = in_set_of(ids, of)
+    d = numpy.where(s, r2 + 1, 0)
+    for axis in (2, 1, 0):
+        d = min_plus_1d(d, axis, isqrt(r2), r2 + 1, 0)
+    core = d > r2
+    e = numpy.where(core, 0, c2 + 1)
+    for axis in (2, 1, 0):
+        e = min_plus_1d(e, axis, isqrt(c2), c2 + 1, c2 + 1)
+    return d, core, s & (e > c2)
+
+
+# ---- the scenarios ----------------------------------------------------------------------------------------------------
+
+PLATE = 16                      # the other two sides of a slab
+SLABS = ((1, 2), (1, 3), (2, 4), (2, 5), (3, 6), (3, 7))        # (K1, w)
+BAR_R2 = (0, 1, 2, 3, 4, 5, 8, 9)
+BARS = (11, 3, 12)
+RIB = (24, 12, 16)
+WEDGE = (8, 12, 16)
+RAGGED = (13, 9, 11)
+TWO = (12, 12, 12)
+
+
+def _one(name, shape):
+    return cc.assembly(name, [shape.make_part(name)])
+
+
+def _slab(axis, w):
+    n = [PLATE] * 3
+    n[axis] = w
+    return _one("slab", _box(n, (0, 0, 0), n))
+
+
+def _bars():
+    """A 3 x 3 and a 2 x 2 bar, 12 long, 6 samples apart: further than any radius of BAR_R2 reaches."""
+    return cc.assembly("bars", [_box(BARS, (0, 0, 0), (3, 3, 12)).make_part("three"), _box(BARS, (9, 0, 0), (11, 2, 12)).make_part("two")])
+
+
+def _cuboid(sides):
+    return _one("cuboid", _box(sides, (0, 0, 0), sides))
+
+
+def _rib():
+    """A body of 12 x 12 x 10 samples carrying a rib 2 wide and 6 high on top and a floor 2 thick beside it."""
+    return _one("casting", _cut(RIB, [((12, 0, 2), (24, 12, 16)), ((0, 0, 10), (5, 12, 16)), ((7, 0, 10), (12, 12, 16))]))
+
+
+def _wedge():
+    """Steps 2, 4, 6 and 8 samples wide, 4 high each: only the narrow end is thin."""
+    holes = []
+    for j in range(3):
+        holes += [((0, 0, 4 * j), (3 - j, 12, 4 * j + 4)), ((5 + j, 0, 4 * j), (8, 12, 4 * j + 4))]
+    return _one("wedge", _cut(WEDGE, holes))
+
+
+def _ragged():
+    """13 x 9 x 11 samples, no multiple of any tile, pz = 16 > nz: a block that reaches every border and z = nz - 1, with a
+    slot 5 deep cut into its top that leaves two walls of 2 and of 3 samples."""
+    return _one("ragged", _cut(RAGGED, [((2, 0, 6), (10, 9, 11))]))
+
+
+def _plate_on_block():
+    """A plate of 2 samples (part 0) glued to a block of 10 (part 1)."""
+    return cc.assembly("glued", [_box(TWO, (0, 0, 0), (2, 12, 12)).make_part("plate"), _box(TWO, (2, 0, 0), (12, 12, 12)).make_part("block")])
+
+
+def _pin_in_block():
+    """A pin of 2 x 2 samples (part 0) pressed through a block (part 1): the pin owns what both contain."""
+    return cc.assembly("pressed", [_box(TWO, (5, 5, 0), (7, 7, 12)).make_part("pin"), _box(TWO, (0, 0, 0), TWO).make_part("block")])
+
+
+SCENES = {"bars": _bars, "rib": _rib, "wedge": _wedge, "ragged": _ragged, "plate_on_block": _plate_on_block,
+          "pin_in_block": _pin_in_block, "shell": comp._shell,
+          "cuboid_5": functools.partial(_cuboid, (5, 5, 5)), "cuboid_4": functools.partial(_cuboid, (5, 4, 5))}
+for _axis, (_k, _w) in itertools.product(range(3), SLABS):
+    SCENES["slab_%s_%d" % ("xyz"[_axis], _w)] = functools.partial(_slab, _axis, _w)
+
+CASES = []
+for _axis, (_k, _w) in itertools.product(range(3), SLABS):
+    CASES.append(Case("slab_%s_k%d_w%d" % ("xyz"[_axis], _k, _w), "slab_%s_%d" % ("xyz"[_axis], _w), SOLID, _k * _k, 3 * _k * _k,
+                      ALL_THIN if (-(-_w // 2)) ** 2 <= _k * _k else NONE_THIN))
+for _r2, _factor in itertools.product(BAR_R2, (1, 3)):
+    if _r2 == 0 and _factor == 3:
+        continue                                                           # (C2 = 0 either way)
+    CASES.append(Case("bars_r%d_c%d" % (_r2, _factor * _r2), "bars", SOLID, _r2, _factor * _r2,
+                      NONE_THIN if _r2 == 0 else MIXED if _r2 < 4 else ALL_THIN))
+CASES += [
+    Case("cuboid_5", "cuboid_5", SOLID, 4, 12, NONE_THIN),                 # every side 2 * K1 + 1
+    Case("cuboid_4", "cuboid_4", SOLID, 4, 12, ALL_THIN),                  # 2 * K1 on one axis: no core at all
+    Case("rib", "rib", SOLID, 4, 12, MIXED),
+    Case("rib_r0", "rib", SOLID, 0, 0, NONE_THIN),                         # R2 = 0: E = S
+    Case("wedge", "wedge", SOLID, 4, 12, MIXED),
+    Case("ragged", "ragged", SOLID, 2, 6, MIXED),
+    Case("ragged_far", "ragged", SOLID, 400, 65534, ALL_THIN),             # K1 = 20 > every dimension, the largest C2: K2 = 255
+    Case("glued_solid", "plate_on_block", SOLID, 4, 12, NONE_THIN),
+    Case("glued_plate", "plate_on_block", 0, 4, 12, ALL_THIN),
+    Case("glued_block", "plate_on_block", 1, 4, 12, NONE_THIN),
+    Case("pressed_solid", "pin_in_block", SOLID, 4, 12, NONE_THIN),
+    Case("pressed_pin", "pin_in_block", 0, 4, 12, ALL_THIN),
+    Case("pressed_block", "pin_in_block", 1, 4, 12, NONE_THIN),
+    Case("shell", "shell", SOLID, 16, 48, ALL_THIN),
+]
+BY_NAME = {c.name: c for c in CASES}
+NAMES = [c.name for c in CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    """(assembly, resolution, visible instances, corner, step, dims) of a scene."""
+    asm = SCENES[name]()
+    instances = _instance_cells.visible(asm, STEP)
+    corner, step, dims = _instance_cells.checked_lattice(instances, STEP)
+    return asm, STEP, instances, corner, step, dims
+
+
+@functools.lru_cache(maxsize=None)
+def part_ids(name):
+    """The dense part ids of a scene: assembly_voxels_scenes.reference_voxels', computed once."""
+    asm, resolution, instances, corner, step, dims = scene(name)
+    ids = voxels.reference_voxels(instances, corner, step, dims, True).ids
+    ids.setflags(write=False)
+    return ids
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case):
+    """The Reference of a case (by name), computed once and shared; nobody changes it."""
+    c = BY_NAME[case]
+    return reference_thin(part_ids(c.scene), c.of, c.r2, c.c2, len(scene(c.scene)[2]))

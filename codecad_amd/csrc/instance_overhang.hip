@@ -1,0 +1,317 @@
+// codecad_amd/csrc/instance_overhang.hip
+//
+// WHAT A PRINT DIRECTION LEAVES IN THE AIR, on the part-id volume of an assembly, for codecad_amd/overhangs.py.  The build
+// direction is s * e, e the unit index vector of `axis` and s = +1 (`up`) or -1; "below p" is p - s e, the LAYER of p is
+// h(p) = p[axis] (s > 0) or n_axis - 1 - p[axis]; h0 is the least layer that holds a sample of S.  All integers, exact.
+//   O (overhang): p in S, h(p) > h0, and p - s e + n not in S for every lateral offset n = (u, v), u^2 + v^2 <= reach_sq;
+//   P (support):  p in the lattice, not in S, h(p) >= h0, and the nearest sample of S above p on its line is in O: its HOLDER;
+//   L (landing):  q in S with q + s e in P;  PLATE LANDINGS: the samples of P with h = h0.
+// Nothing outside the lattice is in S, and no byte of the padding z in [nz, pitch) is read or written.
+//
+// LANES LIE ALONG z IN EVERY KERNEL: a wavefront's global accesses are runs of consecutive bytes.
+//   k_over_first: a UNIT is 64 consecutive z of one (x, y) column, one ballot; a wavefront walks units a grid apart, keeps
+//     n_axis - (the least layer it saw a sample of S in) and ends with at most one atomicMax of that into the DEPTH WORD (the
+//     caller's zero), skipped when the word already holds as much -- it only ever grows, so a stale read costs an atomic and
+//     never a result.  h0 = n_axis - word; 0 stands for an empty S.  The later kernels read the word, the host does not wait
+//     in between.
+//   k_over_mark: the same units, walked the same way.  A lane of S above h0 taps the layer below, the sample straight below
+//     first, then the other offsets of N (at most 24) until some tap is in S; the wavefront leaves the loop, between two rows
+//     of offsets, when no lane is still open.  Writes overhang_ids (the id on O, else 255) and counts O per part.
+//   k_over_columns<false> (axis 0 or 1): a wavefront owns 64 consecutive z of one line along the axis and walks its layers
+//     from the top of the build direction down; a lane carries its holder (255: closed) and whether the sample above was in
+//     P in registers.  Below h0 everything is closed.
+//   k_over_columns<true> (axis 2): the line is the wavefront itself; a unit is an (x, y) column, walked like the units above.
+//     The wavefront walks the words of the column from the top of the build direction down, takes the ballots of S and of O (bit-reversed when s < 0, so that a higher bit is always
+//     ABOVE), finds for every lane the nearest set bit of S above it in the word and fetches that lane's id by a cross-lane
+//     read; where the word holds no S above the lane the CARRY from the word above decides: the holder left open there, and
+//     whether its last sample was in S.  A column so closes and reopens inside a word, crosses words without any solid and
+//     ends at h0 inside one.
+//   Both write support_ids (the holder's id on P, else 255) and landing_ids (the id on L, else 255) and count P per holder,
+//   L per owner and the plate landings: lane p of a wavefront gathers the count of part p over everything the wavefront walks
+//   and adds it once at the end -- one atomic per accumulator and wavefront, and at most 8192 wavefronts where units are walked.
+// No kernel has a private array, LDS or scratch; byte offsets are 64-bit.  The entry points are at the end of this file.
+#include "instance_cells.hpp"
+
+using namespace hu_cells;
+
+namespace {
+
+constexpr uint32_t kEmpty = 255u;                       // instance_voxels.hip: the id of a sample inside no part
+constexpr uint32_t kSolid = HU_OVERHANG_SOLID;          // of: S is id != 255; any other of (<= 63): S is id == of
+constexpr uint32_t kMaxReach = HU_OVERHANG_MAX_REACH_SQ;
+static_assert(kSolid == kEmpty && kMaxReach == 8u, "include/hip_util.h");
+
+struct OverArgs {
+    const uint8_t* ids;                 // uint8[nx][ny][pitch]
+    uint8_t* over;                      // k_over_mark writes it, k_over_columns reads it
+    uint8_t* support;
+    uint8_t* landing;
+    uint32_t* word;                     // the depth word: n_axis - h0, 0 while S is empty
+    unsigned long long* counts;         // 64 accumulators (mark: O); 64 + 64 + 1 (columns: P, L, the plate landings)
+    uint32_t nx, ny, nz, pitch;
+    uint32_t axis, up, reach_sq, of;
+    uint32_t na;                        // dims[axis]
+    uint32_t segments;                  // ceil(nz / 64)
+};
+
+__device__ __forceinline__ bool in_set(uint32_t id, uint32_t of) { return of == kSolid ? id != kEmpty : id == of; }
+
+// lane p's `mine` += the lanes that count and whose id is p, for every id present (wave-uniform loop; instance_thickness.hip)
+__device__ __forceinline__ void gather_counts(bool counted, uint32_t id, uint32_t lane, unsigned long long& mine)
+{
+    for (uint64_t todo = __ballot(counted); todo != 0ull;) {
+        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)__builtin_ctzll(todo));
+        const uint64_t b = __ballot(counted && id == p);
+        todo &= ~b;
+        if (lane == (p & 63u)) mine += (unsigned long long)__popcll(b);
+    }
+}
+
+// 64 consecutive z of one (x, y) column: the unit of a wavefront of k_over_first and k_over_mark (all wave-uniform)
+struct Unit {
+    uint32_t x, y, z0;
+    size_t base;
+};
+__device__ __forceinline__ Unit unit_of(const OverArgs& a, uint64_t unit)
+{
+    const uint64_t column = unit / a.segments;
+    Unit u;
+    u.z0 = ((uint32_t)(unit - column * a.segments)) << 6;
+    u.x = (uint32_t)(column / a.ny), u.y = (uint32_t)(column - (uint64_t)u.x * a.ny);
+    u.base = (size_t)column * a.pitch;
+    return u;
+}
+
+// A wavefront takes the units w, w + W, w + 2 W, ... of `units`, W the wavefronts of the grid (wave-uniform): it gathers over
+// all of them and adds to an accumulator once, however many units the lattice has.
+#define FOR_UNITS(unit, units) \
+    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); unit < (units); unit += (uint64_t)gridDim.x * 4u)
+
+__device__ __forceinline__ uint32_t layer_of(const OverArgs& a, uint32_t along) { return a.up ? along : a.na - 1u - along; }
+
+__global__ void __launch_bounds__(256) k_over_first(const OverArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t depth = 0u;                                              // wave-uniform: n_axis - the least layer seen
+    FOR_UNITS(unit, (uint64_t)a.nx * a.ny * a.segments) {
+        const Unit u = unit_of(a, unit);
+        const uint32_t z = u.z0 + lane;
+        const bool in = z < a.nz && in_set(a.ids[u.base + z], a.of);
+        const uint64_t m = __ballot(in);
+        if (m == 0ull) continue;                                      // wave-uniform
+        // the least layer among the unit's samples of S: along z the lowest set lane (up) or the highest
+        const uint32_t along = a.axis == 0u ? u.x : a.axis == 1u ? u.y
+                             : u.z0 + (a.up ? (uint32_t)__builtin_ctzll(m) : 63u - (uint32_t)__builtin_clzll(m));
+        depth = max(depth, a.na - layer_of(a, along));                // >= 1
+    }
+    if (lane == 0u && __atomic_load_n(a.word, __ATOMIC_RELAXED) < depth) atomicMax(a.word, depth);
+}
+
+__global__ void __launch_bounds__(256) k_over_mark(const OverArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t h0 = a.na - uniform(*a.word);
+    unsigned long long mine = 0ull;
+    const int s = a.up ? 1 : -1;
+    const int reach = a.reach_sq >= 4u ? 2 : a.reach_sq >= 1u ? 1 : 0;
+    FOR_UNITS(unit, (uint64_t)a.nx * a.ny * a.segments) {
+        const Unit u = unit_of(a, unit);
+        const uint32_t z = u.z0 + lane;
+        const bool active = z < a.nz;
+        const uint32_t id = active ? a.ids[u.base + z] : kEmpty;
+        const uint32_t h = layer_of(a, a.axis == 0u ? u.x : a.axis == 1u ? u.y : z);
+        // is the sample below, moved by (du, dv) on the other two axes, in S?  Nothing outside the lattice is.
+        auto tap = [&](int du, int dv) -> bool {
+            const int tx = (int)u.x + (a.axis == 0u ? -s : du);
+            const int ty = (int)u.y + (a.axis == 0u ? du : a.axis == 1u ? -s : dv);
+            const int tz = (int)z + (a.axis == 2u ? -s : dv);
+            if (tx < 0 || tx >= (int)a.nx || ty < 0 || ty >= (int)a.ny || tz < 0 || tz >= (int)a.nz) return false;
+            return in_set(a.ids[((size_t)(uint32_t)tx * a.ny + (uint32_t)ty) * a.pitch + (uint32_t)tz], a.of);
+        };
+        bool open = active && in_set(id, a.of) && h > h0;             // in S above the plate, and no tap in S so far
+        if (open && tap(0, 0)) open = false;
+        for (int du = -reach; du <= reach && __ballot(open) != 0ull; ++du)      // wave-uniform: a row of offsets at a time
+            for (int dv = -reach; dv <= reach; ++dv) {
+                if ((uint32_t)(du * du + dv * dv) > a.reach_sq || (du == 0 && dv == 0)) continue;
+                if (open && tap(du, dv)) open = false;
+            }
+        if (active) a.over[u.base + z] = (uint8_t)(open ? id : kEmpty);
+        gather_counts(open, id, lane, mine);
+    }
+    if (mine != 0ull) atomicAdd(&a.counts[lane], mine);
+}
+
+// what a wavefront of k_over_columns has gathered goes to the accumulators: P per holder, L per owner, the plate landings
+__device__ __forceinline__ void add_counts(const OverArgs& a, uint32_t lane, unsigned long long held, unsigned long long landed,
+                                           unsigned long long plate)
+{
+    if (held != 0ull) atomicAdd(&a.counts[lane], held);
+    if (landed != 0ull) atomicAdd(&a.counts[64u + lane], landed);
+    if (lane == 0u && plate != 0ull) atomicAdd(&a.counts[128u], plate);
+}
+
+template <bool ALONG_Z>
+__global__ void __launch_bounds__(256) k_over_columns(const OverArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t h0 = a.na - uniform(*a.word);
+    unsigned long long held = 0ull, landed = 0ull, plate = 0ull;
+    if (!ALONG_Z) {
+        // a line along x is one y, along y one x; 64 consecutive z of it, one such unit a wavefront
+        const uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6);
+        const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
+        if (unit >= (uint64_t)lines * a.segments) return;
+        const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
+        const bool active = z < a.nz;
+        const size_t stride = a.axis == 0u ? (size_t)a.ny * a.pitch : (size_t)a.pitch;
+        const size_t base = (a.axis == 0u ? (size_t)line * a.pitch : (size_t)line * a.ny * a.pitch) + z;
+        uint32_t holder = kEmpty;                                     // the id of the overhang that holds this lane's column up
+        bool above_held = false;                                      // the sample above is in P
+        for (uint32_t t = 0u; t < a.na; ++t) {                        // wave-uniform: from the top layer down
+            const uint32_t h = a.na - 1u - t;
+            const size_t at = base + (size_t)(a.up ? h : t) * stride;
+            const uint32_t id = active ? a.ids[at] : kEmpty;
+            const bool over = active && a.over[at] != kEmpty;
+            const bool in = active && in_set(id, a.of);
+            if (h < h0) holder = kEmpty, above_held = false;          // (no sample of S is below h0)
+            const bool lands = in && above_held;
+            if (in) holder = over ? id : kEmpty;
+            const bool is_held = active && !in && holder != kEmpty;
+            above_held = is_held;
+            if (active) {
+                a.support[at] = (uint8_t)(is_held ? holder : kEmpty);
+                a.landing[at] = (uint8_t)(lands ? id : kEmpty);
+            }
+            gather_counts(is_held, holder, lane, held);
+            gather_counts(lands, id, lane, landed);
+            if (h == h0) plate += (unsigned long long)__popcll(__ballot(is_held));
+        }
+    } else FOR_UNITS(unit, (uint64_t)a.nx * a.ny) {                   // a unit is a whole (x, y) column
+        const size_t base = (size_t)unit * a.pitch;
+        const uint32_t v = a.up ? lane : 63u - lane;                  // the lane's position in the word: a higher one is above
+        uint32_t carry_holder = kEmpty;                               // wave-uniform: the column open at the word's top
+        bool carry_in = false;                                        // ... and whether the sample above the word is in S
+        for (uint32_t k = 0u; k < a.segments; ++k) {                  // wave-uniform: from the top word down
+            const uint32_t z = ((a.up ? a.segments - 1u - k : k) << 6) + lane;
+            const bool active = z < a.nz;
+            const uint32_t id = active ? a.ids[base + z] : kEmpty;
+            const bool in = active && in_set(id, a.of);
+            uint64_t set = __ballot(in), overs = __ballot(active && a.over[base + z] != kEmpty);
+            if (!a.up) set = __builtin_bitreverse64(set), overs = __builtin_bitreverse64(overs);
+            const uint64_t above = (set >> v) >> 1;                   // the samples of S above this lane in the word
+            const uint32_t j = above != 0ull ? v + 1u + (uint32_t)__builtin_ctzll(above) : v;      // the nearest of them
+            const uint32_t fetched = (uint32_t)__shfl((int)id, (int)(a.up ? j : 63u - j));         // (every lane takes part)
+            const uint32_t holder = above != 0ull ? ((overs >> j) & 1ull ? fetched : kEmpty) : carry_holder;
+            const bool above_in = v == 63u ? carry_in : (above & 1ull) != 0ull;
+            const uint32_t h = layer_of(a, z);
+            const bool is_held = active && !in && h >= h0 && holder != kEmpty;
+            const bool lands = in && !above_in && holder != kEmpty;   // the sample above has the same holder: it is in P
+            if (active) {
+                a.support[base + z] = (uint8_t)(is_held ? holder : kEmpty);
+                a.landing[base + z] = (uint8_t)(lands ? id : kEmpty);
+            }
+            gather_counts(is_held, holder, lane, held);
+            gather_counts(lands, id, lane, landed);
+            plate += (unsigned long long)__popcll(__ballot(is_held && h == h0));
+            if (set != 0ull) {                                        // the lowest sample of S of the word decides what leaves it
+                const uint32_t low = (uint32_t)__builtin_ctzll(set);
+                const uint32_t owner = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)(a.up ? low : 63u - low));
+                carry_holder = (overs >> low) & 1ull ? owner : kEmpty;
+            }
+            carry_in = (set & 1ull) != 0ull;
+        }
+    }
+    add_counts(a, lane, held, landed, plate);
+}
+
+int over_args(const void* ids_dev, uint32_t* word_dev, const uint32_t dims[3], uint32_t pitch, int axis, uint32_t reach_sq,
+              uint32_t of, OverArgs& a)
+{
+    a = OverArgs{};
+    if (!ids_dev || !word_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    for (int i = 0; i < 3; ++i)
+        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
+        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
+    if (axis < 0 || axis > 2) return hu_fail(HU_ERR_BAD_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+    if (reach_sq > kMaxReach) return hu_fail(HU_ERR_BAD_ARG, "reach_sq must be at most 8");
+    if (of > 63u && of != kSolid) return hu_fail(HU_ERR_BAD_ARG, "of must be an instance index up to 63 or HU_OVERHANG_SOLID");
+    if (reinterpret_cast<uintptr_t>(word_dev) % 4u) return hu_fail(HU_ERR_BAD_ARG, "the depth word must be aligned to 4 bytes");
+    a.ids = static_cast<const uint8_t*>(ids_dev);
+    a.word = word_dev;
+    a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
+    a.axis = (uint32_t)axis, a.reach_sq = reach_sq, a.of = of;
+    a.na = dims[axis];
+    a.segments = (a.nz + 63u) / 64u;
+    return HU_OK;
+}
+
+// blocks of four wavefronts for a kernel that walks its units with FOR_UNITS: four units a wavefront at the least, so that
+// small lattices walk too, and at most kMaxBlocks blocks -- eight a compute unit of 256 --, which bounds the atomics on one
+// accumulator whatever the lattice
+constexpr uint64_t kMaxBlocks = 2048u;
+uint32_t walking_blocks(uint64_t units)
+{
+    const uint64_t blocks = (units + 15u) / 16u;
+    return (uint32_t)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hu_overhang_first_layer(const void* ids_dev, uint32_t* word_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up,
+                            uint32_t of, void* stream)
+{
+    OverArgs a;
+    int rc;
+    if ((rc = over_args(ids_dev, word_dev, dims, pitch, axis, 0u, of, a))) return rc;
+    a.up = up != 0;
+    const uint32_t blocks = walking_blocks((uint64_t)a.nx * a.ny * a.segments);
+    hipLaunchKernelGGL(k_over_first, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    HU_HIP(hipGetLastError());
+    return HU_OK;
+}
+
+int hu_overhang_mark(const void* ids_dev, void* overhang_dev, uint32_t* word_dev, uint64_t* counts_dev, const uint32_t dims[3],
+                     uint32_t pitch, int axis, int up, uint32_t reach_sq, uint32_t of, void* stream)
+{
+    OverArgs a;
+    int rc;
+    if ((rc = over_args(ids_dev, word_dev, dims, pitch, axis, reach_sq, of, a))) return rc;
+    if (!overhang_dev || !counts_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(counts_dev) % 8u) return hu_fail(HU_ERR_BAD_ARG, "the counts must be aligned to 8 bytes");
+    a.up = up != 0;
+    a.over = static_cast<uint8_t*>(overhang_dev);
+    a.counts = reinterpret_cast<unsigned long long*>(counts_dev);
+    const uint32_t blocks = walking_blocks((uint64_t)a.nx * a.ny * a.segments);
+    hipLaunchKernelGGL(k_over_mark, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    HU_HIP(hipGetLastError());
+    return HU_OK;
+}
+
+int hu_overhang_columns(const void* ids_dev, const void* overhang_dev, void* support_dev, void* landing_dev, uint32_t* word_dev,
+                        uint64_t* counts_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, uint32_t of, void* stream)
+{
+    OverArgs a;
+    int rc;
+    if ((rc = over_args(ids_dev, word_dev, dims, pitch, axis, 0u, of, a))) return rc;
+    if (!overhang_dev || !support_dev || !landing_dev || !counts_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(counts_dev) % 8u) return hu_fail(HU_ERR_BAD_ARG, "the counts must be aligned to 8 bytes");
+    a.up = up != 0;
+    a.over = static_cast<uint8_t*>(const_cast<void*>(overhang_dev));
+    a.support = static_cast<uint8_t*>(support_dev);
+    a.landing = static_cast<uint8_t*>(landing_dev);
+    a.counts = reinterpret_cast<unsigned long long*>(counts_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (axis == 2) {
+        hipLaunchKernelGGL((k_over_columns<true>), dim3(walking_blocks((uint64_t)a.nx * a.ny)), dim3(256), 0, s, a);
+    } else {                                                          // a wavefront a unit: at most 65536 lines of 1024 words
+        const uint64_t units = (uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments;
+        hipLaunchKernelGGL((k_over_columns<false>), dim3((uint32_t)((units + 3u) / 4u)), dim3(256), 0, s, a);
+    }
+    HU_HIP(hipGetLastError());
+    return HU_OK;
+}
+
+}  // extern "C"

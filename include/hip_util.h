@@ -473,6 +473,33 @@ int hu_thickness_pass_axis(const void* in_dev, void* out_dev, const void* ids_de
                            const uint32_t dims[3], uint32_t pitch, int axis, uint32_t of, uint32_t K, uint32_t cap,
                            uint32_t outside, int finish, uint32_t tile, int lds, void* stream);
 
+/* ---- what a print direction leaves in the air (codecad_amd/overhangs.py) -----------------------
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device.  S is the samples with id != 255
+ * (of == HU_OVERHANG_SOLID) or id == of (of <= 63); nothing outside the lattice is in S, and the padding z in [dims[2], pitch)
+ * of any volume is neither read nor written.  The build direction runs along `axis`, upwards (up != 0: the layer of a sample
+ * is its index on that axis) or downwards (dims[axis] - 1 - index); "below" is one layer less.  word_dev is the DEPTH WORD, a
+ * uint32 the caller zeroes: dims[axis] - h0, h0 the least layer that holds a sample of S, 0 while there is none.
+ * hu_overhang_first_layer: raises the word to that value, at most one atomic per wavefront that holds a sample of S.
+ * hu_overhang_mark: overhang_dev <- the id of a sample of S above layer h0 that has no sample of S below it at any lateral
+ *   offset (u, v) with u * u + v * v <= reach_sq, 255 elsewhere; counts_dev[p] (64 uint64, the caller's zeros) += those of id p.
+ * hu_overhang_columns: along every line of the axis from the top layer down to h0, support_dev <- for a sample not in S whose
+ *   nearest sample of S above is an overhang, that overhang's id, 255 elsewhere; landing_dev <- the id of a sample of S with
+ *   such a sample right above it, 255 elsewhere; counts_dev (129 uint64, the caller's zeros): [p] += the supported samples held
+ *   by id p, [64 + p] += the landings id p owns, [128] += the supported samples in layer h0.  One atomic per accumulator and
+ *   wavefront.
+ * The three run in this order on one stream and read the word on the device: the host need not wait in between.  All allocate
+ * nothing and synchronise nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL pointers, a
+ * pitch that is no multiple of 16 or below dims[2], dims of 0 or above 65536, an axis above 2, reach_sq above
+ * HU_OVERHANG_MAX_REACH_SQ, an `of` above 63 that is not HU_OVERHANG_SOLID, a word not aligned to 4 or counts not to 8 bytes. */
+#define HU_OVERHANG_SOLID 255
+#define HU_OVERHANG_MAX_REACH_SQ 8
+int hu_overhang_first_layer(const void* ids_dev, uint32_t* word_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up,
+                            uint32_t of, void* stream);
+int hu_overhang_mark(const void* ids_dev, void* overhang_dev, uint32_t* word_dev, uint64_t* counts_dev, const uint32_t dims[3],
+                     uint32_t pitch, int axis, int up, uint32_t reach_sq, uint32_t of, void* stream);
+int hu_overhang_columns(const void* ids_dev, const void* overhang_dev, void* support_dev, void* landing_dev, uint32_t* word_dev,
+                        uint64_t* counts_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, uint32_t of, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

@@ -374,8 +374,19 @@ __device__ __forceinline__ void grid_eval_boxes(const E& ev, float4* lds, float 
     // the boxes, its workgroups walking it in order: neighbours meet in one L2.  Measured, 512^3, per-tape code over boxes
     // (profiles/r04_hbm_sweep.jsonl): float grids 0.16-0.18 -> 0.12-0.14 ms (csg_example 0.177 -> 0.116, sponge(4) 0.171 ->
     // 0.138), float4 grids of light tapes -2...-4 % (whole lines either way), sponge(4)'s unchanged.
-    const uint32_t k = blockIdx.x & 7u, q = gridDim.x >> 3, r = gridDim.x & 7u;     // XCD k takes q + (k < r) boxes
-    const uint32_t b = k * q + (k < r ? k : r) + (blockIdx.x >> 3);
+    // FLOAT4 grids (round 6): the eighths are dealt per CHUNK of kDenseChunk boxes of the list, chunk after chunk, not per
+    // launch.  What the chip writes at one moment is then one short range of the box list -- a few chunks, as for runs
+    // along z -- instead of eight ranges an eighth of the grid apart, one per XCD.  Stores alone (tools/experiments/
+    // store_patterns.hip, profiles/r06_store_patterns.txt): 0.362 -> 0.351-0.355 ms for chunks of 256 ... 1024 boxes;
+    // sponge(4), 512^3, bench c3: chunks of 128 / 256 / 512 / 1024 / 2048 boxes 0.408-0.413 / 0.386-0.391 / 0.393-0.398 /
+    // 0.396-0.400 / 0.401-0.403 ms against 0.404-0.408 per launch.  The float layout keeps its eighths per launch (its
+    // neighbours along z share lines).  A bijection for any box count: a chunk is `n` consecutive workgroups and `n` consecutive boxes.
+    // (256 is tuned on that one shape -- 128 is slower than no chunks at all --; x slabs of it and 256^3 grids were not measured)
+    constexpr uint32_t kDenseChunk = 256u;      // a multiple of 8: a workgroup's XCD is its index in the chunk % 8
+    const uint32_t first = LAYOUT == 0 ? blockIdx.x / kDenseChunk * kDenseChunk : 0u;      // (the float layout: one chunk, the launch)
+    const uint32_t n = LAYOUT == 0 ? min(kDenseChunk, gridDim.x - first) : gridDim.x, l = blockIdx.x - first;
+    const uint32_t k = l & 7u, q = n >> 3, r = n & 7u;     // XCD k takes q + (k < r) boxes of the chunk
+    const uint32_t b = first + k * q + (k < r ? k : r) + (l >> 3);
     const uint32_t qz = b % boxes_z, qt = b / boxes_z, qy = qt % boxes_y, qx = qt / boxes_y;
     const BoxOut o{out, 0, sx, sy, sz, LAYOUT == 0 ? 0u : x0, nx_slab};
     box_eval<E, LAYOUT, N, RAGGED>(ev, lds, cx, cy, cz, step, x0, qx * 16u, qy * 16u, qz * 16u, o, masks, b);

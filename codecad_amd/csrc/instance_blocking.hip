@@ -1,0 +1,203 @@
+// codecad_amd/csrc/instance_blocking.hip
+//
+// WHICH PART BLOCKS WHICH ALONG A LATTICE AXIS, on the part-id volume of an assembly, for codecad_amd/disassembly.py.  A LINE
+// of axis a is the samples that agree on the other two indices.  For an ordered pair i != j
+//   D_a[i][j] = min { q[a] - p[a] : ids[p] = i, ids[q] = j, p and q on one line of a, q[a] > p[a] },
+// and the WITNESS is the lexicographically first (x, y, z) among the p that attain it.  Both are one number, the KEY
+//   D << 48 | x << 32 | y << 16 | z        (uint64; indices and D are at most 65535; all ones: no such p and q),
+// and the least key per (a, i, j) is the result: an integer minimum, exact and independent of the order anything ran in.
+//
+// ONLY RUN STARTS COUNT.  A RUN is a maximal stretch of one id != 255 on a line.  The p and q of a least D are the last sample
+// of i before q and the first sample of a run of j: a sample of i between them, or a sample of j right before q, would give
+// less.  So a walk up the line carries, per part, the index of the last sample of its latest run that has ENDED -- written
+// when the run ends, not at every sample -- and lowers keys only where a run starts: against every part seen so far but the
+// run's own.
+//
+// LANES LIE ALONG z IN BOTH KERNELS: a wavefront's global accesses are runs of consecutive bytes, and no byte of the padding z
+// in [nz, pitch) is read.
+//   k_block_lines (axis 0 or 1): a UNIT is 64 consecutive z of one line bundle -- the lines of one y (axis 0) or one x
+//     (axis 1) --; a wavefront walks its unit up the axis, eight samples a lane in flight, and carries per lane the previous
+//     id and a 64-bit mask of the parts seen in registers and the last index of every part as uint16 [part][lane] in LDS: no
+//     private array, no scratch.  A ballot skips the samples at which no lane's id changes.
+//   k_block_columns (axis 2): the line is the wavefront itself; a unit is an (x, y) column, walked word by word (64 samples)
+//     upwards.  LANE p HOLDS THE LAST INDEX OF PART p (instance_overhang.hip: lane p gathers part p).  An EVENT is a sample
+//     whose id differs from the one below it -- one ballot; the id below lane 0 is the CARRY, the last id of the word below,
+//     255 under the column --, and the events of a word are taken in ascending order, wave-uniform: the run that ended (the id
+//     below, if not 255) gives its owner's lane the index below; the run that starts (the id, if not 255), owner j, has every
+//     lane i != j with a last index lower the key of (i, j).  A run across a word edge is no event at lane 0; a word without
+//     solid has at most the event that ends the run below it, and the lanes' last indices pass through it untouched.
+// Both lower keys by 64-bit minimum in a table in LDS, one a workgroup, n * n entries ([i][j] for the lines; [j][i] for the
+// columns, whose 64 lanes then hit consecutive entries), and flush it at the end: at most one global atomicMin per entry, none
+// where the entry still reads all ones or is not below what the global table holds already (it only ever falls, so a stale
+// read costs an atomic and never a result).  Units are walked a grid apart with a bounded grid.  Byte offsets are 64-bit.
+// The entry point is at the end of this file.
+#include "instance_cells.hpp"
+
+using namespace hu_cells;
+
+namespace {
+
+constexpr uint32_t kEmpty = 255u;                       // instance_voxels.hip: the id of a sample inside no part
+constexpr uint32_t kParts = HU_BLOCKING_MAX_PARTS;      // the global table is uint64[3][kParts][kParts]
+constexpr uint32_t kBatch = 8u;                         // samples a lane of k_block_lines has in flight
+constexpr unsigned long long kNever = ~0ull;
+static_assert(kParts == 64u, "include/hip_util.h; a lane per part, a bit per part");
+
+struct BlockArgs {
+    const uint8_t* ids;                 // uint8[nx][ny][pitch]
+    unsigned long long* keys;           // uint64[kParts][kParts] of this axis
+    uint32_t nx, ny, nz, pitch;
+    uint32_t axis, n;
+    uint32_t na;                        // dims[axis]
+    uint32_t segments;                  // ceil(nz / 64)
+};
+
+extern __shared__ unsigned long long block_lds[];       // n * n keys, then (k_block_lines) uint16[n][256] last indices
+
+__device__ __forceinline__ unsigned long long key_of(uint32_t d, uint32_t x, uint32_t y, uint32_t z)
+{
+    return ((unsigned long long)d << 48) | ((unsigned long long)x << 32) | ((unsigned long long)y << 16) | z;
+}
+
+// the id at `at`; anything that is no part of the table counts as empty
+__device__ __forceinline__ uint32_t id_at(const uint8_t* at, uint32_t n)
+{
+    const uint32_t id = *at;
+    return id < n ? id : kEmpty;
+}
+
+__device__ __forceinline__ void lower(unsigned long long* entry, unsigned long long key)
+{
+    if (key < *entry) atomicMin(entry, key);            // (LDS: a read where nothing falls, which is nearly everywhere)
+}
+
+__device__ __forceinline__ void reset_table(unsigned long long* table, uint32_t entries)
+{
+    for (uint32_t e = threadIdx.x; e < entries; e += 256u) table[e] = kNever;
+    __syncthreads();
+}
+
+// LDS entry e = row * n + col goes to the global [row][col], or, TRANSPOSED, to [col][row]
+template <bool TRANSPOSED>
+__device__ __forceinline__ void flush_table(const BlockArgs& a, const unsigned long long* table)
+{
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < a.n * a.n; e += 256u) {
+        const unsigned long long key = table[e];
+        if (key == kNever) continue;
+        const uint32_t row = e / a.n, col = e - row * a.n;
+        unsigned long long* out = a.keys + (TRANSPOSED ? col * kParts + row : row * kParts + col);
+        if (key < __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMin(out, key);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_block_lines(const BlockArgs a)
+{
+    unsigned long long* table = block_lds;                                        // [i][j]
+    uint16_t* last = reinterpret_cast<uint16_t*>(block_lds + a.n * a.n) + threadIdx.x;   // [part][256]: this lane's column
+    const uint32_t lane = threadIdx.x & 63u;
+    reset_table(table, a.n * a.n);
+    const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
+    const size_t stride = a.axis == 0u ? (size_t)a.ny * a.pitch : (size_t)a.pitch;
+    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); unit < (uint64_t)lines * a.segments;
+         unit += (uint64_t)gridDim.x * 4u) {                                      // wave-uniform
+        const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
+        const bool active = z < a.nz;
+        const uint8_t* at = a.ids + (a.axis == 0u ? (size_t)line * a.pitch : (size_t)line * a.ny * a.pitch) + z;
+        uint32_t prev = kEmpty;                                                   // the id of the sample below
+        uint64_t seen = 0ull;                                                     // the parts with a last index
+        for (uint32_t t0 = 0u; t0 < a.na; t0 += kBatch) {                         // wave-uniform: up the axis
+            uint32_t batch[kBatch];                                               // (unrolled: registers)
+#pragma unroll
+            for (uint32_t k = 0u; k < kBatch; ++k)
+                batch[k] = active && t0 + k < a.na ? id_at(at + (size_t)(t0 + k) * stride, a.n) : kEmpty;
+#pragma unroll
+            for (uint32_t k = 0u; k < kBatch; ++k) {
+                const uint32_t id = batch[k], t = t0 + k;                         // (past the line's end: 255, which starts nothing)
+                if (__ballot(id != prev) == 0ull) continue;                       // wave-uniform
+                if (id != prev) {
+                    if (prev != kEmpty) {                                         // a run ended at t - 1
+                        last[prev * 256u] = (uint16_t)(t - 1u);
+                        seen |= 1ull << prev;
+                    }
+                    if (id != kEmpty)                                             // a run of `id` starts at t
+                        for (uint64_t m = seen & ~(1ull << id); m != 0ull; m &= m - 1ull) {
+                            const uint32_t i = (uint32_t)__builtin_ctzll(m), p = last[i * 256u];
+                            lower(&table[i * a.n + id], a.axis == 0u ? key_of(t - p, p, line, z) : key_of(t - p, line, p, z));
+                        }
+                    prev = id;
+                }
+            }
+        }
+    }
+    flush_table<false>(a, table);
+}
+
+__global__ void __launch_bounds__(256) k_block_columns(const BlockArgs a)
+{
+    unsigned long long* table = block_lds;                                        // [j][i]
+    const uint32_t lane = threadIdx.x & 63u;
+    reset_table(table, a.n * a.n);
+    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); unit < (uint64_t)a.nx * a.ny;
+         unit += (uint64_t)gridDim.x * 4u) {                                      // wave-uniform: a unit is an (x, y) column
+        const uint32_t x = (uint32_t)(unit / a.ny), y = (uint32_t)(unit - (uint64_t)x * a.ny);
+        const uint8_t* at = a.ids + (size_t)unit * a.pitch + lane;
+        uint32_t mine = ~0u;                                                      // the last index of part `lane`; ~0: none yet
+        uint32_t carry = kEmpty;                                                  // wave-uniform: the last id of the word below
+        uint32_t next = lane < a.nz ? id_at(at, a.n) : kEmpty;
+        for (uint32_t k = 0u; k < a.segments; ++k) {                              // wave-uniform: up the column
+            const uint32_t z0 = k << 6, id = next;
+            if (k + 1u < a.segments) next = z0 + 64u + lane < a.nz ? id_at(at + z0 + 64u, a.n) : kEmpty;     // (the next word is on its way)
+            const uint32_t shifted = (uint32_t)__shfl_up((int)id, 1);             // (every lane takes part)
+            const uint32_t below = lane == 0u ? carry : shifted;
+            carry = (uint32_t)__builtin_amdgcn_readlane((int)id, 63);             // (255 past the column's end)
+            for (uint64_t events = __ballot(id != below); events != 0ull; events &= events - 1ull) {
+                const int b = (int)__builtin_ctzll(events);
+                const uint32_t ended = (uint32_t)__builtin_amdgcn_readlane((int)below, b);
+                const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)id, b), z = z0 + (uint32_t)b;
+                if (lane == ended) mine = z - 1u;                                 // (never 255: a lane is a part)
+                if (j != kEmpty && lane != j && lane < a.n && mine != ~0u)
+                    lower(&table[j * a.n + lane], key_of(z - mine, x, y, mine));
+            }
+        }
+    }
+    flush_table<true>(a, table);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t dims[3], uint32_t pitch, int axis, uint32_t n,
+                      void* stream)
+{
+    if (!ids_dev || !keys_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(keys_dev) % 8u) return hu_fail(HU_ERR_BAD_ARG, "the key table must be aligned to 8 bytes");
+    for (int i = 0; i < 3; ++i)
+        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
+        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
+    if (axis < 0 || axis > 2) return hu_fail(HU_ERR_BAD_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+    if (n == 0u || n > kParts) return hu_fail(HU_ERR_BAD_ARG, "n must be in 1..64");
+    BlockArgs a{};
+    a.ids = static_cast<const uint8_t*>(ids_dev);
+    a.keys = reinterpret_cast<unsigned long long*>(keys_dev) + (size_t)axis * kParts * kParts;
+    a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
+    a.axis = (uint32_t)axis, a.n = n, a.na = dims[axis];
+    a.segments = (a.nz + 63u) / 64u;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // blocks of four wavefronts that walk units a grid apart; the grid is bounded, which bounds the flushes: a workgroup's
+    // table of n = 64 parts and its last indices are 64 KiB, two workgroups a compute unit of 256
+    const size_t table = (size_t)n * n * 8u;
+    if (axis == 2) {                                                              // four columns a wavefront at the least
+        const uint64_t blocks = ((uint64_t)a.nx * a.ny + 15u) / 16u;
+        hipLaunchKernelGGL(k_block_columns, dim3((uint32_t)(blocks < 2048u ? blocks : 2048u)), dim3(256), table, s, a);
+    } else {                                                                      // a unit is a whole walk up the axis: one each
+        const uint64_t blocks = ((uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments + 3u) / 4u;
+        hipLaunchKernelGGL(k_block_lines, dim3((uint32_t)(blocks < 2048u ? blocks : 2048u)), dim3(256), table + (size_t)n * 512u, s, a);
+    }
+    HU_HIP(hipGetLastError());
+    return HU_OK;
+}
+
+}  // extern "C"

@@ -500,6 +500,24 @@ int hu_overhang_mark(const void* ids_dev, void* overhang_dev, uint32_t* word_dev
 int hu_overhang_columns(const void* ids_dev, const void* overhang_dev, void* support_dev, void* landing_dev, uint32_t* word_dev,
                         uint64_t* counts_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, uint32_t of, void* stream);
 
+/* ---- which part blocks which along a lattice axis (codecad_amd/disassembly.py) -----------------
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, with ids 0 .. n - 1 and 255 for a sample
+ * inside no part (an id from n up counts as 255); the padding z in [dims[2], pitch) is not read.  A line of `axis` is the samples that agree on the other two
+ * indices.  keys_dev is the KEY TABLE, uint64[3][HU_BLOCKING_MAX_PARTS][HU_BLOCKING_MAX_PARTS], which the caller sets to all
+ * ones; a call lowers the entries [axis][i][j], i != j < n, to the least
+ *   (q[axis] - p[axis]) << 48 | p.x << 32 | p.y << 16 | p.z
+ * over the samples p of id i and q of id j on one line of the axis with q[axis] > p[axis]: the least distance from i up to j
+ * and, among the p that attain it, the lexicographically first.  An entry no such p and q exist for stays all ones.  Keys are
+ * lowered in a table in LDS per workgroup (n * n * 8 bytes, and n * 512 bytes of last indices for axis 0 and 1) and reach the
+ * key table by at most one 64-bit atomic minimum per entry and workgroup, so calls for several axes may follow one another
+ * on one stream without the host waiting in between.
+ * Allocates nothing and synchronises nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL
+ * pointers, a key table not aligned to 8 bytes, a pitch that is no multiple of 16 or below dims[2], dims of 0 or above 65536,
+ * an axis outside 0..2, n outside 1..HU_BLOCKING_MAX_PARTS. */
+#define HU_BLOCKING_MAX_PARTS 64
+int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t dims[3], uint32_t pitch, int axis, uint32_t n,
+                      void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

@@ -35,16 +35,15 @@ statistics pass alone again (`component_capacity_runs` says how often it ran: 1 
 guess).  That changes how often a pass runs, never a result.
 """
 import collections
-import ctypes
 
 import numpy
 
 from . import util
 from . import hip_util
-from .assembly_voxels import _device_volume
+from .assembly_voxels import _device_volume, _dims, _cropped, _LabelMask, SOLID
 from .hip_util import manager as hip_manager, check
 
-EMPTY_SPACE, SOLID = "empty_space", "solid"
+EMPTY_SPACE = "empty_space"     # (SOLID: assembly_voxels.py)
 NONE = 0xffffffff               # the label of a sample outside S
 TILE = (8, 8, 16)               # the samples of a tile of the LDS stage (include/hip_util.h HU_COMPONENTS_TILE_*)
 _CAPACITY = 4096                # the first guess of the table's rows
@@ -59,16 +58,12 @@ class Component(collections.namedtuple("Component", "label count box index_sums 
     __slots__ = ()
 
 
-class ComponentsReport(collections.namedtuple("ComponentsReport", "instances corner step dims of labels components part_ids "
+class ComponentsReport(_LabelMask, collections.namedtuple("ComponentsReport", "instances corner step dims of labels components part_ids "
                                                                   "samples_evaluated traversals component_capacity_runs")):
     """`instances`, `corner`, `step`, `dims`, `part_ids`, `samples_evaluated`, `traversals`: as in AssemblyVoxels; `of`: the
     set that was labelled; `labels`: uint32[nx, ny, nz]; `components`: [Component] ordered by label;
     `component_capacity_runs`: how often the statistics pass ran (0 when nothing was launched)."""
     __slots__ = ()
-
-    def mask(self, component):
-        """bool[nx, ny, nz]: the samples of `component` (a Component or a label)."""
-        return self.labels == getattr(component, "label", component)
 
 
 class Cavity(collections.namedtuple("Cavity", Component._fields + ("enclosed_by",))):
@@ -138,7 +133,7 @@ def _label_volume(volume, shape, solid, local, initial_components):
     the table's used rows, how often the statistics pass ran).  `volume` is released here, as soon as no kernel reads it."""
     lib, queue = hip_manager.lib, hip_manager.queue
     nx, ny, pz = volume.shape
-    dims = (ctypes.c_uint32 * 3)(*shape)
+    dims = _dims(shape)
     labels = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
     check(lib.hu_components_local(volume.device_ptr, labels.device_ptr, dims, pz, solid, int(bool(local)), queue.handle),
           "hu_components_local")
@@ -161,7 +156,7 @@ def _label_volume(volume, shape, solid, local, initial_components):
         capacity = count                                               # every root was counted: the second table holds them all
     volume.release()
     check(lib.hu_components_finish(labels.device_ptr, dims, pz, queue.handle), "hu_components_finish")
-    out = numpy.ascontiguousarray(labels.read()[:, :, :shape[2]])
+    out = _cropped(labels, shape[2])
     labels.release()
     return out, rows[1:1 + count], runs
 

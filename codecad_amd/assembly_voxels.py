@@ -46,6 +46,7 @@ PREMISE.  That of `assembly_mass_properties()`: on BOTH sides of the surface |w|
 the bounding box holds the instance.  Shapes from `shapes.unsafe` break it; then the volume may differ from `retire=False`.
 """
 import collections
+import ctypes
 
 import numpy
 
@@ -56,6 +57,8 @@ from ._instance_cells import Instance
 from .assembly_mass import threshold
 
 EMPTY = 255                 # the id of a sample inside no part
+SOLID = "solid"             # the set `of` every sample inside some part, for the checks that take a set (assembly_components.py)
+_SOLID_CODE = 255           # ... as their entry points take it: include/hip_util.h HU_THICKNESS_SOLID, HU_OVERHANG_SOLID
 _RUN = 16                   # a z run of the device buffer is a multiple of this many bytes
 _ACC = numpy.dtype("<u8")   # n counts, then the bytes retired children filled
 
@@ -101,6 +104,38 @@ def top_rows(instances, corner, step, dims, side):
 def _voxels(instances, corner, step, dims, part_ids, counts, evaluations, traversals):
     return AssemblyVoxels([Instance(i.name, i) for i in instances], corner, step, dims, part_ids, [int(c) for c in counts],
                           evaluations, traversals)
+
+
+def _whole(v, least, most):     # what a caller of _device_volume() needs beside it starts here (the device's: csrc/id_volume.hpp)
+    return isinstance(v, (int, numpy.integer)) and not isinstance(v, bool) and least <= v <= most
+
+
+def _of_code(of, n):
+    if of != SOLID and not _whole(of, 0, n - 1):
+        raise ValueError("of must be SOLID or the index of one of the %d visible instances, not %r" % (n, of))
+    return _SOLID_CODE if of == SOLID else int(of)
+
+
+def _axis(axis):
+    if not _whole(axis, 0, 2):
+        raise ValueError("axis must be 0, 1 or 2, not %r" % (axis,))
+    return int(axis)
+
+
+def _dims(shape):
+    return (ctypes.c_uint32 * 3)(*(int(d) for d in shape))
+
+
+def _cropped(buffer, nz):
+    return numpy.ascontiguousarray(buffer.read()[:, :, :nz])
+
+
+class _LabelMask:
+    __slots__ = ()
+
+    def mask(self, region, /):
+        """bool[nx, ny, nz]: the samples of `region` (one of the report's Components or a label)."""
+        return self.labels == getattr(region, "label", region)
 
 
 def assembly_voxels(asm, resolution, initial_capacity=None, retire=True, max_bytes=2 ** 32):

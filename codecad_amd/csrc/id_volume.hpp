@@ -1,0 +1,87 @@
+// codecad_amd/csrc/id_volume.hpp -- the PART-ID VOLUME of an assembly and what the kernels that walk it share.
+//
+// THE CONTRACT.  instance_voxels.hip fills a uint8[nx][ny][pitch] volume on the device, x slowest: the byte of sample (x, y, z) is
+// the index of the part that owns it, 255 (kEmpty) where it is inside no part.  pitch is nz rounded up to a multiple of 16; the
+// PADDING z in [nz, pitch) is never read as data.  Every dimension is at most 65536, so the volume may hold 2^48 bytes: BYTE
+// OFFSETS ARE 64-BIT.  Nothing outside the lattice is inside any part.  A kernel takes the lattice in its argument struct as
+// uint32 nx, ny, nz, pitch and, where it walks units, segments and na, under these names: the structs keep their own layout (the
+// order of a kernel's arguments decides how its scalar loads pair up).  Lanes lie along z; workgroups are four wavefronts.
+#pragma once
+
+#include "instance_cells.hpp"
+
+namespace hu_cells {
+
+constexpr uint32_t kEmpty = 255u;                       // the id of a sample inside no part
+constexpr uint32_t kSolid = HU_THICKNESS_SOLID;         // of: S is id != 255; any other of (<= 63): S is id == of
+static_assert(kSolid == kEmpty && HU_OVERHANG_SOLID == kSolid, "include/hip_util.h");
+
+__device__ __forceinline__ bool in_set(uint32_t id, uint32_t of) { return of == kSolid ? id != kEmpty : id == of; }
+
+// lane p's `mine` += the lanes that count and whose id is p, for every id present (wave-uniform loop)
+__device__ __forceinline__ void gather_counts(bool counted, uint32_t id, uint32_t lane, unsigned long long& mine)
+{
+    for (uint64_t todo = __ballot(counted); todo != 0ull;) {
+        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)__builtin_ctzll(todo));
+        const uint64_t b = __ballot(counted && id == p);
+        todo &= ~b;
+        if (lane == (p & 63u)) mine += (unsigned long long)__popcll(b);
+    }
+}
+
+// unit `unit` of nx * ny * segments: 64 consecutive z, from z0 on, of column (x, y), whose bytes start at `base` (wave-uniform)
+struct ColumnUnit {
+    uint32_t x, y, z0;
+    size_t base;
+};
+template <class A> __device__ __forceinline__ ColumnUnit column_unit(const A& a, uint64_t unit)
+{
+    const uint64_t column = unit / a.segments;
+    ColumnUnit u;
+    u.z0 = ((uint32_t)(unit - column * a.segments)) << 6;
+    u.x = (uint32_t)(column / a.ny), u.y = (uint32_t)(column - (uint64_t)u.x * a.ny);
+    u.base = (size_t)column * a.pitch;
+    return u;
+}
+
+// a wavefront takes the units w, w + W, w + 2 W, ... of `units`, W the wavefronts of the grid (wave-uniform), and gathers over all
+#define HU_FOR_UNITS(unit, units) \
+    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + hu_cells::uniform(threadIdx.x >> 6); unit < (units); unit += (uint64_t)gridDim.x * 4u)
+
+// host side (`dims` is not NULL): the checks, and the fill of the lattice's fields
+inline int check_pitch(const uint32_t dims[3], uint32_t pitch)
+{
+    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
+        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
+    return HU_OK;
+}
+template <class A> int lattice_of(const uint32_t dims[3], uint32_t pitch, A& a)
+{
+    for (int i = 0; i < 3; ++i)
+        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
+    return check_pitch(dims, pitch);
+}
+template <class A> int lattice_units(int axis, A& a)
+{
+    if (axis < 0 || axis > 2) return hu_fail(HU_ERR_BAD_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+    a.na = axis == 0 ? a.nx : axis == 1 ? a.ny : a.nz, a.segments = (a.nz + 63u) / 64u;
+    return HU_OK;
+}
+// `solid`: the name of kSolid in the caller's part of include/hip_util.h
+inline int check_of(uint32_t of, const char* solid)
+{
+    if (of > 63u && of != kSolid) return hu_fail(HU_ERR_BAD_ARG, std::string("of must be an instance index up to 63 or ") + solid);
+    return HU_OK;
+}
+
+// blocks for HU_FOR_UNITS: `per_wavefront` units a wavefront at the least, so that small lattices walk too, and at most
+// kMaxBlocks -- eight a compute unit of 256 --, which bounds the atomics on one accumulator whatever the lattice
+constexpr uint64_t kMaxBlocks = 2048u;
+inline uint32_t walking_blocks(uint64_t units, uint32_t per_wavefront)
+{
+    const uint64_t blocks = (units + 4u * per_wavefront - 1u) / (4u * per_wavefront);
+    return (uint32_t)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
+}
+
+}  // namespace hu_cells

@@ -20,7 +20,7 @@
 //     id and a 64-bit mask of the parts seen in registers and the last index of every part as uint16 [part][lane] in LDS: no
 //     private array, no scratch.  A ballot skips the samples at which no lane's id changes.
 //   k_block_columns (axis 2): the line is the wavefront itself; a unit is an (x, y) column, walked word by word (64 samples)
-//     upwards.  LANE p HOLDS THE LAST INDEX OF PART p (instance_overhang.hip: lane p gathers part p).  An EVENT is a sample
+//     upwards.  LANE p HOLDS THE LAST INDEX OF PART p (as lane p gathers part p in id_volume.hpp).  An EVENT is a sample
 //     whose id differs from the one below it -- one ballot; the id below lane 0 is the CARRY, the last id of the word below,
 //     255 under the column --, and the events of a word are taken in ascending order, wave-uniform: the run that ended (the id
 //     below, if not 255) gives its owner's lane the index below; the run that starts (the id, if not 255), owner j, has every
@@ -29,15 +29,14 @@
 // Both lower keys by 64-bit minimum in a table in LDS, one a workgroup, n * n entries ([i][j] for the lines; [j][i] for the
 // columns, whose 64 lanes then hit consecutive entries), and flush it at the end: at most one global atomicMin per entry, none
 // where the entry still reads all ones or is not below what the global table holds already (it only ever falls, so a stale
-// read costs an atomic and never a result).  Units are walked a grid apart with a bounded grid.  Byte offsets are 64-bit.
-// The entry point is at the end of this file.
-#include "instance_cells.hpp"
+// read costs an atomic and never a result).  Units are walked a grid apart with a bounded grid.  The volume's contract, the
+// units and their walk: id_volume.hpp.  The entry point is at the end of this file.
+#include "id_volume.hpp"
 
 using namespace hu_cells;
 
 namespace {
 
-constexpr uint32_t kEmpty = 255u;                       // instance_voxels.hip: the id of a sample inside no part
 constexpr uint32_t kParts = HU_BLOCKING_MAX_PARTS;      // the global table is uint64[3][kParts][kParts]
 constexpr uint32_t kBatch = 8u;                         // samples a lane of k_block_lines has in flight
 constexpr unsigned long long kNever = ~0ull;
@@ -99,8 +98,7 @@ __global__ void __launch_bounds__(256) k_block_lines(const BlockArgs a)
     reset_table(table, a.n * a.n);
     const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
     const size_t stride = a.axis == 0u ? (size_t)a.ny * a.pitch : (size_t)a.pitch;
-    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); unit < (uint64_t)lines * a.segments;
-         unit += (uint64_t)gridDim.x * 4u) {                                      // wave-uniform
+    HU_FOR_UNITS(unit, (uint64_t)lines * a.segments) {
         const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
         const bool active = z < a.nz;
         const uint8_t* at = a.ids + (a.axis == 0u ? (size_t)line * a.pitch : (size_t)line * a.ny * a.pitch) + z;
@@ -138,8 +136,7 @@ __global__ void __launch_bounds__(256) k_block_columns(const BlockArgs a)
     unsigned long long* table = block_lds;                                        // [j][i]
     const uint32_t lane = threadIdx.x & 63u;
     reset_table(table, a.n * a.n);
-    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); unit < (uint64_t)a.nx * a.ny;
-         unit += (uint64_t)gridDim.x * 4u) {                                      // wave-uniform: a unit is an (x, y) column
+    HU_FOR_UNITS(unit, (uint64_t)a.nx * a.ny) {                                      // a unit is an (x, y) column
         const uint32_t x = (uint32_t)(unit / a.ny), y = (uint32_t)(unit - (uint64_t)x * a.ny);
         const uint8_t* at = a.ids + (size_t)unit * a.pitch + lane;
         uint32_t mine = ~0u;                                                      // the last index of part `lane`; ~0: none yet
@@ -173,28 +170,22 @@ int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t di
 {
     if (!ids_dev || !keys_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (reinterpret_cast<uintptr_t>(keys_dev) % 8u) return hu_fail(HU_ERR_BAD_ARG, "the key table must be aligned to 8 bytes");
-    for (int i = 0; i < 3; ++i)
-        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
-        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
-    if (axis < 0 || axis > 2) return hu_fail(HU_ERR_BAD_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
-    if (n == 0u || n > kParts) return hu_fail(HU_ERR_BAD_ARG, "n must be in 1..64");
     BlockArgs a{};
+    if (int rc = lattice_of(dims, pitch, a)) return rc;
+    if (int rc = lattice_units(axis, a)) return rc;
+    if (n == 0u || n > kParts) return hu_fail(HU_ERR_BAD_ARG, "n must be in 1..64");
     a.ids = static_cast<const uint8_t*>(ids_dev);
     a.keys = reinterpret_cast<unsigned long long*>(keys_dev) + (size_t)axis * kParts * kParts;
-    a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
-    a.axis = (uint32_t)axis, a.n = n, a.na = dims[axis];
-    a.segments = (a.nz + 63u) / 64u;
+    a.axis = (uint32_t)axis, a.n = n;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // blocks of four wavefronts that walk units a grid apart; the grid is bounded, which bounds the flushes: a workgroup's
-    // table of n = 64 parts and its last indices are 64 KiB, two workgroups a compute unit of 256
+    // the bounded grid also bounds the flushes: a workgroup's table of n = 64 parts and its last indices are 64 KiB, two
+    // workgroups a compute unit
     const size_t table = (size_t)n * n * 8u;
     if (axis == 2) {                                                              // four columns a wavefront at the least
-        const uint64_t blocks = ((uint64_t)a.nx * a.ny + 15u) / 16u;
-        hipLaunchKernelGGL(k_block_columns, dim3((uint32_t)(blocks < 2048u ? blocks : 2048u)), dim3(256), table, s, a);
+        hipLaunchKernelGGL(k_block_columns, dim3(walking_blocks((uint64_t)a.nx * a.ny, 4u)), dim3(256), table, s, a);
     } else {                                                                      // a unit is a whole walk up the axis: one each
-        const uint64_t blocks = ((uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments + 3u) / 4u;
-        hipLaunchKernelGGL(k_block_lines, dim3((uint32_t)(blocks < 2048u ? blocks : 2048u)), dim3(256), table + (size_t)n * 512u, s, a);
+        const uint64_t units = (uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments;
+        hipLaunchKernelGGL(k_block_lines, dim3(walking_blocks(units, 1u)), dim3(256), table + (size_t)n * 512u, s, a);
     }
     HU_HIP(hipGetLastError());
     return HU_OK;

@@ -1,8 +1,8 @@
 // codecad_amd/csrc/instance_components.hip
 //
 // The CONNECTED COMPONENTS of a predicate on the part-id volume of an assembly (codecad_amd/assembly_components.py): S is
-// the samples with id == 255 (empty space) or id != 255 (solid) of the uint8[nx][ny][pitch] volume instance_voxels.hip
-// leaves on the device, two samples of S are connected when they differ by one step along one axis, and the label of a
+// the samples with id == 255 (empty space) or id != 255 (solid) of the uint8[nx][ny][pitch] part-id volume (id_volume.hpp
+// has its contract), two samples of S are connected when they differ by one step along one axis, and the label of a
 // sample is the smallest linear index (x * ny + y) * nz + z of its component, NONE = 0xffffffff outside S.  The padding
 // z in [nz, pitch) is neither in S nor anybody's neighbour: no kernel reads a byte of it as a sample.
 //
@@ -35,7 +35,7 @@
 // No kernel has a private array or scratch.  The entry points are at the end of this file.
 #include <algorithm>
 
-#include "instance_cells.hpp"
+#include "id_volume.hpp"
 
 using namespace sdfk;
 using namespace hu_cells;
@@ -44,7 +44,6 @@ namespace {
 
 constexpr uint32_t kNone = 0xffffffffu;     // the label of a sample outside S
 constexpr uint32_t kSlot = 0x80000000u;     // stage 4: the entry of a root holds kSlot | slot
-constexpr uint32_t kEmpty = 255u;           // instance_voxels.hip: the id of a sample inside no part
 constexpr uint32_t kTileX = HU_COMPONENTS_TILE_X, kTileY = HU_COMPONENTS_TILE_Y, kTileZ = HU_COMPONENTS_TILE_Z;
 constexpr uint32_t kTile = kTileX * kTileY * kTileZ;
 static_assert(kTileX == 8u && kTileY == 8u && kTileZ == 16u && kTile == 1024u, "the index arithmetic of k_comp_local");
@@ -101,7 +100,7 @@ __device__ __forceinline__ void unite(uint32_t* label, uint32_t a, uint32_t b)
     }
 }
 
-__device__ __forceinline__ bool in_set(uint32_t id, uint32_t solid) { return (id != kEmpty) == (solid != 0u); }
+__device__ __forceinline__ bool in_flagged_set(uint32_t id, uint32_t solid) { return (id != kEmpty) == (solid != 0u); }
 
 template <bool LOCAL>
 __global__ void __launch_bounds__(256) k_comp_local(const CompArgs k)
@@ -119,7 +118,7 @@ __global__ void __launch_bounds__(256) k_comp_local(const CompArgs k)
 #pragma unroll
             for (uint32_t dz = 0; dz < 16u; ++dz) {
                 const uint32_t word = dz < 4u ? v.x : dz < 8u ? v.y : dz < 12u ? v.z : v.w;
-                const bool in = z0 + dz < k.nz && in_set((word >> (8u * (dz & 3u))) & 0xffu, k.solid);   // (the padding is not in S)
+                const bool in = z0 + dz < k.nz && in_flagged_set((word >> (8u * (dz & 3u))) & 0xffu, k.solid);   // (the padding is not in S)
                 mask |= in ? 1u << dz : 0u;
             }
         }
@@ -298,7 +297,8 @@ __device__ __forceinline__ void flush(const CompArgs& k, const Run& r, uint32_t 
 // A UNIT is 64 consecutive z of one column: x and y are wave-uniform, so the x and y sums are count * x and count * y, the z
 // range comes from the ballot, and only the z sum and the owners' mask need a reduction across the lanes.  A wavefront walks
 // kStatsUnits consecutive units (along z, then y, then x) and keeps gathering in registers while the component stays the
-// same: the outside, one component of millions of samples, costs an atomic per word every 64 units and not every unit.
+// same: the outside, one component of millions of samples, costs an atomic per word every 64 units and not every unit.  It
+// indexes in 32 bits (at most 2^31 entries) and its units are consecutive: not column_unit and HU_FOR_UNITS.
 constexpr uint32_t kStatsUnits = 64u;
 __global__ void __launch_bounds__(256) k_comp_stats(const CompArgs k)
 {
@@ -374,17 +374,13 @@ int comp_args(const void* volume_dev, void* labels_dev, const uint32_t dims[3], 
 {
     k = CompArgs{};
     if (!labels_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    for (int i = 0; i < 3; ++i)
-        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
-        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
+    if (int rc = lattice_of(dims, pitch, k)) return rc;
     const unsigned __int128 total = (unsigned __int128)dims[0] * dims[1] * pitch;
     if (total > ((unsigned __int128)1 << 31)) return hu_fail(HU_ERR_BAD_ARG, "a label volume holds at most 2^31 entries");
     if (reinterpret_cast<uintptr_t>(volume_dev) % 16u || reinterpret_cast<uintptr_t>(labels_dev) % 4u)
         return hu_fail(HU_ERR_BAD_ARG, "the volume must be aligned to 16 bytes, the labels to 4");
     k.volume = static_cast<const uint8_t*>(volume_dev);
     k.labels = static_cast<uint32_t*>(labels_dev);
-    k.nx = dims[0], k.ny = dims[1], k.nz = dims[2], k.pitch = pitch;
     k.total = (uint32_t)total;
     return HU_OK;
 }

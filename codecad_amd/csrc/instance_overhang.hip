@@ -29,17 +29,15 @@
 //   Both write support_ids (the holder's id on P, else 255) and landing_ids (the id on L, else 255) and count P per holder,
 //   L per owner and the plate landings: lane p of a wavefront gathers the count of part p over everything the wavefront walks
 //   and adds it once at the end -- one atomic per accumulator and wavefront, and at most 8192 wavefronts where units are walked.
-// No kernel has a private array, LDS or scratch; byte offsets are 64-bit.  The entry points are at the end of this file.
-#include "instance_cells.hpp"
+// No kernel has a private array, LDS or scratch.  The volume, its units and their walk: id_volume.hpp.  Entry points: at the end.
+#include "id_volume.hpp"
 
 using namespace hu_cells;
 
 namespace {
 
-constexpr uint32_t kEmpty = 255u;                       // instance_voxels.hip: the id of a sample inside no part
-constexpr uint32_t kSolid = HU_OVERHANG_SOLID;          // of: S is id != 255; any other of (<= 63): S is id == of
 constexpr uint32_t kMaxReach = HU_OVERHANG_MAX_REACH_SQ;
-static_assert(kSolid == kEmpty && kMaxReach == 8u, "include/hip_util.h");
+static_assert(kMaxReach == 8u, "include/hip_util.h");
 
 struct OverArgs {
     const uint8_t* ids;                 // uint8[nx][ny][pitch]
@@ -54,47 +52,14 @@ struct OverArgs {
     uint32_t segments;                  // ceil(nz / 64)
 };
 
-__device__ __forceinline__ bool in_set(uint32_t id, uint32_t of) { return of == kSolid ? id != kEmpty : id == of; }
-
-// lane p's `mine` += the lanes that count and whose id is p, for every id present (wave-uniform loop; instance_thickness.hip)
-__device__ __forceinline__ void gather_counts(bool counted, uint32_t id, uint32_t lane, unsigned long long& mine)
-{
-    for (uint64_t todo = __ballot(counted); todo != 0ull;) {
-        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)__builtin_ctzll(todo));
-        const uint64_t b = __ballot(counted && id == p);
-        todo &= ~b;
-        if (lane == (p & 63u)) mine += (unsigned long long)__popcll(b);
-    }
-}
-
-// 64 consecutive z of one (x, y) column: the unit of a wavefront of k_over_first and k_over_mark (all wave-uniform)
-struct Unit {
-    uint32_t x, y, z0;
-    size_t base;
-};
-__device__ __forceinline__ Unit unit_of(const OverArgs& a, uint64_t unit)
-{
-    const uint64_t column = unit / a.segments;
-    Unit u;
-    u.z0 = ((uint32_t)(unit - column * a.segments)) << 6;
-    u.x = (uint32_t)(column / a.ny), u.y = (uint32_t)(column - (uint64_t)u.x * a.ny);
-    u.base = (size_t)column * a.pitch;
-    return u;
-}
-
-// A wavefront takes the units w, w + W, w + 2 W, ... of `units`, W the wavefronts of the grid (wave-uniform): it gathers over
-// all of them and adds to an accumulator once, however many units the lattice has.
-#define FOR_UNITS(unit, units) \
-    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6); unit < (units); unit += (uint64_t)gridDim.x * 4u)
-
 __device__ __forceinline__ uint32_t layer_of(const OverArgs& a, uint32_t along) { return a.up ? along : a.na - 1u - along; }
 
 __global__ void __launch_bounds__(256) k_over_first(const OverArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t depth = 0u;                                              // wave-uniform: n_axis - the least layer seen
-    FOR_UNITS(unit, (uint64_t)a.nx * a.ny * a.segments) {
-        const Unit u = unit_of(a, unit);
+    HU_FOR_UNITS(unit, (uint64_t)a.nx * a.ny * a.segments) {
+        const ColumnUnit u = column_unit(a, unit);
         const uint32_t z = u.z0 + lane;
         const bool in = z < a.nz && in_set(a.ids[u.base + z], a.of);
         const uint64_t m = __ballot(in);
@@ -114,8 +79,8 @@ __global__ void __launch_bounds__(256) k_over_mark(const OverArgs a)
     unsigned long long mine = 0ull;
     const int s = a.up ? 1 : -1;
     const int reach = a.reach_sq >= 4u ? 2 : a.reach_sq >= 1u ? 1 : 0;
-    FOR_UNITS(unit, (uint64_t)a.nx * a.ny * a.segments) {
-        const Unit u = unit_of(a, unit);
+    HU_FOR_UNITS(unit, (uint64_t)a.nx * a.ny * a.segments) {
+        const ColumnUnit u = column_unit(a, unit);
         const uint32_t z = u.z0 + lane;
         const bool active = z < a.nz;
         const uint32_t id = active ? a.ids[u.base + z] : kEmpty;
@@ -186,7 +151,7 @@ __global__ void __launch_bounds__(256) k_over_columns(const OverArgs a)
             gather_counts(lands, id, lane, landed);
             if (h == h0) plate += (unsigned long long)__popcll(__ballot(is_held));
         }
-    } else FOR_UNITS(unit, (uint64_t)a.nx * a.ny) {                   // a unit is a whole (x, y) column
+    } else HU_FOR_UNITS(unit, (uint64_t)a.nx * a.ny) {                   // a unit is a whole (x, y) column
         const size_t base = (size_t)unit * a.pitch;
         const uint32_t v = a.up ? lane : 63u - lane;                  // the lane's position in the word: a higher one is above
         uint32_t carry_holder = kEmpty;                               // wave-uniform: the column open at the word's top
@@ -229,31 +194,15 @@ int over_args(const void* ids_dev, uint32_t* word_dev, const uint32_t dims[3], u
 {
     a = OverArgs{};
     if (!ids_dev || !word_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    for (int i = 0; i < 3; ++i)
-        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
-        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
-    if (axis < 0 || axis > 2) return hu_fail(HU_ERR_BAD_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
+    int rc;
+    if ((rc = lattice_of(dims, pitch, a)) || (rc = lattice_units(axis, a))) return rc;
     if (reach_sq > kMaxReach) return hu_fail(HU_ERR_BAD_ARG, "reach_sq must be at most 8");
-    if (of > 63u && of != kSolid) return hu_fail(HU_ERR_BAD_ARG, "of must be an instance index up to 63 or HU_OVERHANG_SOLID");
+    if ((rc = check_of(of, "HU_OVERHANG_SOLID"))) return rc;
     if (reinterpret_cast<uintptr_t>(word_dev) % 4u) return hu_fail(HU_ERR_BAD_ARG, "the depth word must be aligned to 4 bytes");
     a.ids = static_cast<const uint8_t*>(ids_dev);
     a.word = word_dev;
-    a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
     a.axis = (uint32_t)axis, a.reach_sq = reach_sq, a.of = of;
-    a.na = dims[axis];
-    a.segments = (a.nz + 63u) / 64u;
     return HU_OK;
-}
-
-// blocks of four wavefronts for a kernel that walks its units with FOR_UNITS: four units a wavefront at the least, so that
-// small lattices walk too, and at most kMaxBlocks blocks -- eight a compute unit of 256 --, which bounds the atomics on one
-// accumulator whatever the lattice
-constexpr uint64_t kMaxBlocks = 2048u;
-uint32_t walking_blocks(uint64_t units)
-{
-    const uint64_t blocks = (units + 15u) / 16u;
-    return (uint32_t)(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
 
 }  // namespace
@@ -267,8 +216,7 @@ int hu_overhang_first_layer(const void* ids_dev, uint32_t* word_dev, const uint3
     int rc;
     if ((rc = over_args(ids_dev, word_dev, dims, pitch, axis, 0u, of, a))) return rc;
     a.up = up != 0;
-    const uint32_t blocks = walking_blocks((uint64_t)a.nx * a.ny * a.segments);
-    hipLaunchKernelGGL(k_over_first, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(k_over_first, dim3(walking_blocks((uint64_t)a.nx * a.ny * a.segments, 4u)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     HU_HIP(hipGetLastError());
     return HU_OK;
 }
@@ -284,8 +232,7 @@ int hu_overhang_mark(const void* ids_dev, void* overhang_dev, uint32_t* word_dev
     a.up = up != 0;
     a.over = static_cast<uint8_t*>(overhang_dev);
     a.counts = reinterpret_cast<unsigned long long*>(counts_dev);
-    const uint32_t blocks = walking_blocks((uint64_t)a.nx * a.ny * a.segments);
-    hipLaunchKernelGGL(k_over_mark, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(k_over_mark, dim3(walking_blocks((uint64_t)a.nx * a.ny * a.segments, 4u)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     HU_HIP(hipGetLastError());
     return HU_OK;
 }
@@ -305,7 +252,7 @@ int hu_overhang_columns(const void* ids_dev, const void* overhang_dev, void* sup
     a.counts = reinterpret_cast<unsigned long long*>(counts_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (axis == 2) {
-        hipLaunchKernelGGL((k_over_columns<true>), dim3(walking_blocks((uint64_t)a.nx * a.ny)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_over_columns<true>), dim3(walking_blocks((uint64_t)a.nx * a.ny, 4u)), dim3(256), 0, s, a);
     } else {                                                          // a wavefront a unit: at most 65536 lines of 1024 words
         const uint64_t units = (uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments;
         hipLaunchKernelGGL((k_over_columns<false>), dim3((uint32_t)((units + 3u) / 4u)), dim3(256), 0, s, a);

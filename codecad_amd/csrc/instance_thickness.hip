@@ -25,19 +25,17 @@
 //     writes thin_ids (the id where thin, else 255; pitch as the ids) instead of distances and counts the thin samples per
 //     part: lane p of a wavefront gathers the count of part p over the wavefront's rows and adds it once at the end -- one
 //     atomic per accumulator and wavefront.
-// No kernel has a private array or scratch; byte offsets are 64-bit.  The entry points are at the end of this file.
-#include "instance_cells.hpp"
+// No kernel has a private array or scratch.  The volume's contract: id_volume.hpp.  The entry points are at the end of this file.
+#include "id_volume.hpp"
 
 using namespace hu_cells;
 
 namespace {
 
-constexpr uint32_t kEmpty = 255u;                       // instance_voxels.hip: the id of a sample inside no part
-constexpr uint32_t kSolid = HU_THICKNESS_SOLID;         // of: S is id != 255; any other of (<= 63): S is id == of
 constexpr uint32_t kMaxK = HU_THICKNESS_MAX_K;
 constexpr uint32_t kRows = HU_THICKNESS_LDS_ROWS;       // rows of 64 uint16 of k_thick_axis' LDS
 constexpr uint32_t kSegment = 64u + 2u * kMaxK + 2u;    // k_thick_z: a wavefront's inputs, 576
-static_assert(kMaxK == 255u && kRows == 256u && kSolid == kEmpty, "include/hip_util.h");
+static_assert(kMaxK == 255u && kRows == 256u, "include/hip_util.h");
 
 struct ThickArgs {
     const uint8_t* ids;                 // uint8[nx][ny][pitch] (z pass of transform 1; FINISH != 0)
@@ -54,8 +52,6 @@ struct ThickArgs {
     uint64_t stride, slab;              // ... elements between two positions, and between two slabs
 };
 
-__device__ __forceinline__ bool in_set(uint32_t id, uint32_t of) { return of == kSolid ? id != kEmpty : id == of; }
-
 // the stencil at one sample: tap(d) is in(i + d), d in [-K, K].  Wave-uniform trip count; best <= cap throughout.
 template <class Tap> __device__ __forceinline__ uint32_t stencil(uint32_t K, uint32_t cap, bool active, Tap tap)
 {
@@ -67,17 +63,6 @@ template <class Tap> __device__ __forceinline__ uint32_t stencil(uint32_t K, uin
         if (go) best = min(best, min(tap(-(int)k), tap((int)k)) + kk);
     }
     return best;
-}
-
-// lane p's `mine` += the lanes of this row that count and whose id is p, for every id present (wave-uniform loop)
-__device__ __forceinline__ void gather_counts(bool counted, uint32_t id, uint32_t lane, unsigned long long& mine)
-{
-    for (uint64_t todo = __ballot(counted); todo != 0ull;) {
-        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)id, (int)__builtin_ctzll(todo));
-        const uint64_t b = __ballot(counted && id == p);
-        todo &= ~b;
-        if (lane == (p & 63u)) mine += (unsigned long long)__popcll(b);
-    }
 }
 
 template <bool T2, bool LDS>
@@ -159,14 +144,10 @@ int thick_args(const uint32_t dims[3], uint32_t pitch, uint32_t K, uint32_t cap,
 {
     a = ThickArgs{};
     if (!dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    for (int i = 0; i < 3; ++i)
-        if (dims[i] == 0u || dims[i] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
-        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
+    if (int rc = lattice_of(dims, pitch, a)) return rc;
     if (cap > 65535u) return hu_fail(HU_ERR_BAD_ARG, "cap must be at most 65535");
     if (K > kMaxK) return hu_fail(HU_ERR_BAD_ARG, "K must be at most 255");
-    if (of > 63u && of != kSolid) return hu_fail(HU_ERR_BAD_ARG, "of must be an instance index up to 63 or HU_THICKNESS_SOLID");
-    a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
+    if (int rc = check_of(of, "HU_THICKNESS_SOLID")) return rc;
     a.K = K, a.cap = cap, a.of = of;
     return HU_OK;
 }

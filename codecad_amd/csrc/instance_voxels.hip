@@ -31,10 +31,10 @@
 // Evaluations are counted as the other kernels count them, live lanes x candidates the wavefront evaluated.  The
 // accumulators are n + 1 uint64: the samples each instance owns, then the bytes the retired children filled.
 // Built WITHOUT -structurizecfg-skip-uniform-regions (hip_util/builder.py FLAGGED_SOURCES).  The entry points are at the end of
-// this file.
+// this file.  What the kernels that walk the volume afterwards rely on: id_volume.hpp.
 #include <algorithm>
 
-#include "instance_cells.hpp"
+#include "id_volume.hpp"
 
 using namespace sdfk;
 using namespace hu_cells;
@@ -48,7 +48,6 @@ struct VoxelArgs {
     uint32_t pitch;                  // bytes of a z run: dims z rounded up to a multiple of 16
     uint32_t retire;                 // cells: a child whose lowest candidate is provably full is filled and leaves the lists
 };
-constexpr uint32_t kEmpty = 255u;    // the id of a sample inside no part
 constexpr uint32_t kNone = 64u;      // a lane without a full candidate
 
 struct VoxelRow {
@@ -249,8 +248,7 @@ int voxel_args(const void* table_dev, uint32_t n, const void* parents_dev, const
     if (!volume_dev || !acc_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
     if (!std::isfinite(step) || step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
-    if (pitch % 16u || pitch < dims[2] || pitch > 65536u)
-        return hu_fail(HU_ERR_BAD_ARG, "pitch must be a multiple of 16 from dims[2] to 65536");
+    if ((rc = check_pitch(dims, pitch))) return rc;
     if (reinterpret_cast<uintptr_t>(volume_dev) % 16u) return hu_fail(HU_ERR_BAD_ARG, "the volume must be aligned to 16 bytes");
     k.volume = static_cast<uint8_t*>(volume_dev);
     k.pitch = pitch;

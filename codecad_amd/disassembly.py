@@ -35,13 +35,12 @@ of keys.
 """
 import collections
 import collections.abc
-import ctypes
 import math
 
 import numpy
 
 from . import hip_util
-from .assembly_voxels import _device_volume
+from .assembly_voxels import _device_volume, _whole, _axis, _dims
 from .hip_util import manager as hip_manager, check
 
 NEVER = 0xffffffff              # no sample of j lies beyond a sample of i on any line of the axis
@@ -52,17 +51,10 @@ _ONES = 0xffffffffffffffff
 
 
 def _indices(parts, n, what):
-    whole = lambda k: isinstance(k, (int, numpy.integer)) and not isinstance(k, bool)     # noqa: E731
-    group = (parts,) if whole(parts) else tuple(parts) if isinstance(parts, collections.abc.Iterable) and not isinstance(parts, str) else None
-    if group is None or not all(whole(k) and 0 <= k < n for k in group):
+    group = (parts,) if _whole(parts, 0, n - 1) else tuple(parts) if isinstance(parts, collections.abc.Iterable) and not isinstance(parts, str) else None
+    if group is None or not all(_whole(k, 0, n - 1) for k in group):
         raise ValueError("%s must be indices of the %d visible instances, not %r" % (what, n, parts))
     return sorted({int(k) for k in group})
-
-
-def _axis(axis):
-    if not (isinstance(axis, (int, numpy.integer)) and not isinstance(axis, bool) and 0 <= axis <= 2):
-        raise ValueError("axis must be 0, 1 or 2, not %r" % (axis,))
-    return int(axis)
 
 
 class DisassemblyReport(collections.namedtuple("DisassemblyReport", "instances corner step dims part_ids counts distance witness "
@@ -143,7 +135,7 @@ def disassembly(asm, resolution, initial_capacity=None, max_bytes=2 ** 32):
         return report(numpy.full((3, n, n), NEVER, numpy.uint32), numpy.full((3, n, n, 3), -1, numpy.int32))
     lib, queue = hip_manager.lib, hip_manager.queue
     pz = volume.shape[2]
-    dims = (ctypes.c_uint32 * 3)(*(int(d) for d in voxels.dims))
+    dims = _dims(voxels.dims)
     keys = hip_util.Buffer(numpy.uint64, _KEYS, queue=queue)
     check(lib.hu_memset(keys.device_ptr, 0xff, keys.size, queue.handle), "hu_memset")
     for axis in range(3):

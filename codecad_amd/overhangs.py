@@ -48,34 +48,28 @@ nx * ny * pz; the labelling afterwards holds `support_ids` and the labels, 5: th
 5 * nx * ny * pz > max_bytes, and when the label volume would have more than 2^31 entries, before anything is launched.
 """
 import collections
-import ctypes
 
 import numpy
 
 from . import _instance_cells as cells
 from . import hip_util
-from .assembly_voxels import _device_volume, EMPTY
+from .assembly_voxels import _device_volume, _whole, _of_code, _axis, _dims, _cropped, _LabelMask, EMPTY
 from .assembly_components import SOLID, NONE, _components, _label_volume, _check_entries
 from .hip_util import manager as hip_manager, check
 
 MAX_REACH_SQ = 8                # include/hip_util.h HU_OVERHANG_MAX_REACH_SQ
 SAMPLE_BYTES = 5                # support_ids and the labels: what is held per sample at the peak
-_SOLID_CODE = 255               # include/hip_util.h HU_OVERHANG_SOLID
 _ACC = (4, 64)                  # uint64: O, P and L per part, then the plate landings and the depth word
 _PLATE, _WORD = 3 * 64, 3 * 64 + 1
 
 
-class OverhangReport(collections.namedtuple("OverhangReport", "instances corner step dims of axis up reach_sq first_layer part_ids "
+class OverhangReport(_LabelMask, collections.namedtuple("OverhangReport", "instances corner step dims of axis up reach_sq first_layer part_ids "
                                                               "overhang_ids support_ids landing_ids counts overhang_counts "
                                                               "support_counts landing_counts plate_landings supports labels "
                                                               "samples_evaluated traversals component_capacity_runs")):
     """`instances`, `corner`, `step`, `dims`, `part_ids`, `counts`, `samples_evaluated`, `traversals`: as in AssemblyVoxels;
     `component_capacity_runs`: as in ComponentsReport; every other field: the module's docstring."""
     __slots__ = ()
-
-    def mask(self, region):
-        """bool[nx, ny, nz]: the samples of `region` (a Component of `supports` or a label)."""
-        return self.labels == getattr(region, "label", region)
 
     def support_volume(self):
         """|P| * step^3: the material the supports take."""
@@ -91,10 +85,6 @@ class OverhangReport(collections.namedtuple("OverhangReport", "instances corner 
         return sum(self.overhang_counts) == 0
 
 
-def _small_int(v, most):
-    return isinstance(v, (int, numpy.integer)) and not isinstance(v, bool) and 0 <= v <= most
-
-
 def overhangs(asm, resolution, axis=2, up=True, reach_sq=1, of=SOLID, initial_components=None, initial_capacity=None,
               max_bytes=2 ** 32):
     """The samples of the visible instances of the 3D assembly `asm`, on the lattice of `interference(asm, resolution)`, that a
@@ -106,13 +96,10 @@ def overhangs(asm, resolution, axis=2, up=True, reach_sq=1, of=SOLID, initial_co
     cell list of the voxel traversal.  Raises ValueError for what assembly_voxels() refuses, for a bad `of`, `axis` or
     `reach_sq`, more than 2^31 label entries and for volumes of more than `max_bytes` bytes together."""
     n = len(cells.visible(asm, resolution))
-    if of != SOLID and not (_small_int(of, n - 1)):
-        raise ValueError("of must be SOLID or the index of one of the %d visible instances, not %r" % (n, of))
-    if not _small_int(axis, 2):
-        raise ValueError("axis must be 0, 1 or 2, not %r" % (axis,))
-    if not _small_int(reach_sq, MAX_REACH_SQ):
+    code, axis = _of_code(of, n), _axis(axis)
+    if not _whole(reach_sq, 0, MAX_REACH_SQ):
         raise ValueError("reach_sq must be an integer from 0 to %d, not %r" % (MAX_REACH_SQ, reach_sq))
-    axis, up, reach_sq = int(axis), bool(up), int(reach_sq)
+    up, reach_sq = bool(up), int(reach_sq)
     voxels, volume = _device_volume(asm, resolution, initial_capacity, True, max_bytes, sample_bytes=SAMPLE_BYTES,
                                     check_dims=_check_entries)
     shape = tuple(int(d) for d in voxels.dims)
@@ -127,8 +114,7 @@ def overhangs(asm, resolution, axis=2, up=True, reach_sq=1, of=SOLID, initial_co
                       numpy.full(shape, NONE, numpy.uint32), 0)
     lib, queue = hip_manager.lib, hip_manager.queue
     nx, ny, pz = volume.shape
-    dims = (ctypes.c_uint32 * 3)(*shape)
-    code = _SOLID_CODE if of == SOLID else int(of)
+    dims = _dims(shape)
     acc = hip_util.Buffer(numpy.uint64, _ACC, queue=queue)
     check(lib.hu_memset(acc.device_ptr, 0, acc.size, queue.handle), "hu_memset")
     word = acc.device_ptr + 8 * _WORD
@@ -138,7 +124,7 @@ def overhangs(asm, resolution, axis=2, up=True, reach_sq=1, of=SOLID, initial_co
                                queue.handle), "hu_overhang_mark")
     check(lib.hu_overhang_columns(volume.device_ptr, over.device_ptr, support.device_ptr, landing.device_ptr, word,
                                   acc.device_ptr + 8 * 64, dims, pz, axis, int(up), code, queue.handle), "hu_overhang_columns")
-    overhang_ids, support_ids, landing_ids = (numpy.ascontiguousarray(b.read()[:, :, :shape[2]]) for b in (over, support, landing))
+    overhang_ids, support_ids, landing_ids = (_cropped(b, shape[2]) for b in (over, support, landing))
     totals = acc.read()
     for b in (over, landing, volume, acc):
         b.release()

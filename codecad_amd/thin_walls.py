@@ -51,35 +51,29 @@ together: 7 bytes a sample; the labelling afterwards holds the thin ids and the 
 7 * nx * ny * pz > max_bytes, and when the label volume would have more than 2^31 entries, before anything is launched.
 """
 import collections
-import ctypes
 import math
 
 import numpy
 
 from . import _instance_cells as cells
 from . import hip_util
-from .assembly_voxels import _device_volume, EMPTY
+from .assembly_voxels import _device_volume, _of_code, _dims, _cropped, _LabelMask, EMPTY
 from .assembly_components import SOLID, NONE, _components, _label_volume, _check_entries
 from .hip_util import manager as hip_manager, check
 
 MAX_COVER_SQ = 65534            # C2 + 1 is the largest uint16
 SAMPLE_BYTES = 7                # the ids and three uint16 volumes: what is held per sample at the peak
 LDS_ROWS = 256                  # include/hip_util.h HU_THICKNESS_LDS_ROWS: rows of 64 uint16 a workgroup may stage
-_SOLID_CODE = 255               # include/hip_util.h HU_THICKNESS_SOLID
 _GLOBAL_TILE = 64               # positions along the axis a workgroup takes when it reads its taps from global memory
 _MAX_LDS_K = 96                 # the tile of the LDS path, LDS_ROWS - 2 K, is at least 64 up to here
 
 
-class ThinWallReport(collections.namedtuple("ThinWallReport", "instances corner step dims of radius_sq cover_sq part_ids depth_sq "
+class ThinWallReport(_LabelMask, collections.namedtuple("ThinWallReport", "instances corner step dims of radius_sq cover_sq part_ids depth_sq "
                                                               "thin_ids counts core_counts thin_counts regions labels "
                                                               "samples_evaluated traversals component_capacity_runs")):
     """`instances`, `corner`, `step`, `dims`, `part_ids`, `counts`, `samples_evaluated`, `traversals`: as in AssemblyVoxels;
     `component_capacity_runs`: as in ComponentsReport; every other field: the module's docstring."""
     __slots__ = ()
-
-    def mask(self, region):
-        """bool[nx, ny, nz]: the samples of `region` (a Component of `regions` or a label)."""
-        return self.labels == getattr(region, "label", region)
 
 
 def radii(step, min_thickness=None, radius_sq=None, cover_sq=None):
@@ -121,8 +115,7 @@ def thin_walls(asm, resolution, min_thickness=None, of=SOLID, radius_sq=None, co
     traversal.  Raises ValueError for what assembly_voxels() refuses, for a bad `of`, bad radii, more than 2^31 label entries
     and for volumes of more than `max_bytes` bytes together."""
     n = len(cells.visible(asm, resolution))
-    if of != SOLID and not (isinstance(of, (int, numpy.integer)) and not isinstance(of, bool) and 0 <= of < n):
-        raise ValueError("of must be SOLID or the index of one of the %d visible instances, not %r" % (n, of))
+    code = _of_code(of, n)
     r2, c2 = radii(numpy.float32(resolution), min_thickness, radius_sq, cover_sq)
     voxels, volume = _device_volume(asm, resolution, initial_capacity, True, max_bytes, sample_bytes=SAMPLE_BYTES,
                                     check_dims=_check_entries)
@@ -137,8 +130,7 @@ def thin_walls(asm, resolution, min_thickness=None, of=SOLID, radius_sq=None, co
                       numpy.full(shape, NONE, numpy.uint32), 0)
     lib, queue = hip_manager.lib, hip_manager.queue
     nx, ny, pz = volume.shape
-    dims = (ctypes.c_uint32 * 3)(*shape)
-    code = _SOLID_CODE if of == SOLID else int(of)
+    dims = _dims(shape)
     k1, k2 = math.isqrt(r2), math.isqrt(c2)
     z_lds = int(bool(lds))
 
@@ -165,8 +157,7 @@ def thin_walls(asm, resolution, min_thickness=None, of=SOLID, radius_sq=None, co
     other.release()
     thin = hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue)
     axis_pass(third, None, 0, k2, c2 + 1, c2 + 1, finish=2, thin=thin, counts=acc.device_ptr + 64 * 8)
-    depth_sq = numpy.ascontiguousarray(depth.read()[:, :, :shape[2]])
-    thin_ids = numpy.ascontiguousarray(thin.read()[:, :, :shape[2]])
+    depth_sq, thin_ids = _cropped(depth, shape[2]), _cropped(thin, shape[2])
     totals = acc.read()
     for b in (depth, third, volume, acc):
         b.release()

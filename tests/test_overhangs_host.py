@@ -374,7 +374,7 @@ def test_abi_of_the_new_entry_points():
         assert len(_lib.PROTOTYPES[name]) == len(proto.split(","))
         assert ("int %s(" % name) in integration
     constant = lambda name: int(re.search(r"#define %s (\d+)" % name, header).group(1))   # noqa: E731
-    assert constant("HU_OVERHANG_SOLID") == ov._SOLID_CODE == EMPTY
+    assert constant("HU_OVERHANG_SOLID") == av._SOLID_CODE == EMPTY
     assert constant("HU_OVERHANG_MAX_REACH_SQ") == ov.MAX_REACH_SQ
     assert ov._ACC == (4, 64) and (ov._PLATE, ov._WORD) == (192, 193)                 # the columns' counts start at row 1: 64 + 64 + 1
 

@@ -355,7 +355,7 @@ def test_abi_of_the_new_entry_points():
         assert len(_lib.PROTOTYPES[name]) == len(proto.split(","))
         assert ("int %s(" % name) in integration
     constant = lambda name: int(re.search(r"#define %s (\d+)" % name, header).group(1))   # noqa: E731
-    assert constant("HU_THICKNESS_SOLID") == tw._SOLID_CODE == EMPTY
+    assert constant("HU_THICKNESS_SOLID") == av._SOLID_CODE == EMPTY
     assert constant("HU_THICKNESS_LDS_ROWS") == tw.LDS_ROWS and constant("HU_THICKNESS_MAX_K") == 255 == scenes.isqrt(tw.MAX_COVER_SQ)
     assert all(sum(tw.axis_tile(k, True)) - 1 + 2 * k <= tw.LDS_ROWS for k in range(0, tw._MAX_LDS_K + 1))
     assert tw.axis_tile(tw._MAX_LDS_K, True) == (64, 1) and tw.axis_tile(tw._MAX_LDS_K + 1, True) == (64, 0)

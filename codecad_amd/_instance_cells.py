@@ -17,6 +17,7 @@ from . import nodes
 from . import hip_util
 from . import subdivision
 from .hip_util import manager as hip_manager, check
+from .hip_util._lib import CellsLaunch, CellsChildren
 
 MAX_INSTANCES = 64          # one bit each in a cell's candidate mask
 _ROW = 16                   # bytes per cell row {x0 | y0 << 16, z0, mask lo, mask hi}
@@ -66,11 +67,13 @@ def checked_lattice(instances, resolution, grow=0.0):
     return corner, step, dims
 
 
-def top_side(dims, first=16, factor=4):
+def top_side(dims, first=16, factor=4, most=None):
     """The side of the top level's cells: `first` samples, times `factor` (a level's cells per axis: 4 for the cubic
-    cells of the checks, 8 for the square tiles of a section) while there would be too many of them."""
+    cells of the checks, 8 for the square tiles of a section) while there would be more than `most` of them
+    (_MAX_TOP_CELLS unless a check has a cap of its own)."""
+    most = _MAX_TOP_CELLS if most is None else most
     side = first
-    while numpy.prod(-(-dims // side)) > _MAX_TOP_CELLS:
+    while numpy.prod(-(-numpy.asarray(dims, dtype=numpy.int64) // side)) > most:
         side *= factor
     return side
 
@@ -107,6 +110,19 @@ def cell_rows(wins, dims, side, least=2):
         rows[:, 1] = idx[:, 2] * side
         rows[:, 2] = (m & numpy.uint64(0xffffffff)).astype(numpy.uint32)
         rows[:, 3] = (m >> numpy.uint64(32)).astype(numpy.uint32)
+    return rows
+
+
+def all_rows(n, dims, side):
+    """Rows of the top level: every cell of `side` samples, every one of the n instances a candidate."""
+    counts = tuple(int(-(-d // side)) for d in dims)
+    idx = numpy.indices(counts).reshape(3, -1).T.astype(numpy.int64) * side
+    mask = (1 << n) - 1
+    rows = numpy.zeros((len(idx), 4), dtype=numpy.uint32)
+    rows[:, 0] = idx[:, 0] | (idx[:, 1] << 16)
+    rows[:, 1] = idx[:, 2]
+    rows[:, 2] = mask & 0xffffffff
+    rows[:, 3] = mask >> 32
     return rows
 
 
@@ -187,25 +203,30 @@ def _run(table, n, distance_only, lane_bytes, wins, top, sides, corner, step, di
     first[1:] = top
     parents = hip_util.Buffer(numpy.uint32, first.shape, queue=queue)
     parents.enqueue_write(first)
-    buffers, max_parents = [parents], len(top)
-    d = (ctypes.c_uint32 * 3)(*(int(v) for v in dims))
-    c = (ctypes.c_float * 3)(*(float(v) for v in corner))
-    evaluations = results.device_ptr + 16 * n_levels
-    instances = (table.device_ptr, n, distance_only, lane_bytes) + (() if wins is None else (wins.device_ptr,))
+    buffers = [parents]
+    # what every launch takes (include/hip_util.h hu_cells_launch); a level moves the parent fields on to its children
+    launch = CellsLaunch(table_dev=table.device_ptr, windows_dev=None if wins is None else wins.device_ptr,
+                         evaluations_dev=results.device_ptr + 16 * n_levels, stream=queue.handle, n=n, lane_bytes=lane_bytes,
+                         distance_only=distance_only, dims=tuple(int(v) for v in dims), corner=tuple(float(v) for v in corner), step=step)
+
+    def parents_are(buffer, capacity):
+        launch.parents_dev, launch.n_parents_dev, launch.max_parents = buffer.device_ptr + row_bytes, buffer.device_ptr, capacity
+
+    parents_are(parents, len(top))
+    accumulators_dev = results.device_ptr + head
+    extra = () if cells_extra is None else tuple(cells_extra) + (accumulators_dev,)
     for level, (side, capacity) in enumerate(zip(sides, capacities)):
         child = side // factor
         children = hip_util.Buffer(numpy.uint32, (capacity + 1, words), queue=queue)
         check(lib.hu_memset(children.device_ptr, 0, row_bytes, queue.handle), "hu_memset")
-        extra = () if cells_extra is None else tuple(cells_extra) + (results.device_ptr + head,)
-        check(getattr(lib, cells)(*instances, parents.device_ptr + row_bytes, parents.device_ptr, max_parents, child, d, c, *frame, step,
-                                  thr(child), children.device_ptr, children.device_ptr + row_bytes, capacity, *extra, evaluations,
-                                  queue.handle), cells)
+        listed = CellsChildren(counter_dev=children.device_ptr, children_dev=children.device_ptr + row_bytes, capacity=capacity,
+                               child_side=child, thr=thr(child))
+        check(getattr(lib, cells)(ctypes.byref(launch), ctypes.byref(listed), *frame, *extra), cells)
         check(lib.hu_memcpy_d2d(results.device_ptr + 16 * level, children.device_ptr, 16, queue.handle), "hu_memcpy_d2d")
         buffers.append(children)
-        parents, max_parents = children, capacity
-    for name, extra in finest:              # in this order, on the one stream
-        check(getattr(lib, name)(*instances, parents.device_ptr + row_bytes, parents.device_ptr, max_parents, d, c, *frame, step, *extra,
-                                 results.device_ptr + head, evaluations, queue.handle), name)
+        parents_are(children, capacity)
+    for name, own in finest:                # in this order, on the one stream
+        check(getattr(lib, name)(ctypes.byref(launch), *frame, *own, accumulators_dev), name)
     got = results.read()                    # the one synchronisation
     for b in buffers + [results]:
         b.release()
@@ -218,10 +239,11 @@ def traverse(instances, top, side, corner, step, dims, initial_capacity, pair_dt
     """The traversal from the top-level rows `top` (cells of `side` samples), run again with larger lists while one
     overflowed -> (evaluations of the last run, pair accumulators [n, n], runs).  What the check decides: `pair_dtype`
     and `pair_init` ({field: initial value}) of the accumulators; `thr`, child side -> float32 threshold of a level;
-    `cells`, the entry point of the coarser levels; `finest`, [(entry point of the finest level, its arguments between
-    step and the accumulators)], launched in that order; `wins`, clearance's windows (int64[n, 2, 3]), uploaded for
+    `cells`, the entry point of the coarser levels; `finest`, [(entry point of the finest level, its own arguments between
+    `frame` and the accumulators)], launched in that order; `frame`, what both take first of their own arguments (a
+    section's plane); `wins`, clearance's windows (int64[n, 2, 3]), uploaded for
     its entry points; `row_bytes`, the size of a row of `top` and of every list (16, or 32 for rows with a second mask);
-    `cells_extra`, arguments of `cells` between its capacity and its evaluations, after which it then also gets the
+    `cells_extra`, arguments of `cells` after `frame`, after which it then also gets the
     accumulators (the mass properties' levels add to them); `accumulators`, their number when it is not n * n."""
     queue = hip_manager.queue
     n = len(instances)

@@ -129,17 +129,7 @@ def sort_triangles(records):
 def top_cells(wins, cubes, side, everywhere=False):
     """uint32[m, 4] rows of the top level: the cells of `side` cubes that a window reaches, each with the instances whose
     windows do; `everywhere`: every cell with every instance."""
-    if not everywhere:
-        return cells.cell_rows(wins, cubes, side, least=1)
-    n_cells = -(-cubes // side)
-    idx = numpy.indices(tuple(int(v) for v in n_cells)).reshape(3, -1).T.astype(numpy.int64) * side
-    mask = (1 << len(wins)) - 1
-    rows = numpy.zeros((len(idx), 4), dtype=numpy.uint32)
-    rows[:, 0] = idx[:, 0] | (idx[:, 1] << 16)
-    rows[:, 1] = idx[:, 2]
-    rows[:, 2] = mask & 0xffffffff
-    rows[:, 3] = mask >> 32
-    return rows
+    return cells.all_rows(len(wins), cubes, side) if everywhere else cells.cell_rows(wins, cubes, side, least=1)
 
 
 def first_capacity(wins):

@@ -912,12 +912,6 @@ int hu_mass_properties_level_indirect(hu_tape t, const double* parents_dev, cons
     return launch_classify<true, true>(t, a, max_parents, dims, stream);
 }
 
-int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, size_t bytes, int* distance_only_out,
-                          uint32_t* lane_bytes)
-{
-    return hu_instance_table(tapes, n, 0, table_host, bytes, distance_only_out, lane_bytes);
-}
-
 int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void* table_host, size_t bytes, int* distance_only_out,
                       uint32_t* lane_bytes)
 {

@@ -5,7 +5,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/hip_util.h"
 #include "tape_format.hpp"
+
+// the launch records of the C ABI (hip_util.h): hip_util/_lib.py mirrors them field by field
+static_assert(sizeof(hu_cells_launch) == HU_CELLS_LAUNCH_BYTES, "hu_cells_launch must have the size hip_util.h states");
+static_assert(sizeof(hu_cells_children) == HU_CELLS_CHILDREN_BYTES, "hu_cells_children must have the size hip_util.h states");
 
 namespace hu_cells {
 
@@ -16,7 +21,7 @@ struct InstanceRec {
     const float* extra;
     uint32_t n4, pad;
 };
-static_assert(sizeof(InstanceRec) == 24, "hu_interference_table writes 24-byte records");
+static_assert(sizeof(InstanceRec) == 24, "hu_instance_table writes 24-byte records");
 
 // interference: the accumulators of the pair (i, j), i < j, at pairs[i * n_instances + j]: samples inside both, the sums
 // of their x, y, z indices, and the box of those indices (lo starts at 0xffffffff, hi at 0)

@@ -109,67 +109,67 @@ __device__ __forceinline__ void add_samples(Acc* acc, bool both, uint64_t b, uin
 // host side: the entry points over instance cells (instance_pairs.hip, instance_section.hip, instance_mass.hip)
 // ------------------------------------------------------------------------------------------
 
-// What every entry point over instance cells checks and fills.  The entry points of `clearance` also want the windows,
-// a z extent within 16 bits (the witness packs an index into 16 bits per axis) and a finite step >= 0; interference's
-// were released without those checks and keep accepting what they accepted.
-inline int cells_args(bool clearance, const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev,
-                      const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                      uint64_t* evaluations_dev, Args& a)
+// What every entry point over instance cells checks and fills, from its launch record (hip_util.h).  The entry points of
+// `clearance` also want the windows, a z extent within 16 bits (the witness packs an index into 16 bits per axis) and a
+// finite step >= 0; interference's were released without those checks and keep accepting what they accepted.  `planar`:
+// the lattice lies on a plane, {dims[0], dims[1], 1}, and dims[2] is not read.
+inline int cells_args(bool clearance, const hu_cells_launch* l, Args& a, bool planar = false)
 {
-    if (!table_dev || (clearance && !windows_dev) || !n_parents_dev || !dims || !corner || !evaluations_dev || (!parents_dev && max_parents))
+    if (!l || !l->table_dev || (clearance && !l->windows_dev) || !l->n_parents_dev || !l->evaluations_dev || (!l->parents_dev && l->max_parents))
         return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (n == 0 || n > 64u) return hu_fail(HU_ERR_BAD_ARG, "1..64 instances");
+    const uint32_t dims[3] = {l->dims[0], l->dims[1], planar ? 1u : l->dims[2]};
+    if (l->n == 0 || l->n > 64u) return hu_fail(HU_ERR_BAD_ARG, "1..64 instances");
     if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0 || dims[0] > 65536u || dims[1] > 65536u || (clearance && dims[2] > 65536u))
         return hu_fail(HU_ERR_BAD_ARG, clearance ? "lattice dims must be in 1..65536" : "lattice dims must be positive, x and y at most 65536");
-    if (clearance && (!std::isfinite(step) || step < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    if (clearance && (!std::isfinite(l->step) || l->step < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
     std::memset(&a, 0, sizeof(a));
-    a.table = static_cast<const InstanceRec*>(table_dev);
-    a.windows = windows_dev;
-    a.n_instances = n;
-    a.parents = static_cast<const uint4*>(parents_dev);
-    a.n_parents_dev = n_parents_dev;
-    a.max_parents = max_parents;
+    a.table = static_cast<const InstanceRec*>(l->table_dev);
+    a.windows = l->windows_dev;
+    a.n_instances = l->n;
+    a.parents = static_cast<const uint4*>(l->parents_dev);
+    a.n_parents_dev = l->n_parents_dev;
+    a.max_parents = l->max_parents;
     for (int i = 0; i < 3; ++i) {
         a.dims[i] = dims[i];
-        a.corner[i] = corner[i];
+        a.corner[i] = l->corner[i];
     }
-    a.step = step;
-    a.evaluations = reinterpret_cast<unsigned long long*>(evaluations_dev);
+    a.step = l->step;
+    a.evaluations = reinterpret_cast<unsigned long long*>(l->evaluations_dev);
     return HU_OK;
 }
 
-// ... and what those of a level above the finest one add: the children's list, their side and the threshold that drops a
-// candidate.  The bounds of child_side and thr are each check's own: its entry point tests them after this.
-inline int cells_children(Args& a, uint32_t child_side, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity)
+// ... and what those of a level above the finest one add, from its record: the children's list, their side and the threshold
+// that drops a candidate.  The bounds of child_side and thr are each check's own: its entry point tests them after this.
+inline int cells_children(Args& a, const hu_cells_children* c)
 {
-    if (!counter_dev || (!children_dev && capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    a.child_side = child_side;
-    a.thr = thr;
-    a.counter = counter_dev;
-    a.children = static_cast<uint4*>(children_dev);
-    a.capacity = capacity;
+    if (!c || !c->counter_dev || (!c->children_dev && c->capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    a.child_side = c->child_side;
+    a.thr = c->thr;
+    a.counter = c->counter_dev;
+    a.children = static_cast<uint4*>(c->children_dev);
+    a.capacity = c->capacity;
     return HU_OK;
 }
 
-// The launch of `kernel` over the cells of `a`, which is `k` or a part of it: a wavefront per cell, in workgroups of four
-// wavefronts while their LDS fits 48 KiB (host.hpp hu_workgroup), as launch_shape() sizes the one-voxel interpreter kernels.
-// A lane's LDS: `lane_bytes`, the register file of the largest instance, then `extra_lane_bytes` (clearance's w area at the
-// finest level, the section's at its tiles: 4 bytes per instance and lane).
+// The launch of `kernel` over the cells of `a`, which is `k` or a part of it, on the record's stream: a wavefront per cell,
+// in workgroups of four wavefronts while their LDS fits 48 KiB (host.hpp hu_workgroup), as launch_shape() sizes the one-voxel
+// interpreter kernels.  A lane's LDS: the record's lane_bytes, the register file of the largest instance, then
+// `extra_lane_bytes` (clearance's w area at the finest level, the section's at its tiles: 4 bytes per instance and lane).
 template <class K>
-int cells_launch(void (*kernel)(K), K& k, Args& a, uint32_t lane_bytes, size_t extra_lane_bytes, void* stream)
+int cells_launch(void (*kernel)(K), K& k, Args& a, const hu_cells_launch& l, size_t extra_lane_bytes)
 {
     uint32_t block;
     size_t lds;
     int rc;
     // the scalar slots and every area after the register file are read as 4-byte words at lane_bytes * block
-    if (lane_bytes % 4u) return hu_fail(HU_ERR_BAD_ARG, "lane_bytes must be a multiple of 4");
-    if ((rc = hu_workgroup((size_t)lane_bytes + extra_lane_bytes, block, lds))) return rc;
+    if (l.lane_bytes % 4u) return hu_fail(HU_ERR_BAD_ARG, "lane_bytes must be a multiple of 4");
+    if ((rc = hu_workgroup((size_t)l.lane_bytes + extra_lane_bytes, block, lds))) return rc;
     if ((rc = hu_ensure_attrs())) return rc;
-    a.scratch_offset = lane_bytes * block;
+    a.scratch_offset = l.lane_bytes * block;
     const uint64_t blocks = ((uint64_t)a.max_parents + block / 64u - 1) / (block / 64u);
     if (blocks == 0) return HU_OK;
     if (blocks > 0x7fffffffull) return hu_fail(HU_ERR_BAD_ARG, "cell list too long for one launch");
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(block), lds, (hipStream_t)stream, k);
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(block), lds, (hipStream_t)l.stream, k);
     HU_HIP(hipGetLastError());
     return HU_OK;
 }

@@ -248,28 +248,24 @@ int gap_layout(void* acc_dev, uint32_t n, uint32_t top_side, GapLayout& out)
 
 // What the three entry points check and fill alike: cells_args() of interference's lattice, and what the witness needs:
 // every index within 16 bits.
-int gap_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-             const uint32_t dims[3], const float corner[3], float step, uint64_t* evaluations_dev, GapArgs& g)
+int gap_args(const hu_cells_launch* l, GapArgs& g)
 {
     int rc;
     std::memset(&g, 0, sizeof(g));
-    if ((rc = cells_args(false, table_dev, n, nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, g.c)))
-        return rc;
-    if (dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(step) || step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    if ((rc = cells_args(false, l, g.c))) return rc;
+    if (l->dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (!std::isfinite(l->step) || l->step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
     return HU_OK;
 }
 
 // a launch over the finest cells: the leaf (level rows and the copy of the keys first) or the witness
-int gap_finest(bool witness, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-               const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-               uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int gap_finest(bool witness, const hu_cells_launch* l, uint32_t top_side, void* acc_dev)
 {
     GapArgs g;
     GapLayout at;
     int rc;
-    if ((rc = gap_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, g))) return rc;
-    if ((rc = gap_layout(acc_dev, n, top_side, at))) return rc;
+    if ((rc = gap_args(l, g))) return rc;
+    if ((rc = gap_layout(acc_dev, l->n, top_side, at))) return rc;
     g.c.child_side = 1u;
     g.witness = at.witness;
     if (witness) {
@@ -277,10 +273,10 @@ int gap_finest(bool witness, const void* table_dev, uint32_t n, int distance_onl
     } else {
         g.bound = at.key_array(at.levels);
         g.next = at.key_array(at.levels + 1u);
-        HU_HIP(hipMemcpyAsync(at.rows + (at.levels - 1u), n_parents_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        HU_HIP(hipMemcpyAsync(g.next, g.bound, at.n2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HU_HIP(hipMemcpyAsync(at.rows + (at.levels - 1u), l->n_parents_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)l->stream));
+        HU_HIP(hipMemcpyAsync(g.next, g.bound, at.n2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)l->stream));
     }
-    return cells_launch(kGapTable[witness ? 2 : 1][distance_only_kernel != 0], g, g.c, lane_bytes, 4u * n, stream);
+    return cells_launch(kGapTable[witness ? 2 : 1][l->distance_only != 0], g, g.c, *l, 4u * l->n);
 }
 
 }  // namespace
@@ -292,46 +288,38 @@ hipError_t hu_cells::allow_big_lds_gap(size_t bytes)
 
 extern "C" {
 
-int hu_separation_cells(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                        const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
-                        const float corner[3], float step, float r, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                        uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_separation_cells(const hu_cells_launch* launch, const hu_cells_children* children, uint32_t top_side, void* acc_dev)
 {
     GapArgs g;
     GapLayout at;
     int rc;
-    if ((rc = gap_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, g))) return rc;
-    if ((rc = cells_children(g.c, child_side, r, counter_dev, children_dev, capacity))) return rc;
-    if ((rc = gap_layout(acc_dev, n, top_side, at))) return rc;
-    if (!std::isfinite(r) || r < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "r must be finite and not negative");
+    if ((rc = gap_args(launch, g))) return rc;
+    if ((rc = cells_children(g.c, children))) return rc;
+    if ((rc = gap_layout(acc_dev, launch->n, top_side, at))) return rc;
+    if (!std::isfinite(g.c.thr) || g.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "r must be finite and not negative");
     // the level of the cells whose children have child_side: 0 for the top side's
     uint32_t level = at.levels;
     for (uint32_t s = top_side / 4u, l = 0; s >= 4u; s /= 4u, ++l)
-        if (s == child_side) level = l;
+        if (s == g.c.child_side) level = l;
     if (level == at.levels) return hu_fail(HU_ERR_BAD_ARG, "child_side must be top_side / 4^k, at least 4");
     g.bound = at.key_array(level);
     g.next = at.key_array(level + 1u);
     g.witness = at.witness;
+    hipStream_t stream = (hipStream_t)launch->stream;
     if (level)
-        HU_HIP(hipMemcpyAsync(at.rows + (level - 1u), n_parents_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    HU_HIP(hipMemcpyAsync(g.next, g.bound, at.n2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return cells_launch(kGapTable[0][distance_only_kernel != 0], g, g.c, lane_bytes, 4u * n, stream);
+        HU_HIP(hipMemcpyAsync(at.rows + (level - 1u), launch->n_parents_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    HU_HIP(hipMemcpyAsync(g.next, g.bound, at.n2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    return cells_launch(kGapTable[0][launch->distance_only != 0], g, g.c, *launch, 4u * launch->n);
 }
 
-int hu_separation_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                       const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                       uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_separation_leaf(const hu_cells_launch* launch, uint32_t top_side, void* acc_dev)
 {
-    return gap_finest(false, table_dev, n, distance_only_kernel, lane_bytes, parents_dev, n_parents_dev, max_parents, dims, corner, step,
-                      top_side, acc_dev, evaluations_dev, stream);
+    return gap_finest(false, launch, top_side, acc_dev);
 }
 
-int hu_separation_witness(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                          uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_separation_witness(const hu_cells_launch* launch, uint32_t top_side, void* acc_dev)
 {
-    return gap_finest(true, table_dev, n, distance_only_kernel, lane_bytes, parents_dev, n_parents_dev, max_parents, dims, corner, step,
-                      top_side, acc_dev, evaluations_dev, stream);
+    return gap_finest(true, launch, top_side, acc_dev);
 }
 
 }  // extern "C"

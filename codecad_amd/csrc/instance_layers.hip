@@ -32,15 +32,12 @@ constexpr uint32_t kMaxLayers = 1u << 20;     // (a record keeps the layer in th
 
 // What both entry points of the layered outlines check and fill: outline_frame_args() and the table of the layers' corners.
 // `corner` is checked and otherwise unused.
-int layer_args(const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-               uint32_t max_parents, const uint32_t dims[2], const float corner[3], const float u[3], const float v[3],
-               const float* layer_corners_dev, uint32_t n_layers, float step, uint64_t* evaluations_dev, LayerArgs& t)
+int layer_args(const hu_cells_launch* l, const float u[3], const float v[3], const float* layer_corners_dev, uint32_t n_layers, LayerArgs& t)
 {
-    if (!dims || !u || !v || !layer_corners_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (!l || !u || !v || !layer_corners_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (n_layers == 0u || n_layers > kMaxLayers) return hu_fail(HU_ERR_BAD_ARG, "1..2^20 layers");
     int rc;
-    if ((rc = outline_frame_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, step, evaluations_dev, t)))
-        return rc;
+    if ((rc = outline_frame_args(l, u, v, t))) return rc;
     t.layer_corners = reinterpret_cast<const float4*>(layer_corners_dev);
     t.n_layers = n_layers;
     return HU_OK;
@@ -55,42 +52,25 @@ hipError_t hu_cells::allow_big_lds_layers(size_t bytes)
 
 extern "C" {
 
-int hu_layer_tiles(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
-                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                   const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], const float* layer_corners_dev,
-                   uint32_t n_layers, float step, float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                   uint64_t* evaluations_dev, void* stream)
+int hu_layer_tiles(const hu_cells_launch* launch, const hu_cells_children* children, const float u[3], const float v[3],
+                   const float* layer_corners_dev, uint32_t n_layers)
 {
     LayerArgs t;
     int rc;
-    if ((rc = layer_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, layer_corners_dev, n_layers,
-                         step, evaluations_dev, t)))
-        return rc;
-    if ((rc = cells_children(t.c, child_side, radius, counter_dev, children_dev, capacity))) return rc;
-    if (child_side < 8u || child_side > 8192u || (child_side & (child_side - 1u)))
-        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 8..8192");
-    if (std::isnan(radius) || radius < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
-    return cells_launch(kLayerTable[0][distance_only_kernel != 0], t, t.c, lane_bytes, 0u, stream);
+    if ((rc = layer_args(launch, u, v, layer_corners_dev, n_layers, t))) return rc;
+    if ((rc = outline_children(t.c, children))) return rc;
+    return cells_launch(kLayerTable[0][launch->distance_only != 0], t, t.c, *launch, 0u);
 }
 
-int hu_layer_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
-                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
-                  const float corner[3], const float u[3], const float v[3], const float* layer_corners_dev, uint32_t n_layers,
-                  float step, void* segments_dev, uint32_t segment_capacity, uint64_t* totals_dev, uint64_t* evaluations_dev,
-                  void* stream)
+int hu_layer_leaf(const hu_cells_launch* launch, const float u[3], const float v[3], const float* layer_corners_dev, uint32_t n_layers,
+                  void* segments_dev, uint32_t segment_capacity, uint64_t* totals_dev)
 {
     LayerArgs t;
     int rc;
-    if ((rc = layer_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, layer_corners_dev, n_layers,
-                         step, evaluations_dev, t)))
-        return rc;
-    if (!totals_dev || (!segments_dev && segment_capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    t.c.child_side = 1u;
-    t.c.pairs = totals_dev;
-    t.segments = static_cast<uint4*>(segments_dev);
-    t.segment_capacity = segment_capacity;
+    if ((rc = layer_args(launch, u, v, layer_corners_dev, n_layers, t))) return rc;
+    if ((rc = outline_segments(t, segments_dev, segment_capacity, totals_dev))) return rc;
     // the 81 values of a tile: 128 floats per wavefront, 8 bytes per lane, after the register file
-    return cells_launch(kLayerTable[1][distance_only_kernel != 0], t, t.c, lane_bytes, 8u, stream);
+    return cells_launch(kLayerTable[1][launch->distance_only != 0], t, t.c, *launch, 8u);
 }
 
 }  // extern "C"

@@ -256,15 +256,14 @@ void (*const kMassTable[2][2])(Args) = {
 
 // What both entry points of the assembly's mass properties check and fill: cells_args() of interference's lattice, and
 // what the sums need: every index within 16 bits, and a lattice whose second-moment sums fit 64 bits.
-int mass_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-              const uint32_t dims[3], const float corner[3], float step, void* acc_dev, uint64_t* evaluations_dev, Args& a)
+int mass_args(const hu_cells_launch* l, void* acc_dev, Args& a)
 {
     int rc;
-    if ((rc = cells_args(false, table_dev, n, nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
-        return rc;
+    if ((rc = cells_args(false, l, a))) return rc;
     if (!acc_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    const uint32_t* dims = l->dims;
     if (dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(step) || step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    if (!std::isfinite(l->step) || l->step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
     const uint64_t longest = std::max(dims[0], std::max(dims[1], dims[2])) - 1u;
     const unsigned __int128 bound = (unsigned __int128)dims[0] * dims[1] * dims[2] * longest * longest;
     if (bound >> 64) return hu_fail(HU_ERR_BAD_ARG, "the lattice's second-moment index sums would not fit 64 bits");
@@ -281,33 +280,28 @@ hipError_t hu_cells::allow_big_lds_mass(size_t bytes)
 
 extern "C" {
 
-int hu_assembly_mass_cells(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                           const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
-                           const float corner[3], float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                           int retire, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_assembly_mass_cells(const hu_cells_launch* launch, const hu_cells_children* children, int retire, void* acc_dev)
 {
     Args a;
     int rc;
-    if ((rc = mass_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, acc_dev, evaluations_dev, a))) return rc;
-    if ((rc = cells_children(a, child_side, thr, counter_dev, children_dev, capacity))) return rc;
-    if (child_side < 4u || child_side > 16384u || (child_side & (child_side - 1u)))
+    if ((rc = mass_args(launch, acc_dev, a))) return rc;
+    if ((rc = cells_children(a, children))) return rc;
+    if (a.child_side < 4u || a.child_side > 16384u || (a.child_side & (a.child_side - 1u)))
         return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
-    if (!std::isfinite(thr) || thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
-    if (max_parents > 0x7fffffffu || capacity > 0x7fffffffu) return hu_fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
+    if (!std::isfinite(a.thr) || a.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    if (a.max_parents > 0x7fffffffu || a.capacity > 0x7fffffffu) return hu_fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
     a.flags = retire ? kMassRetire : 0u;
-    return cells_launch(kMassTable[0][distance_only_kernel != 0], a, a, lane_bytes, 0u, stream);
+    return cells_launch(kMassTable[0][launch->distance_only != 0], a, a, *launch, 0u);
 }
 
-int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                          void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_assembly_mass_leaf(const hu_cells_launch* launch, void* acc_dev)
 {
     Args a;
     int rc;
-    if ((rc = mass_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, acc_dev, evaluations_dev, a))) return rc;
-    if (max_parents > 0x7fffffffu) return hu_fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
+    if ((rc = mass_args(launch, acc_dev, a))) return rc;
+    if (a.max_parents > 0x7fffffffu) return hu_fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
     a.child_side = 1u;
-    return cells_launch(kMassTable[1][distance_only_kernel != 0], a, a, lane_bytes, 0u, stream);
+    return cells_launch(kMassTable[1][launch->distance_only != 0], a, a, *launch, 0u);
 }
 
 }  // extern "C"

@@ -211,40 +211,32 @@ hipError_t hu_cells::allow_big_lds_mesh(size_t bytes)
 
 extern "C" {
 
-int hu_mesh_cells(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
-                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                  const uint32_t dims[3], const float corner[3], float step, float radius, uint32_t* counter_dev, void* children_dev,
-                  uint32_t capacity, uint64_t* evaluations_dev, void* stream)
+int hu_mesh_cells(const hu_cells_launch* launch, const hu_cells_children* children)
 {
     MeshArgs t;
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, t.c)))
-        return rc;
-    if ((rc = cells_children(t.c, child_side, radius, counter_dev, children_dev, capacity))) return rc;
-    if (child_side < 4u || child_side > 16384u || (child_side & (child_side - 1u)))
+    if ((rc = cells_args(true, launch, t.c))) return rc;
+    if ((rc = cells_children(t.c, children))) return rc;
+    if (t.c.child_side < 4u || t.c.child_side > 16384u || (t.c.child_side & (t.c.child_side - 1u)))
         return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
-    if (std::isnan(radius) || radius < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
-    return cells_launch(kMeshTable[0][distance_only_kernel != 0], t, t.c, lane_bytes, 0u, stream);
+    if (std::isnan(t.c.thr) || t.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
+    return cells_launch(kMeshTable[0][launch->distance_only != 0], t, t.c, *launch, 0u);
 }
 
-int hu_mesh_leaf_instances(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
-                           const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3],
-                           const float corner[3], float step, void* triangles_dev, uint32_t triangle_capacity, uint64_t* totals_dev,
-                           uint64_t* evaluations_dev, void* stream)
+int hu_mesh_leaf_instances(const hu_cells_launch* launch, void* triangles_dev, uint32_t triangle_capacity, uint64_t* totals_dev)
 {
     MeshArgs t;
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, t.c)))
-        return rc;
+    if ((rc = cells_args(true, launch, t.c))) return rc;
     if (!totals_dev || (!triangles_dev && triangle_capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     t.c.child_side = 1u;
     t.c.pairs = totals_dev;
     t.triangles = static_cast<uint4*>(triangles_dev);
     t.triangle_capacity = triangle_capacity;
     // the 125 values of a cell: 128 floats per wavefront, 8 bytes per lane, after the register file
-    return cells_launch(kMeshTable[1][distance_only_kernel != 0], t, t.c, lane_bytes, 8u, stream);
+    return cells_launch(kMeshTable[1][launch->distance_only != 0], t, t.c, *launch, 8u);
 }
 
 }  // extern "C"

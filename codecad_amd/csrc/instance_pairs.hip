@@ -229,38 +229,31 @@ void (*const kKernels[])(Args) = {
 };
 
 // a level of cells above the finest one, of either check
-int cells_level(bool clearance, const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                uint32_t child_side, const uint32_t dims[3], const float corner[3], float step, float thr, uint32_t* counter_dev,
-                void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream)
+int cells_level(bool clearance, const hu_cells_launch* l, const hu_cells_children* c)
 {
     Args a;
     int rc;
-    if ((rc = cells_args(clearance, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
-        return rc;
-    if ((rc = cells_children(a, child_side, thr, counter_dev, children_dev, capacity))) return rc;
-    if (child_side < 4u || child_side > 16384u) return hu_fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
-    if (clearance && (!std::isfinite(thr) || thr < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
-    const auto kernel = clearance ? (distance_only_kernel ? k_instance_cells<true, true> : k_instance_cells<false, true>)
-                                  : (distance_only_kernel ? k_instance_cells<true, false> : k_instance_cells<false, false>);
-    return cells_launch(kernel, a, a, lane_bytes, 0u, stream);
+    if ((rc = cells_args(clearance, l, a))) return rc;
+    if ((rc = cells_children(a, c))) return rc;
+    if (a.child_side < 4u || a.child_side > 16384u) return hu_fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
+    if (clearance && (!std::isfinite(a.thr) || a.thr < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    const auto kernel = clearance ? (l->distance_only ? k_instance_cells<true, true> : k_instance_cells<false, true>)
+                                  : (l->distance_only ? k_instance_cells<true, false> : k_instance_cells<false, false>);
+    return cells_launch(kernel, a, a, *l, 0u);
 }
 
-// a launch over the finest cells: interference's leaf (no windows, no t), clearance's leaf or witness
-int cells_finest(void (*kernel)(Args), bool clearance, const void* table_dev, uint32_t n, uint32_t lane_bytes, const uint32_t* windows_dev,
-                 const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3],
-                 const float corner[3], float step, float t, void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+// a launch over the finest cells, kernels[distance_only]: interference's leaf (no windows, no t), clearance's leaf or witness
+int cells_finest(void (*const (&kernels)[2])(Args), bool clearance, const hu_cells_launch* l, float t, void* pairs_dev)
 {
     Args a;
     int rc;
-    if ((rc = cells_args(clearance, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, a)))
-        return rc;
+    if ((rc = cells_args(clearance, l, a))) return rc;
     if (!pairs_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (clearance && (!std::isfinite(t) || t < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "t must be finite and not negative");
     a.child_side = 1u;
     a.t = t;
     a.pairs = pairs_dev;
-    return cells_launch(kernel, a, a, lane_bytes, clearance ? 4u * n : 0u, stream);
+    return cells_launch(kernels[l->distance_only != 0], a, a, *l, clearance ? 4u * l->n : 0u);
 }
 
 }  // namespace
@@ -275,51 +268,29 @@ hipError_t hu_cells::allow_big_lds(size_t bytes)
 
 extern "C" {
 
-int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
-                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                                   uint64_t* evaluations_dev, void* stream)
+int hu_interference_cells_indirect(const hu_cells_launch* launch, const hu_cells_children* children)
 {
-    return cells_level(false, table_dev, n, distance_only_kernel, lane_bytes, nullptr, parents_dev, n_parents_dev, max_parents,
-                       child_side, dims, corner, step, thr, counter_dev, children_dev, capacity, evaluations_dev, stream);
+    return cells_level(false, launch, children);
 }
 
-int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
-                                  uint64_t* evaluations_dev, void* stream)
+int hu_interference_leaf_indirect(const hu_cells_launch* launch, void* pairs_dev)
 {
-    return cells_finest(distance_only_kernel ? k_interference_leaf<true> : k_interference_leaf<false>, false, table_dev, n, lane_bytes,
-                        nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, 0.0f, pairs_dev, evaluations_dev, stream);
+    return cells_finest({k_interference_leaf<false>, k_interference_leaf<true>}, false, launch, 0.0f, pairs_dev);
 }
 
-int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                                uint32_t max_parents, uint32_t child_side, const uint32_t dims[3], const float corner[3],
-                                float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                                uint64_t* evaluations_dev, void* stream)
+int hu_clearance_cells_indirect(const hu_cells_launch* launch, const hu_cells_children* children)
 {
-    return cells_level(true, table_dev, n, distance_only_kernel, lane_bytes, windows_dev, parents_dev, n_parents_dev, max_parents,
-                       child_side, dims, corner, step, thr, counter_dev, children_dev, capacity, evaluations_dev, stream);
+    return cells_level(true, launch, children);
 }
 
-int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                               const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                               uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
-                               void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+int hu_clearance_leaf_indirect(const hu_cells_launch* launch, float t, void* pairs_dev)
 {
-    return cells_finest(distance_only_kernel ? k_clearance_leaf<true> : k_clearance_leaf<false>, true, table_dev, n, lane_bytes,
-                        windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+    return cells_finest({k_clearance_leaf<false>, k_clearance_leaf<true>}, true, launch, t, pairs_dev);
 }
 
-int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes,
-                                  const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                                  uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
-                                  void* pairs_dev, uint64_t* evaluations_dev, void* stream)
+int hu_clearance_witness_indirect(const hu_cells_launch* launch, float t, void* pairs_dev)
 {
-    return cells_finest(distance_only_kernel ? k_clearance_witness<true> : k_clearance_witness<false>, true, table_dev, n, lane_bytes,
-                        windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, step, t, pairs_dev, evaluations_dev, stream);
+    return cells_finest({k_clearance_witness<false>, k_clearance_witness<true>}, true, launch, t, pairs_dev);
 }
 
 }  // extern "C"

@@ -171,19 +171,15 @@ void (*const kSectionTable[2][2][2])(SectionArgs) = {
 
 // What both entry points of the section check and fill: cells_args() of a lattice {dims u, dims v, 1} with windows, and the
 // plane's frame.
-int section_args(const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                 uint32_t max_parents, const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], float step,
-                 uint64_t* evaluations_dev, SectionArgs& t)
+int section_args(const hu_cells_launch* l, const float u[3], const float v[3], SectionArgs& t)
 {
-    if (!dims || !u || !v) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    const uint32_t dims3[3] = {dims[0], dims[1], 1u};
+    if (!u || !v) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims3, corner, step, evaluations_dev, t.c)))
-        return rc;
-    if ((uint64_t)dims[0] * dims[1] > (1ull << 28)) return hu_fail(HU_ERR_BAD_ARG, "a section holds at most 2^28 samples");
+    if ((rc = cells_args(true, l, t.c, true))) return rc;
+    if ((uint64_t)l->dims[0] * l->dims[1] > (1ull << 28)) return hu_fail(HU_ERR_BAD_ARG, "a section holds at most 2^28 samples");
     for (int i = 0; i < 3; ++i) {
-        if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(corner[i])) return hu_fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
+        if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(l->corner[i])) return hu_fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
         t.u[i] = u[i];
         t.v[i] = v[i];
     }
@@ -204,34 +200,26 @@ hipError_t hu_cells::allow_big_lds_section(size_t bytes)
 
 extern "C" {
 
-int hu_section_tiles(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
-                     const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                     const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], int with_distance, float step,
-                     float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity, uint64_t* evaluations_dev,
-                     void* stream)
+int hu_section_tiles(const hu_cells_launch* launch, const hu_cells_children* children, const float u[3], const float v[3],
+                     int with_distance)
 {
     SectionArgs t;
     int rc;
-    if ((rc = section_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, step, evaluations_dev, t)))
-        return rc;
-    if ((rc = cells_children(t.c, child_side, radius, counter_dev, children_dev, capacity))) return rc;
-    if (child_side < 8u || child_side > 8192u || (child_side & (child_side - 1u)))
+    if ((rc = section_args(launch, u, v, t))) return rc;
+    if ((rc = cells_children(t.c, children))) return rc;
+    if (t.c.child_side < 8u || t.c.child_side > 8192u || (t.c.child_side & (t.c.child_side - 1u)))
         return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 8..8192");
-    if (std::isnan(radius) || radius < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
+    if (std::isnan(t.c.thr) || t.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
     // WITH_DISTANCE keeps every candidate's w at the children's centres: 4 bytes per instance and lane after the register file
-    return cells_launch(kSectionTable[0][distance_only_kernel != 0][with_distance != 0], t, t.c, lane_bytes, with_distance ? 4u * n : 0u, stream);
+    return cells_launch(kSectionTable[0][launch->distance_only != 0][with_distance != 0], t, t.c, *launch, with_distance ? 4u * launch->n : 0u);
 }
 
-int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const uint32_t* windows_dev,
-                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
-                    const float corner[3], const float u[3], const float v[3], int with_distance, float step, int32_t* part_ids_dev,
-                    uint8_t* inside_count_dev, float* distance_dev, int32_t* nearest_dev, void* acc_dev, uint64_t* evaluations_dev,
-                    void* stream)
+int hu_section_leaf(const hu_cells_launch* launch, const float u[3], const float v[3], int with_distance, int32_t* part_ids_dev,
+                    uint8_t* inside_count_dev, float* distance_dev, int32_t* nearest_dev, void* acc_dev)
 {
     SectionArgs t;
     int rc;
-    if ((rc = section_args(table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims, corner, u, v, step, evaluations_dev, t)))
-        return rc;
+    if ((rc = section_args(launch, u, v, t))) return rc;
     if (!part_ids_dev || !inside_count_dev || !acc_dev || (with_distance && (!distance_dev || !nearest_dev)))
         return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     t.c.child_side = 1u;
@@ -240,7 +228,7 @@ int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only_kernel,
     t.inside_count = inside_count_dev;
     t.distance = distance_dev;
     t.nearest = nearest_dev;
-    return cells_launch(kSectionTable[1][distance_only_kernel != 0][with_distance != 0], t, t.c, lane_bytes, 0u, stream);
+    return cells_launch(kSectionTable[1][launch->distance_only != 0][with_distance != 0], t, t.c, *launch, 0u);
 }
 
 }  // extern "C"

@@ -237,18 +237,15 @@ void (*const kVoxelTable[2][2])(VoxelArgs) = {
 
 // What both entry points of the part-id volume check and fill: cells_args() of interference's lattice, every index within
 // 16 bits, and a volume whose z runs are `pitch` bytes: a multiple of 16 that holds dims z.
-int voxel_args(const void* table_dev, uint32_t n, const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-               const uint32_t dims[3], const float corner[3], float step, void* volume_dev, uint32_t pitch, void* acc_dev,
-               uint64_t* evaluations_dev, VoxelArgs& k)
+int voxel_args(const hu_cells_launch* l, void* volume_dev, uint32_t pitch, void* acc_dev, VoxelArgs& k)
 {
     int rc;
     k = VoxelArgs{};
-    if ((rc = cells_args(false, table_dev, n, nullptr, parents_dev, n_parents_dev, max_parents, dims, corner, step, evaluations_dev, k.c)))
-        return rc;
+    if ((rc = cells_args(false, l, k.c))) return rc;
     if (!volume_dev || !acc_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(step) || step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
-    if ((rc = check_pitch(dims, pitch))) return rc;
+    if (l->dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
+    if (!std::isfinite(l->step) || l->step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
+    if ((rc = check_pitch(l->dims, pitch))) return rc;
     if (reinterpret_cast<uintptr_t>(volume_dev) % 16u) return hu_fail(HU_ERR_BAD_ARG, "the volume must be aligned to 16 bytes");
     k.volume = static_cast<uint8_t*>(volume_dev);
     k.pitch = pitch;
@@ -265,33 +262,27 @@ hipError_t hu_cells::allow_big_lds_voxels(size_t bytes)
 
 extern "C" {
 
-int hu_assembly_voxels_cells(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                             const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
-                             const float corner[3], float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                             int retire, void* volume_dev, uint32_t pitch, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_assembly_voxels_cells(const hu_cells_launch* launch, const hu_cells_children* children, int retire, void* volume_dev,
+                             uint32_t pitch, void* acc_dev)
 {
     VoxelArgs k;
     int rc;
-    if ((rc = voxel_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, volume_dev, pitch, acc_dev, evaluations_dev, k)))
-        return rc;
-    if ((rc = cells_children(k.c, child_side, thr, counter_dev, children_dev, capacity))) return rc;
-    if (child_side < 4u || child_side > 16384u || (child_side & (child_side - 1u)))
+    if ((rc = voxel_args(launch, volume_dev, pitch, acc_dev, k))) return rc;
+    if ((rc = cells_children(k.c, children))) return rc;
+    if (k.c.child_side < 4u || k.c.child_side > 16384u || (k.c.child_side & (k.c.child_side - 1u)))
         return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
-    if (!std::isfinite(thr) || thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
+    if (!std::isfinite(k.c.thr) || k.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
     k.retire = retire ? 1u : 0u;
-    return cells_launch(kVoxelTable[0][distance_only_kernel != 0], k, k.c, lane_bytes, 0u, stream);
+    return cells_launch(kVoxelTable[0][launch->distance_only != 0], k, k.c, *launch, 0u);
 }
 
-int hu_assembly_voxels_leaf(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const void* parents_dev,
-                            const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                            void* volume_dev, uint32_t pitch, void* acc_dev, uint64_t* evaluations_dev, void* stream)
+int hu_assembly_voxels_leaf(const hu_cells_launch* launch, void* volume_dev, uint32_t pitch, void* acc_dev)
 {
     VoxelArgs k;
     int rc;
-    if ((rc = voxel_args(table_dev, n, parents_dev, n_parents_dev, max_parents, dims, corner, step, volume_dev, pitch, acc_dev, evaluations_dev, k)))
-        return rc;
+    if ((rc = voxel_args(launch, volume_dev, pitch, acc_dev, k))) return rc;
     k.c.child_side = 1u;
-    return cells_launch(kVoxelTable[1][distance_only_kernel != 0], k, k.c, lane_bytes, 0u, stream);
+    return cells_launch(kVoxelTable[1][launch->distance_only != 0], k, k.c, *launch, 0u);
 }
 
 }  // extern "C"

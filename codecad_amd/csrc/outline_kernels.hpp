@@ -192,21 +192,40 @@ template <bool DO, class A> __device__ __forceinline__ void outline_leaf(const A
 // What the entry points of both units check and fill alike: cells_args() of a lattice of squares {dims a, dims b, 1} with
 // windows, and the plane's frame.
 template <class A>
-int outline_frame_args(const void* table_dev, uint32_t n, const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                       uint32_t max_parents, const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], float step,
-                       uint64_t* evaluations_dev, A& t)
+int outline_frame_args(const hu_cells_launch* l, const float u[3], const float v[3], A& t)
 {
-    if (!dims || !u || !v) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    const uint32_t dims3[3] = {dims[0], dims[1], 1u};
+    if (!u || !v) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, table_dev, n, windows_dev, parents_dev, n_parents_dev, max_parents, dims3, corner, step, evaluations_dev, t.c)))
-        return rc;
+    if ((rc = cells_args(true, l, t.c, true))) return rc;
     for (int i = 0; i < 3; ++i) {
-        if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(corner[i])) return hu_fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
+        if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(l->corner[i])) return hu_fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
         t.u[i] = u[i];
         t.v[i] = v[i];
     }
+    return HU_OK;
+}
+
+// ... what their tile levels add: cells_children() and the bounds of a tile's side and radius
+inline int outline_children(Args& a, const hu_cells_children* c)
+{
+    int rc;
+    if ((rc = cells_children(a, c))) return rc;
+    if (a.child_side < 8u || a.child_side > 8192u || (a.child_side & (a.child_side - 1u)))
+        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 8..8192");
+    if (std::isnan(a.thr) || a.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
+    return HU_OK;
+}
+
+// ... and their leaves: the segment records and their totals
+template <class A>
+int outline_segments(A& t, void* segments_dev, uint32_t segment_capacity, uint64_t* totals_dev)
+{
+    if (!totals_dev || (!segments_dev && segment_capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    t.c.child_side = 1u;
+    t.c.pairs = totals_dev;
+    t.segments = static_cast<uint4*>(segments_dev);
+    t.segment_capacity = segment_capacity;
     return HU_OK;
 }
 

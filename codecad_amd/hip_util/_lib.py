@@ -12,6 +12,21 @@ _u3 = _c.POINTER(_c.c_uint32)
 _d3 = _c.POINTER(_c.c_double)
 _pvp = _c.POINTER(_c.c_void_p)
 
+
+class CellsLaunch(_c.Structure):
+    """hu_cells_launch (include/hip_util.h): what every launch over instance cells takes."""
+    _fields_ = [("table_dev", _vp), ("windows_dev", _vp), ("parents_dev", _vp), ("n_parents_dev", _vp), ("evaluations_dev", _vp),
+                ("stream", _vp), ("n", _u32), ("lane_bytes", _u32), ("max_parents", _u32), ("distance_only", _c.c_int32),
+                ("dims", _u32 * 3), ("corner", _f * 3), ("step", _f)]
+
+
+class CellsChildren(_c.Structure):
+    """hu_cells_children: what a level above the finest one adds."""
+    _fields_ = [("counter_dev", _vp), ("children_dev", _vp), ("capacity", _u32), ("child_side", _u32), ("thr", _f)]
+
+
+_L, _C = _c.POINTER(CellsLaunch), _c.POINTER(CellsChildren)
+
 # name -> argtypes; every function returns int except hu_last_error
 PROTOTYPES = {
     "hu_abi_version": [],
@@ -57,28 +72,27 @@ PROTOTYPES = {
     "hu_mass_properties_level_indirect": [_vp, _vp, _vp, _u32, _d, _u3, _f, _f, _vp, _vp, _vp, _u32, _vp],
     "hu_mass_properties_level_owned": [_vp, _vp, _vp, _u32, _d, _u3, _f, _f, _vp, _vp, _vp, _u32, _u32, _u32, _vp],
     "hu_mass_integrals_indirect": [_vp, _vp, _vp, _u32, _d, _vp, _u32, _vp],
-    "hu_interference_table": [_c.POINTER(_vp), _u32, _vp, _sz, _c.POINTER(_i), _c.POINTER(_u32)],
     "hu_instance_table": [_c.POINTER(_vp), _u32, _i, _vp, _sz, _c.POINTER(_i), _c.POINTER(_u32)],
-    "hu_interference_cells_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
-    "hu_interference_leaf_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _vp, _vp, _vp],
-    "hu_clearance_cells_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
-    "hu_clearance_leaf_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _f, _vp, _vp, _vp],
-    "hu_clearance_witness_indirect": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _f, _vp, _vp, _vp],
-    "hu_section_tiles": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f4, _f4, _i, _f, _f, _vp, _vp, _u32, _vp, _vp],
-    "hu_section_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f4, _f4, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "hu_outline_tiles": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f4, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
-    "hu_outline_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f4, _f4, _f, _vp, _u32, _vp, _vp, _vp],
-    "hu_layer_tiles": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f4, _f4, _vp, _u32, _f, _f, _vp, _vp, _u32, _vp, _vp],
-    "hu_layer_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f4, _f4, _vp, _u32, _f, _vp, _u32, _vp, _vp, _vp],
-    "hu_mesh_cells": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _vp, _vp],
-    "hu_mesh_leaf_instances": [_vp, _u32, _i, _u32, _vp, _vp, _vp, _u32, _u3, _f4, _f, _vp, _u32, _vp, _vp, _vp],
-    "hu_assembly_mass_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _i, _vp, _vp, _vp],
-    "hu_assembly_mass_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _vp, _vp, _vp],
-    "hu_separation_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
-    "hu_separation_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _u32, _vp, _vp, _vp],
-    "hu_separation_witness": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _u32, _vp, _vp, _vp],
-    "hu_assembly_voxels_cells": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u32, _u3, _f4, _f, _f, _vp, _vp, _u32, _i, _vp, _u32, _vp, _vp, _vp],
-    "hu_assembly_voxels_leaf": [_vp, _u32, _i, _u32, _vp, _vp, _u32, _u3, _f4, _f, _vp, _u32, _vp, _vp, _vp],
+    "hu_interference_cells_indirect": [_L, _C],
+    "hu_interference_leaf_indirect": [_L, _vp],
+    "hu_clearance_cells_indirect": [_L, _C],
+    "hu_clearance_leaf_indirect": [_L, _f, _vp],
+    "hu_clearance_witness_indirect": [_L, _f, _vp],
+    "hu_section_tiles": [_L, _C, _f4, _f4, _i],
+    "hu_section_leaf": [_L, _f4, _f4, _i, _vp, _vp, _vp, _vp, _vp],
+    "hu_outline_tiles": [_L, _C, _f4, _f4],
+    "hu_outline_leaf": [_L, _f4, _f4, _vp, _u32, _vp],
+    "hu_layer_tiles": [_L, _C, _f4, _f4, _vp, _u32],
+    "hu_layer_leaf": [_L, _f4, _f4, _vp, _u32, _vp, _u32, _vp],
+    "hu_mesh_cells": [_L, _C],
+    "hu_mesh_leaf_instances": [_L, _vp, _u32, _vp],
+    "hu_assembly_mass_cells": [_L, _C, _i, _vp],
+    "hu_assembly_mass_leaf": [_L, _vp],
+    "hu_separation_cells": [_L, _C, _u32, _vp],
+    "hu_separation_leaf": [_L, _u32, _vp],
+    "hu_separation_witness": [_L, _u32, _vp],
+    "hu_assembly_voxels_cells": [_L, _C, _i, _vp, _u32, _vp],
+    "hu_assembly_voxels_leaf": [_L, _vp, _u32, _vp],
     "hu_components_local": [_vp, _vp, _u3, _u32, _i, _i, _vp],
     "hu_components_merge": [_vp, _u3, _u32, _i, _vp],
     "hu_components_flatten": [_vp, _u3, _u32, _vp],
@@ -165,7 +179,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_char_p if name == "hu_last_error" else ctypes.c_int
-    if lib.hu_abi_version() != 1:
+    if lib.hu_abi_version() != 2:
         raise RuntimeError("libhip_util.so ABI version mismatch")
     _lib = lib
     return lib

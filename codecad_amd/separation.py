@@ -77,23 +77,10 @@ class SeparationReport(collections.namedtuple("SeparationReport",
 
 def top_side(dims):
     """The side of the top level's cells: the smallest 16 * 4^k with at most _MAX_TOP_CELLS of them."""
-    side = 16
-    while numpy.prod(-(-numpy.asarray(dims, dtype=numpy.int64) // side)) > _MAX_TOP_CELLS:
-        side *= 4
-    return side
+    return cells.top_side(dims, most=_MAX_TOP_CELLS)
 
 
-def top_rows(n, dims, side):
-    """Rows of the top level: every cell of `side` samples, every one of the n instances a candidate."""
-    counts = [int(-(-d // side)) for d in dims]
-    idx = numpy.stack(numpy.meshgrid(*(numpy.arange(c, dtype=numpy.int64) * side for c in counts), indexing="ij"), axis=-1).reshape(-1, 3)
-    mask = (1 << n) - 1
-    rows = numpy.zeros((len(idx), 4), dtype=numpy.uint32)
-    rows[:, 0] = idx[:, 0] | (idx[:, 1] << 16)
-    rows[:, 1] = idx[:, 2]
-    rows[:, 2] = mask & 0xffffffff
-    rows[:, 3] = mask >> 32
-    return rows
+top_rows = cells.all_rows
 
 
 def radius(child, step):

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HU_ABI_VERSION 1
+#define HU_ABI_VERSION 2
 
 enum hu_status {
     HU_OK = 0,
@@ -194,12 +194,39 @@ int hu_mass_properties_level_owned(hu_tape t, const double* parents_dev, const u
 int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev,
                                uint32_t max_parents, double s, double* out_dev, uint32_t rows, void* stream);
 
+/* ---- the launch records of the entry points over instance cells ------------------------------------
+ * Every entry point from here to hu_mesh_leaf_instances (hu_instance_table apart) launches one kernel over a list of cells
+ * and takes what such a launch needs as ONE record, hu_cells_launch; those of a level above the finest one also take the
+ * children's list as hu_cells_children.  Then come the check's own arguments.  The records are read during the call and
+ * not kept: a caller may fill one, and change its parent fields from level to level.  A NULL record is HU_ERR_BAD_ARG. */
+typedef struct hu_cells_launch {        /* what every launch over instance cells takes */
+    const void* table_dev;              /* hu_instance_table's records */
+    const uint32_t* windows_dev;        /* n x 6; NULL for entry points that take none, which never read it */
+    const void* parents_dev;            /* rows after the list's header */
+    const uint32_t* n_parents_dev;      /* word 0 of the list's header */
+    uint64_t* evaluations_dev;
+    void* stream;
+    uint32_t n, lane_bytes, max_parents;   /* n and lane_bytes as hu_instance_table gave them */
+    int32_t distance_only;              /* as hu_instance_table gave it */
+    uint32_t dims[3];                   /* section, outline and layer entry points read [0] and [1] only */
+    float corner[3];
+    float step;
+} hu_cells_launch;
+typedef struct hu_cells_children {      /* ... and what a level above the finest adds */
+    uint32_t* counter_dev;              /* word 0 of the children's header */
+    void* children_dev;                 /* rows after it */
+    uint32_t capacity, child_side;
+    float thr;                          /* the "radius" or "r" of the section, outline, layer, mesh and separation levels */
+} hu_cells_children;
+#define HU_CELLS_LAUNCH_BYTES 96
+#define HU_CELLS_CHILDREN_BYTES 32
+
 /* ---- interference between the instances of an assembly (codecad_amd/interference.py) --------------
  * The instances' tapes are evaluated one at a time by the interpreter; the kernels reach them through a device
  * table of 24-byte records, n <= 64 (one bit each in a cell's candidate mask).  A cell list is a [header row |
  * rows...] buffer of 16-byte rows {x0 | y0 << 16, z0, mask lo, mask hi}, header word 0 its length; a cell is a cube
  * of lattice samples (corner + step * index, per axis) whose first sample is (x0, y0, z0).
- * hu_interference_table: no device work.  Writes the table of `tapes` into table_host (host memory of at least
+ * hu_instance_table: no device work.  Writes the table of `tapes` into table_host (host memory of at least
  *   n * 24 bytes; the caller uploads it): every instance's distance-only program when all have one (*distance_only
  *   = 1), else every instance's full program, and *lane_bytes, the LDS bytes per lane of a register file that holds
  *   every instance's (one layout for all: the wavefronts of a workgroup run different instances at once).
@@ -211,26 +238,16 @@ int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_d
  *   min x, y, z; uint32 max x, y, z; 8 bytes unused).
  * Both read the number of parents from *n_parents_dev (at most max_parents are there) and add the sample
  * evaluations they perform to *evaluations_dev. */
-int hu_interference_table(const hu_tape* tapes, uint32_t n, void* table_host, size_t bytes, int* distance_only,
-                          uint32_t* lane_bytes);
-/* The same table for a caller that says which programs it wants: full_programs != 0 writes every instance's FULL
- * program (*distance_only = 0) whether or not all have a distance-only one -- the ray caster over instances needs the
- * directions --, and reports a register file of one float4 slot at least (*lane_bytes >= 16) even when no program
- * stores a value; full_programs = 0 is hu_interference_table. */
+/* full_programs != 0 writes every instance's FULL program (*distance_only = 0) whether or not all have a distance-only
+ * one -- the ray caster over instances needs the directions --, and reports a register file of one float4 slot at least
+ * (*lane_bytes >= 16) even when no program stores a value. */
 int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void* table_host, size_t bytes,
                       int* distance_only, uint32_t* lane_bytes);
-int hu_interference_cells_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
-                                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                   uint32_t child_side, const uint32_t dims[3], const float corner[3], float step,
-                                   float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                                   uint64_t* evaluations_dev, void* stream);
-int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
-                                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                  const uint32_t dims[3], const float corner[3], float step, void* pairs_dev,
-                                  uint64_t* evaluations_dev, void* stream);
+int hu_interference_cells_indirect(const hu_cells_launch* launch, const hu_cells_children* children);
+int hu_interference_leaf_indirect(const hu_cells_launch* launch, void* pairs_dev);
 
 /* ---- clearance (near misses) between the instances of an assembly (codecad_amd/clearance.py) ----
- * The interference traversal with a threshold: the same table (hu_interference_table), cell lists and lattice.  Each
+ * The interference traversal with a threshold: the same table (hu_instance_table), cell lists and lattice.  Each
  * also takes windows_dev, n x 6 uint32 {lo x, y, z, hi x, y, z}: the lattice indices at which instance k may be near,
  * inclusive.  A sample is near the pair (i, j) when it lies in both windows and w_i < t, w_j < t (strictly); there
  * v = max(w_i, w_j).  dims at most 65536 per axis; step, t and thr finite and not negative.
@@ -244,19 +261,9 @@ int hu_interference_leaf_indirect(const void* table_dev, uint32_t n, int distanc
  * hu_clearance_witness_indirect: after the leaf launch, over the same list and accumulators: each pair's witness
  *   becomes the least x << 32 | y << 16 | z of its near samples whose v has the pair's key.
  * All read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
-int hu_clearance_cells_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
-                                const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                                uint32_t max_parents, uint32_t child_side, const uint32_t dims[3], const float corner[3],
-                                float step, float thr, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                                uint64_t* evaluations_dev, void* stream);
-int hu_clearance_leaf_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
-                               const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                               uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
-                               void* pairs_dev, uint64_t* evaluations_dev, void* stream);
-int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
-                                  const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                                  uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step, float t,
-                                  void* pairs_dev, uint64_t* evaluations_dev, void* stream);
+int hu_clearance_cells_indirect(const hu_cells_launch* launch, const hu_cells_children* children);
+int hu_clearance_leaf_indirect(const hu_cells_launch* launch, float t, void* pairs_dev);
+int hu_clearance_witness_indirect(const hu_cells_launch* launch, float t, void* pairs_dev);
 
 /* ---- the planar section of an assembly (codecad_amd/section.py) --------------------------------
  * A 2D lattice of dims[0] x dims[1] samples on a plane, sample (i, j) at (corner + u * (step * i)) + v * (step * j) per
@@ -272,16 +279,11 @@ int hu_clearance_witness_indirect(const void* table_dev, uint32_t n, int distanc
  *   that are in no row are left as they are.  acc_dev: n * n accumulators of hu_interference_leaf_indirect's layout (third
  *   index 0), [k * n + k] over the samples inside k, [i * n + j] (i < j) over those inside both.
  * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
-int hu_section_tiles(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                     const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                     const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], int with_distance,
-                     float step, float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity,
-                     uint64_t* evaluations_dev, void* stream);
-int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
-                    const float corner[3], const float u[3], const float v[3], int with_distance, float step,
+int hu_section_tiles(const hu_cells_launch* launch, const hu_cells_children* children, const float u[3], const float v[3],
+                     int with_distance);
+int hu_section_leaf(const hu_cells_launch* launch, const float u[3], const float v[3], int with_distance,
                     int32_t* part_ids_dev, uint8_t* inside_count_dev, float* distance_dev, int32_t* nearest_dev,
-                    void* acc_dev, uint64_t* evaluations_dev, void* stream);
+                    void* acc_dev);
 
 /* ---- the outlines of an assembly's section (codecad_amd/section_outlines.py) -------------------
  * The section's lattice with a ring of samples around it: samples carry the shifted index s = (i + 1, j + 1), 0 .. dims[0]
@@ -304,15 +306,9 @@ int hu_section_leaf(const void* table_dev, uint32_t n, int distance_only, uint32
  *   records at or past segment_capacity are counted and not stored (segments_dev may be NULL for a capacity of 0).
  * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform (samples and children
  * past the lattice's rim not counted) to *evaluations_dev. */
-int hu_outline_tiles(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                     const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                     const uint32_t dims[2], const float corner[3], const float u[3], const float v[3], float step,
-                     float radius, uint32_t* counter_dev, void* children_dev, uint32_t capacity, uint64_t* evaluations_dev,
-                     void* stream);
-int hu_outline_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                    const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
-                    const float corner[3], const float u[3], const float v[3], float step, void* segments_dev,
-                    uint32_t segment_capacity, uint64_t* totals_dev, uint64_t* evaluations_dev, void* stream);
+int hu_outline_tiles(const hu_cells_launch* launch, const hu_cells_children* children, const float u[3], const float v[3]);
+int hu_outline_leaf(const hu_cells_launch* launch, const float u[3], const float v[3], void* segments_dev,
+                    uint32_t segment_capacity, uint64_t* totals_dev);
 
 /* ---- the layered outlines of an assembly (codecad_amd/layer_outlines.py) -----------------------
  * The outlines above on a stack of n_layers parallel planes, every layer in one traversal.  The layers share the table, the
@@ -324,16 +320,10 @@ int hu_outline_leaf(const void* table_dev, uint32_t n, int distance_only, uint32
  * hu_layer_leaf: hu_outline_leaf on the row's layer, with records {a | b << 16, k | e_from << 8 | e_to << 10 | layer << 12,
  *   float t_from, float t_to}; totals_dev counts over all layers.
  * Every other argument, check and count is that of the outline entry points. */
-int hu_layer_tiles(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                   const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                   const uint32_t dims[2], const float corner[3], const float u[3], const float v[3],
-                   const float* layer_corners_dev, uint32_t n_layers, float step, float radius, uint32_t* counter_dev,
-                   void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream);
-int hu_layer_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[2],
-                  const float corner[3], const float u[3], const float v[3], const float* layer_corners_dev,
-                  uint32_t n_layers, float step, void* segments_dev, uint32_t segment_capacity, uint64_t* totals_dev,
-                  uint64_t* evaluations_dev, void* stream);
+int hu_layer_tiles(const hu_cells_launch* launch, const hu_cells_children* children, const float u[3], const float v[3],
+                   const float* layer_corners_dev, uint32_t n_layers);
+int hu_layer_leaf(const hu_cells_launch* launch, const float u[3], const float v[3], const float* layer_corners_dev,
+                  uint32_t n_layers, void* segments_dev, uint32_t segment_capacity, uint64_t* totals_dev);
 
 /* ---- the mass properties of an assembly (codecad_amd/assembly_mass.py) -------------------------
  * The lattice, the instance table and the [header row | rows...] lists of the interference entry points, with rows (and a
@@ -351,13 +341,8 @@ int hu_layer_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t
  * hu_assembly_mass_leaf: a cell of 4^3 samples per parent row; full instances are inside at every sample, the other
  *   candidates are evaluated at every sample.
  * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
-int hu_assembly_mass_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                           const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
-                           const float corner[3], float step, float thr, uint32_t* counter_dev, void* children_dev,
-                           uint32_t capacity, int retire, void* acc_dev, uint64_t* evaluations_dev, void* stream);
-int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
-                          float step, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+int hu_assembly_mass_cells(const hu_cells_launch* launch, const hu_cells_children* children, int retire, void* acc_dev);
+int hu_assembly_mass_leaf(const hu_cells_launch* launch, void* acc_dev);
 
 /* ---- the least gap of every pair of instances (codecad_amd/separation.py) -----------------------
  * The lattice, the instance table and the 16-byte rows of the interference entry points, every index within 16 bits; step
@@ -375,16 +360,9 @@ int hu_assembly_mass_leaf(const void* table_dev, uint32_t n, int distance_only, 
  * hu_separation_witness: after the leaf launch, over the same list: each pair's witness becomes the least
  *   x << 32 | y << 16 | z of the samples whose v has the pair's final key.
  * All read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
-int hu_separation_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                        const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
-                        const float corner[3], float step, float r, uint32_t* counter_dev, void* children_dev,
-                        uint32_t capacity, uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream);
-int hu_separation_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                       const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
-                       float step, uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream);
-int hu_separation_witness(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                          const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
-                          float step, uint32_t top_side, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+int hu_separation_cells(const hu_cells_launch* launch, const hu_cells_children* children, uint32_t top_side, void* acc_dev);
+int hu_separation_leaf(const hu_cells_launch* launch, uint32_t top_side, void* acc_dev);
+int hu_separation_witness(const hu_cells_launch* launch, uint32_t top_side, void* acc_dev);
 
 /* ---- the part-id volume of an assembly (codecad_amd/assembly_voxels.py) -------------------------
  * The lattice, the instance table and the [header row | rows...] lists of the interference entry points, 16-byte rows
@@ -403,14 +381,9 @@ int hu_separation_witness(const void* table_dev, uint32_t n, int distance_only, 
  * hu_assembly_voxels_leaf: a cell of 4^3 samples per parent row; every candidate but a capped one is evaluated at every
  *   sample; each z run of four samples is written as one dword (255 past dims[2]).
  * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform to *evaluations_dev. */
-int hu_assembly_voxels_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                             const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side, const uint32_t dims[3],
-                             const float corner[3], float step, float thr, uint32_t* counter_dev, void* children_dev,
-                             uint32_t capacity, int retire, void* volume_dev, uint32_t pitch, void* acc_dev,
-                             uint64_t* evaluations_dev, void* stream);
-int hu_assembly_voxels_leaf(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const void* parents_dev,
-                            const uint32_t* n_parents_dev, uint32_t max_parents, const uint32_t dims[3], const float corner[3],
-                            float step, void* volume_dev, uint32_t pitch, void* acc_dev, uint64_t* evaluations_dev, void* stream);
+int hu_assembly_voxels_cells(const hu_cells_launch* launch, const hu_cells_children* children, int retire, void* volume_dev,
+                             uint32_t pitch, void* acc_dev);
+int hu_assembly_voxels_leaf(const hu_cells_launch* launch, void* volume_dev, uint32_t pitch, void* acc_dev);
 
 /* ---- connected components of the part-id volume (codecad_amd/assembly_components.py) -----------
  * volume_dev: the uint8[dims[0]][dims[1]][pitch] volume of the entry points above, still on the device.  S is its samples
@@ -539,15 +512,9 @@ int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t di
  *   and not stored (triangles_dev may be NULL for a capacity of 0).
  * Both read the number of parents from *n_parents_dev and add the sample evaluations they perform (samples and children
  * past the lattice's rim not counted) to *evaluations_dev. */
-int hu_mesh_cells(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes, const uint32_t* windows_dev,
-                  const void* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, uint32_t child_side,
-                  const uint32_t dims[3], const float corner[3], float step, float radius, uint32_t* counter_dev,
-                  void* children_dev, uint32_t capacity, uint64_t* evaluations_dev, void* stream);
-int hu_mesh_leaf_instances(const void* table_dev, uint32_t n, int distance_only, uint32_t lane_bytes,
-                           const uint32_t* windows_dev, const void* parents_dev, const uint32_t* n_parents_dev,
-                           uint32_t max_parents, const uint32_t dims[3], const float corner[3], float step,
-                           void* triangles_dev, uint32_t triangle_capacity, uint64_t* totals_dev, uint64_t* evaluations_dev,
-                           void* stream);
+int hu_mesh_cells(const hu_cells_launch* launch, const hu_cells_children* children);
+int hu_mesh_leaf_instances(const hu_cells_launch* launch, void* triangles_dev, uint32_t triangle_capacity,
+                           uint64_t* totals_dev);
 
 /* ---- renderers on the same evaluate() -------------------- */
 /* rendering/ray_caster.cl:146-159, launched by rendering/ray_caster.py:93-110 with global size

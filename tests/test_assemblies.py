@@ -194,13 +194,13 @@ def test_instance_kernels_keep_their_records_in_scalar_registers(tmp_path):
 def test_interference_entry_points_reject_bad_arguments():
     from codecad_amd.hip_util import _lib
     import ctypes
+    import cells_abi
     lib = _lib.load()
     dl, lb = ctypes.c_int(0), ctypes.c_uint32(0)
     buf = (ctypes.c_uint8 * 64)()
     tapes = (ctypes.c_void_p * 1)(None)
-    assert lib.hu_interference_table(tapes, 1, buf, 64, ctypes.byref(dl), ctypes.byref(lb)) == -3
-    assert lib.hu_interference_table(tapes, 65, buf, 64, ctypes.byref(dl), ctypes.byref(lb)) == -3
-    d = (ctypes.c_uint32 * 3)(8, 8, 8)
-    c = (ctypes.c_float * 3)(0, 0, 0)
-    assert lib.hu_interference_leaf_indirect(None, 2, 1, 64, None, None, 0, d, c, 0.1, None, None, None) == -3
+    assert lib.hu_instance_table(tapes, 1, 0, buf, 64, ctypes.byref(dl), ctypes.byref(lb)) == -3
+    assert lib.hu_instance_table(tapes, 65, 0, buf, 64, ctypes.byref(dl), ctypes.byref(lb)) == -3
+    nulls = cells_abi.launch(table_dev=None, parents_dev=None, n_parents_dev=None, evaluations_dev=None)
+    assert lib.hu_interference_leaf_indirect(nulls, None) == -3
     assert b"NULL" in lib.hu_last_error()

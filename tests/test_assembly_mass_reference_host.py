@@ -21,6 +21,7 @@ from codecad_amd import shapes, _instance_cells, assembly_mass
 from codecad_amd.hip_util import _lib
 
 import assembly_mass_scenes as scenes
+import cells_abi
 from assembly_mass_scenes import SCENES, scene, reference
 
 
@@ -270,9 +271,17 @@ class _FakeBuffer:
 def _recorded_run(monkeypatch, top, **kwargs):
     calls = []
 
+    def as_called(arg):
+        """a launch record as it was when the call was made (_run() moves its parent fields on from level to level)"""
+        record = getattr(arg, "_obj", None)
+        if not isinstance(record, ctypes.Structure):
+            return arg
+        values = {name: getattr(record, name) for name, _ in record._fields_}
+        return {name: list(v) if isinstance(v, ctypes.Array) else v for name, v in values.items()}
+
     class Lib:
         def __getattr__(self, name):
-            return lambda *args: calls.append((name, args)) or 0
+            return lambda *args: calls.append((name, tuple(as_called(a) for a in args))) or 0
 
     _FakeBuffer.made = []
     monkeypatch.setattr(_instance_cells, "hip_manager", types.SimpleNamespace(lib=Lib(), queue=types.SimpleNamespace(handle=None)))
@@ -289,7 +298,8 @@ def _recorded_run(monkeypatch, top, **kwargs):
 
 def test_the_default_rows_of_the_traversal_are_what_they_were(monkeypatch):
     """interference's first list, byte for byte: a 16-byte header {count, 0, 0, 0} and the 16-byte rows of top_cells();
-    its entry points get the rows 16 bytes in; and the same with 32-byte rows where they are asked for."""
+    its entry points get the rows 16 bytes in, by the fields of their launch records; and the same with 32-byte rows where
+    they are asked for."""
     asm, resolution, instances, corner, step, dims = scene("boxes")
     top = _instance_cells.top_cells(instances, corner, float(step), dims, 16)
     assert len(top) >= 1 and top.dtype == numpy.uint32 and top.shape[1] == 4
@@ -300,9 +310,19 @@ def test_the_default_rows_of_the_traversal_are_what_they_were(monkeypatch):
     assert children.shape == (capacities[0] + 1, 4)
     by_name = dict(calls)
     assert by_name["hu_memset"][:3] == (children.device_ptr, 0, 16)
-    assert by_name["cells"][4:7] == (parents.device_ptr + 16, parents.device_ptr, len(top)) and len(by_name["cells"]) == 17
-    assert by_name["cells"][12:15] == (children.device_ptr, children.device_ptr + 16, capacities[0])
-    assert by_name["leaf"][4:7] == (children.device_ptr + 16, children.device_ptr, capacities[0]) and len(by_name["leaf"]) == 13
+
+    def parents_of(launch):
+        return launch["parents_dev"], launch["n_parents_dev"], launch["max_parents"]
+
+    launch, listed = by_name["cells"]
+    assert parents_of(launch) == (parents.device_ptr + 16, parents.device_ptr, len(top))
+    assert (launch["table_dev"], launch["windows_dev"], launch["n"], launch["distance_only"], launch["lane_bytes"]) == (0x10, None, 2, 1, 64)
+    assert (launch["dims"], launch["corner"], launch["step"]) == ([28, 16, 24], [0.0] * 3, numpy.float32(0.1))
+    assert launch["evaluations_dev"] == results.device_ptr + 16
+    assert (listed["counter_dev"], listed["children_dev"], listed["capacity"]) == (children.device_ptr, children.device_ptr + 16, capacities[0])
+    assert (listed["child_side"], listed["thr"]) == (4, 1.0)
+    launch, pairs = by_name["leaf"]
+    assert parents_of(launch) == (children.device_ptr + 16, children.device_ptr, capacities[0]) and pairs == results.device_ptr + 32
     assert results.written.size == 16 + 16 + 4 * 64 and _instance_cells.levels(64, 1, None)[0] == [64, 16]
     # rows of 32 bytes, an argument and the accumulators for the cells level, one accumulator per instance
     rows = assembly_mass.top_rows(instances, corner, step, dims, 16)
@@ -313,8 +333,8 @@ def test_the_default_rows_of_the_traversal_are_what_they_were(monkeypatch):
     assert parents.written.tobytes()[:32] == numpy.array([len(rows)] + [0] * 7, dtype=numpy.uint32).tobytes()
     assert parents.written.tobytes()[32:] == rows.tobytes() and children.shape == (capacities[0] + 1, 8)
     by_name = dict(calls)
-    assert by_name["cells"][4:7] == (parents.device_ptr + 32, parents.device_ptr, len(rows)) and len(by_name["cells"]) == 19
-    assert by_name["cells"][15:17] == (1, results.device_ptr + 32) and by_name["leaf"][4] == children.device_ptr + 32
+    assert parents_of(by_name["cells"][0]) == (parents.device_ptr + 32, parents.device_ptr, len(rows)) and len(by_name["cells"]) == 4
+    assert by_name["cells"][2:] == (1, results.device_ptr + 32) and by_name["leaf"][0]["parents_dev"] == children.device_ptr + 32
     assert results.written.size == 16 + 16 + 2 * 64
 
 
@@ -330,32 +350,32 @@ def test_abi_of_the_new_entry_points():
         assert len(_lib.PROTOTYPES[name]) == len(proto.split(","))
         with open(os.path.join(os.path.dirname(_lib.HEADER), "..", "INTEGRATION.md")) as f:
             assert ("int %s(" % name) in f.read()
+        assert _lib.PROTOTYPES[name][0] == ctypes.POINTER(_lib.CellsLaunch)
+    assert _lib.PROTOTYPES["hu_assembly_mass_cells"][1] == ctypes.POINTER(_lib.CellsChildren)
     assert assembly_mass._ACC.itemsize == 192 and assembly_mass._ROW == 32
     buf = (ctypes.c_uint8 * 256)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
-    f3 = (ctypes.c_float * 3)(0, 0, 0)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
+    held = cells_abi.held(p, (64, 64, 64))
+    NULL_RECORD = cells_abi.NULL_RECORD
 
-    def dims(a, b, c):
-        return (ctypes.c_uint32 * 3)(a, b, c)
+    def cells_call(child_side=4, thr=1.0, counter_dev=p, children_dev=p, children={}, acc=p, **broken):
+        listed = cells_abi.children(counter_dev=counter_dev, children_dev=children_dev, capacity=1, child_side=child_side, thr=thr, **children)
+        return lib.hu_assembly_mass_cells(cells_abi.launch(**dict(held, **broken)), listed, 1, acc)
 
-    def cells_call(table=p, n=2, parents=p, n_parents=p, child=4, d=dims(64, 64, 64), corner=f3, step=0.1, thr=1.0, counter=p, children=p,
-                   acc=p, evaluations=p):
-        return lib.hu_assembly_mass_cells(table, n, 1, 64, parents, n_parents, 1, child, d, corner, step, thr, counter, children, 1, 1, acc,
-                                          evaluations, None)
+    def leaf_call(acc=p, **broken):
+        return lib.hu_assembly_mass_leaf(cells_abi.launch(**dict(held, **broken)), acc)
 
-    def leaf_call(table=p, n=2, parents=p, n_parents=p, d=dims(64, 64, 64), corner=f3, step=0.1, acc=p, evaluations=p):
-        return lib.hu_assembly_mass_leaf(table, n, 1, 64, parents, n_parents, 1, d, corner, step, acc, evaluations, None)
-
-    common = [{"table": None}, {"parents": None}, {"n_parents": None}, {"evaluations": None}, {"acc": None}, {"d": None}, {"corner": None},
-              {"n": 0}, {"n": 65}, {"d": dims(0, 8, 8)}, {"d": dims(8, 65537, 8)}, {"d": dims(8, 8, 65537)}, {"d": dims(7132, 7132, 7132)},
+    common = [{"table_dev": None}, {"parents_dev": None}, {"n_parents_dev": None}, {"evaluations_dev": None}, {"acc": None}, NULL_RECORD,
+              {"n": 0}, {"n": 65}, {"dims": (0, 8, 8)}, {"dims": (8, 65537, 8)}, {"dims": (8, 8, 65537)}, {"dims": (7132, 7132, 7132)},
               {"step": float("nan")}, {"step": -1.0}]
-    for kwargs in common + [{"child": 2}, {"child": 12}, {"child": 32768}, {"thr": -1.0}, {"thr": float("nan")}, {"counter": None},
-                            {"children": None}]:
+    for kwargs in common + [{"child_side": 2}, {"child_side": 12}, {"child_side": 32768}, {"thr": -1.0}, {"thr": float("nan")},
+                            {"counter_dev": None}, {"children_dev": None}, {"children": NULL_RECORD}]:
         assert cells_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
     for kwargs in common:
         assert leaf_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
+    assert leaf_call(**NULL_RECORD) == -3 and b"NULL" in lib.hu_last_error()
 
 
 def test_the_kernels_keep_their_records_in_scalar_registers(tmp_path):

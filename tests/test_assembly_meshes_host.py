@@ -21,6 +21,7 @@ from codecad_amd.hip_util import _lib
 import oracle
 
 import assembly_meshes_scenes as scenes
+import cells_abi
 from assembly_meshes_scenes import (SCENES, scene, reference, traversal, meshes_of, check_mesh_properties, euler_characteristic,
                                     components, triangles_reached, dense_evaluations, default_capacity, case_table, crossing,
                                     triangles_of, is_closed_and_oriented, signed_volume)
@@ -325,37 +326,35 @@ def test_abi_of_the_mesh_entry_points():
     for name in ("hu_mesh_cells", "hu_mesh_leaf_instances"):
         assert name in declared and name in _lib.PROTOTYPES and hasattr(lib, name)
         assert len(_lib.PROTOTYPES[name]) == len(_arguments(name))
-    clearance_cells = _arguments("hu_clearance_cells_indirect")
-    assert _arguments("hu_mesh_cells") == [("radius" if a == "thr" else a) for a in clearance_cells]      # what traverse() passes a level
-    assert _lib.PROTOTYPES["hu_mesh_cells"] == _lib.PROTOTYPES["hu_clearance_cells_indirect"]
-    assert _arguments("hu_mesh_leaf_instances") == clearance_cells[:8] + ["dims", "corner", "step", "triangles_dev", "triangle_capacity",
-                                                                          "totals_dev", "evaluations_dev", "stream"]
+    # a level is what traverse() passes every level, and the leaf adds its records after the launch record
+    assert _lib.PROTOTYPES["hu_mesh_cells"] == _lib.PROTOTYPES["hu_clearance_cells_indirect"] == \
+        [ctypes.POINTER(_lib.CellsLaunch), ctypes.POINTER(_lib.CellsChildren)]
+    assert _arguments("hu_mesh_cells") == _arguments("hu_clearance_cells_indirect") == ["launch", "children"]
+    assert _lib.PROTOTYPES["hu_mesh_leaf_instances"][0] == ctypes.POINTER(_lib.CellsLaunch)
+    assert _arguments("hu_mesh_leaf_instances") == ["launch", "triangles_dev", "triangle_capacity", "totals_dev"]
     buf = (ctypes.c_uint8 * 64)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
-    f3 = (ctypes.c_float * 3)(0, 0, 0)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
+    held = cells_abi.held(p, (64, 64, 64))
+    NULL_RECORD = cells_abi.NULL_RECORD
 
-    def dims(a, b, c):
-        return (ctypes.c_uint32 * 3)(a, b, c)
+    def cells_call(child_side=4, thr=1.0, counter_dev=p, children_dev=p, children={}, **broken):
+        listed = cells_abi.children(counter_dev=counter_dev, children_dev=children_dev, capacity=1, child_side=child_side, thr=thr, **children)
+        return lib.hu_mesh_cells(cells_abi.launch(**dict(held, **broken)), listed)
 
-    def cells_call(table=p, n=2, windows=p, parents=p, n_parents=p, child=4, d=dims(64, 64, 64), corner=f3, step=0.1, r=1.0, counter=p,
-                   children=p, evaluations=p):
-        return lib.hu_mesh_cells(table, n, 1, 64, windows, parents, n_parents, 1, child, d, corner, step, r, counter, children, 1,
-                                 evaluations, None)
+    def leaf_call(triangles=p, capacity=1, totals=p, **broken):
+        return lib.hu_mesh_leaf_instances(cells_abi.launch(**dict(held, **broken)), triangles, capacity, totals)
 
-    def leaf_call(table=p, n=2, windows=p, parents=p, n_parents=p, d=dims(64, 64, 64), corner=f3, step=0.1, triangles=p, capacity=1,
-                  totals=p, evaluations=p):
-        return lib.hu_mesh_leaf_instances(table, n, 1, 64, windows, parents, n_parents, 1, d, corner, step, triangles, capacity, totals,
-                                          evaluations, None)
-
-    common = [{"table": None}, {"windows": None}, {"parents": None}, {"n_parents": None}, {"evaluations": None}, {"d": None}, {"corner": None},
-              {"n": 0}, {"n": 65}, {"d": dims(0, 8, 8)}, {"d": dims(8, 65537, 8)}, {"d": dims(65537, 8, 8)}, {"d": dims(8, 8, 65537)},
+    common = [{"table_dev": None}, {"windows_dev": None}, {"parents_dev": None}, {"n_parents_dev": None}, {"evaluations_dev": None},
+              NULL_RECORD, {"n": 0}, {"n": 65}, {"dims": (0, 8, 8)}, {"dims": (8, 65537, 8)}, {"dims": (65537, 8, 8)}, {"dims": (8, 8, 65537)},
               {"step": float("nan")}, {"step": -1.0}]
-    for kwargs in common + [{"child": 2}, {"child": 12}, {"child": 32768}, {"r": -1.0}, {"r": float("nan")}, {"counter": None}, {"children": None}]:
+    for kwargs in common + [{"child_side": 2}, {"child_side": 12}, {"child_side": 32768}, {"thr": -1.0}, {"thr": float("nan")},
+                            {"counter_dev": None}, {"children_dev": None}, {"children": NULL_RECORD}]:
         assert cells_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
     for kwargs in common + [{"triangles": None}, {"totals": None}]:
         assert leaf_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
+    assert leaf_call(**NULL_RECORD) == -3 and b"NULL" in lib.hu_last_error()
 
 
 def test_the_mesh_kernels_use_no_scratch_and_the_registers_recorded(tmp_path):

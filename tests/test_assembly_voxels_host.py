@@ -19,6 +19,7 @@ from codecad_amd import shapes, rendering, _instance_cells
 from codecad_amd.hip_util import _lib
 
 import assembly_mass_scenes as mass_scenes
+import cells_abi
 import assembly_voxels_scenes as scenes
 from assembly_voxels_scenes import SCENES, scene, reference, EMPTY
 
@@ -266,32 +267,32 @@ def test_abi_of_the_new_entry_points():
         assert len(_lib.PROTOTYPES[name]) == len(proto.split(","))
         with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
             assert ("int %s(" % name) in f.read()
+        assert _lib.PROTOTYPES[name][0] == ctypes.POINTER(_lib.CellsLaunch)
+    assert _lib.PROTOTYPES["hu_assembly_voxels_cells"][1] == ctypes.POINTER(_lib.CellsChildren)
     buf = (ctypes.c_uint8 * 512)()
-    p = ctypes.c_void_p((ctypes.addressof(buf) + 255) & ~255)      # aligned, as a volume must be
-    f3 = (ctypes.c_float * 3)(0, 0, 0)
+    p = (ctypes.addressof(buf) + 255) & ~255                       # aligned, as a volume must be
+    held = cells_abi.held(p, (64, 64, 64))
+    NULL_RECORD = cells_abi.NULL_RECORD
 
-    def dims(a, b, c):
-        return (ctypes.c_uint32 * 3)(a, b, c)
+    def cells_call(child_side=4, thr=1.0, counter_dev=p, children_dev=p, children={}, volume=p, pitch=64, acc=p, **broken):
+        listed = cells_abi.children(counter_dev=counter_dev, children_dev=children_dev, capacity=1, child_side=child_side, thr=thr, **children)
+        return lib.hu_assembly_voxels_cells(cells_abi.launch(**dict(held, **broken)), listed, 1, volume, pitch, acc)
 
-    def cells_call(table=p, n=2, parents=p, n_parents=p, child=4, d=dims(64, 64, 64), corner=f3, step=0.1, thr=1.0, counter=p, children=p,
-                   volume=p, pitch=64, acc=p, evaluations=p):
-        return lib.hu_assembly_voxels_cells(table, n, 1, 64, parents, n_parents, 1, child, d, corner, step, thr, counter, children, 1, 1,
-                                            volume, pitch, acc, evaluations, None)
+    def leaf_call(volume=p, pitch=64, acc=p, **broken):
+        return lib.hu_assembly_voxels_leaf(cells_abi.launch(**dict(held, **broken)), volume, pitch, acc)
 
-    def leaf_call(table=p, n=2, parents=p, n_parents=p, d=dims(64, 64, 64), corner=f3, step=0.1, volume=p, pitch=64, acc=p, evaluations=p):
-        return lib.hu_assembly_voxels_leaf(table, n, 1, 64, parents, n_parents, 1, d, corner, step, volume, pitch, acc, evaluations, None)
-
-    unaligned = ctypes.c_void_p(p.value + 4)
-    common = [{"table": None}, {"parents": None}, {"n_parents": None}, {"evaluations": None}, {"acc": None}, {"volume": None}, {"d": None},
-              {"corner": None}, {"n": 0}, {"n": 65}, {"d": dims(0, 8, 8)}, {"d": dims(8, 65537, 8)}, {"d": dims(8, 8, 65537)},
+    unaligned = p + 4
+    common = [{"table_dev": None}, {"parents_dev": None}, {"n_parents_dev": None}, {"evaluations_dev": None}, {"acc": None}, {"volume": None},
+              NULL_RECORD, {"n": 0}, {"n": 65}, {"dims": (0, 8, 8)}, {"dims": (8, 65537, 8)}, {"dims": (8, 8, 65537)},
               {"step": float("nan")}, {"step": -1.0}, {"pitch": 48}, {"pitch": 72}, {"pitch": 0}, {"pitch": 65552}, {"volume": unaligned}]
-    for kwargs in common + [{"child": 2}, {"child": 12}, {"child": 32768}, {"thr": -1.0}, {"thr": float("nan")}, {"counter": None},
-                            {"children": None}]:
+    for kwargs in common + [{"child_side": 2}, {"child_side": 12}, {"child_side": 32768}, {"thr": -1.0}, {"thr": float("nan")},
+                            {"counter_dev": None}, {"children_dev": None}, {"children": NULL_RECORD}]:
         assert cells_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
     for kwargs in common:
         assert leaf_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
+    assert leaf_call(**NULL_RECORD) == -3 and b"NULL" in lib.hu_last_error()
 
 
 def documented_vgprs():

@@ -12,6 +12,7 @@ from codecad_amd import nodes, _instance_cells
 from codecad_amd.hip_util import _lib
 
 import assembly_mass_scenes as mass_scenes
+import cells_abi
 import assembly_picture_scenes as aps
 import heavy_instances as hi
 
@@ -208,8 +209,8 @@ def test_the_regimes_a_larger_register_file_reaches():
 def test_lane_bytes_that_are_no_multiple_of_four_are_refused():
     lib = _lib.load()
     buf = (ctypes.c_uint8 * 64)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
-    d, c = (ctypes.c_uint32 * 3)(8, 8, 8), (ctypes.c_float * 3)(0, 0, 0)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
     for lane_bytes in (2, 66, 209):
-        assert lib.hu_interference_leaf_indirect(p, 2, 0, lane_bytes, p, p, 1, d, c, 0.1, p, p, None) == -3
+        launch = cells_abi.launch(distance_only=0, lane_bytes=lane_bytes, **cells_abi.held(p, (8, 8, 8)))
+        assert lib.hu_interference_leaf_indirect(launch, p) == -3
         assert "multiple of 4" in lib.hu_last_error().decode()

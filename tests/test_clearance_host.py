@@ -1,10 +1,9 @@
 """What the clearance check (codecad_amd/clearance.py) decides without a device: its argument checks, its lattice and
 windows, its top-level cells and the argument checks of its entry points (the ISA of its kernels: test_assemblies.py)."""
-import ctypes
-
 import numpy
 import pytest
 
+import cells_abi
 import codecad_amd as cc
 from codecad_amd import shapes
 from codecad_amd.interference import lattice as interference_lattice
@@ -80,26 +79,24 @@ def test_clearance_entry_points_reject_bad_arguments():
     let something through could launch a kernel over the made-up pointers."""
     from codecad_amd.hip_util import _lib
     lib = _lib.load()
-    fake = ctypes.c_void_p(4096)                    # never dereferenced: each call is rejected first
-    d = (ctypes.c_uint32 * 3)(8, 8, 8)
-    big = (ctypes.c_uint32 * 3)(8, 8, 65537)
-    c = (ctypes.c_float * 3)(0, 0, 0)
+    fake = cells_abi.FAKE
+    big = (8, 8, 65537)
     nan, inf = float("nan"), float("inf")
 
-    def cells(n=2, table=fake, wins=fake, dims=d, step=0.1, thr=0.5, counter=fake):
-        return lib.hu_clearance_cells_indirect(table, n, 1, 64, wins, fake, fake, 0, 4, dims, c, step, thr, counter, fake, 0,
-                                               fake, None)
+    def cells(thr=0.5, counter=fake, **broken):
+        return lib.hu_clearance_cells_indirect(cells_abi.launch(**broken), cells_abi.children(thr=thr, counter_dev=counter))
 
-    def finest(name, n=2, table=fake, wins=fake, dims=d, step=0.1, t=0.25, pairs=fake):
-        return getattr(lib, name)(table, n, 1, 64, wins, fake, fake, 0, dims, c, step, t, pairs, fake, None)
+    def finest(name, t=0.25, pairs=fake, **broken):
+        return getattr(lib, name)(cells_abi.launch(**broken), t, pairs)
 
-    bad = [cells(n=0), cells(n=65), cells(table=None), cells(wins=None), cells(counter=None), cells(dims=big),
+    bad = [cells(n=0), cells(n=65), cells(table_dev=None), cells(windows_dev=None), cells(counter=None), cells(dims=big),
            cells(step=-0.1), cells(step=nan), cells(step=inf), cells(thr=-1.0), cells(thr=nan)]
     for name in ("hu_clearance_leaf_indirect", "hu_clearance_witness_indirect"):
-        bad += [finest(name, n=0), finest(name, n=65), finest(name, table=None), finest(name, wins=None),
+        bad += [finest(name, n=0), finest(name, n=65), finest(name, table_dev=None), finest(name, windows_dev=None),
                 finest(name, pairs=None), finest(name, dims=big), finest(name, step=-0.1), finest(name, step=inf),
                 finest(name, t=-0.25), finest(name, t=nan), finest(name, t=inf)]
     assert bad == [-3] * len(bad)
-    assert lib.hu_clearance_leaf_indirect(None, 2, 1, 64, None, None, None, 0, d, c, 0.1, 0.25, None, None, None) == -3
+    nulls = cells_abi.launch(table_dev=None, windows_dev=None, parents_dev=None, n_parents_dev=None, evaluations_dev=None)
+    assert lib.hu_clearance_leaf_indirect(nulls, 0.25, None) == -3
     assert b"NULL" in lib.hu_last_error()
     assert finest("hu_clearance_witness_indirect", t=nan) == -3 and b"t must be" in lib.hu_last_error()

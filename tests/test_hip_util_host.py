@@ -18,7 +18,37 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert sorted(_lib.PROTOTYPES) == declared      # every declared function has a typed binding
-    assert lib.hu_abi_version() == 1
+    assert lib.hu_abi_version() == 2
+
+
+CELL_LEVELS = ["hu_interference_cells_indirect", "hu_clearance_cells_indirect", "hu_section_tiles", "hu_outline_tiles", "hu_layer_tiles",
+               "hu_mesh_cells", "hu_assembly_mass_cells", "hu_separation_cells", "hu_assembly_voxels_cells"]
+CELL_LEAVES = ["hu_interference_leaf_indirect", "hu_clearance_leaf_indirect", "hu_clearance_witness_indirect", "hu_section_leaf",
+               "hu_outline_leaf", "hu_layer_leaf", "hu_mesh_leaf_instances", "hu_assembly_mass_leaf", "hu_separation_leaf",
+               "hu_separation_witness", "hu_assembly_voxels_leaf"]
+
+
+def test_the_launch_records_mirror_the_header():
+    """Every entry point over instance cells takes hu_cells_launch first, a level hu_cells_children second, and the ctypes
+    Structures that fill them have the header's fields, in its order, and its sizes: what keeps a call from shifting."""
+    import re
+    with open(_lib.HEADER) as f:
+        header = f.read()
+    for name in CELL_LEVELS + CELL_LEAVES:
+        assert _lib.PROTOTYPES[name][0] == ctypes.POINTER(_lib.CellsLaunch), name
+        assert (_lib.PROTOTYPES[name][1] == ctypes.POINTER(_lib.CellsChildren)) == (name in CELL_LEVELS), name
+    taking = sorted(name for name, argtypes in _lib.PROTOTYPES.items() if ctypes.POINTER(_lib.CellsLaunch) in argtypes)
+    assert taking == sorted(CELL_LEVELS + CELL_LEAVES) and len(taking) == 20
+    for record, structure in (("hu_cells_launch", _lib.CellsLaunch), ("hu_cells_children", _lib.CellsChildren)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (record, record), header, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        declared = [re.sub(r"\[\d+\]", "", part.split()[-1]).strip("*") for line in body.split(";") if line.strip()
+                    for part in line.split(",")]
+        assert declared == [name for name, _ in structure._fields_], record
+        size = int(re.search(r"#define %s_BYTES (\d+)" % record.upper(), header).group(1))
+        assert ctypes.sizeof(structure) == size, record
+    # field by field: the C compiler's layout (instance_args.hpp asserts the sizes) is ctypes' for these types
+    assert _lib.CellsLaunch.dims.offset == 64 and _lib.CellsLaunch.step.offset == 88 and _lib.CellsChildren.thr.offset == 24
 
 
 def test_no_gpu_means_loud_failure_not_fallback():

@@ -19,6 +19,7 @@ from codecad_amd.section_outlines import SEGMENT, Outlines, stitch
 from codecad_amd.rendering import assembly_layers_svg, assembly_section_svg
 from codecad_amd.hip_util import _lib
 
+import cells_abi
 import layer_outlines_scenes as scenes
 import test_section_host as tsh
 import test_section_outlines_host as tso
@@ -297,34 +298,34 @@ def test_abi_of_the_layer_entry_points():
         at = want.index("v") + 1
         assert tso._arguments(layered) == want[:at] + ["layer_corners_dev", "n_layers"] + want[at:]
         assert _lib.PROTOTYPES[layered] == _lib.PROTOTYPES[plain][:at] + [_lib._vp, _lib._u32] + _lib.PROTOTYPES[plain][at:]
+        assert _lib.PROTOTYPES[layered][0] == ctypes.POINTER(_lib.CellsLaunch)
+    assert _lib.PROTOTYPES["hu_layer_tiles"][1] == ctypes.POINTER(_lib.CellsChildren)
     buf = (ctypes.c_uint8 * 64)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
     f3 = (ctypes.c_float * 3)(0, 0, 0)
     nan3 = (ctypes.c_float * 3)(0, float("nan"), 0)
+    held = cells_abi.held(p, (64, 64, 1))
+    NULL_RECORD = cells_abi.NULL_RECORD
 
-    def dims(a, b):
-        return (ctypes.c_uint32 * 2)(a, b)
+    def tiles_call(u=f3, v=f3, corners=p, layers=1, child_side=8, thr=1.0, counter_dev=p, children_dev=p, children={}, **broken):
+        listed = cells_abi.children(counter_dev=counter_dev, children_dev=children_dev, capacity=1, child_side=child_side, thr=thr, **children)
+        return lib.hu_layer_tiles(cells_abi.launch(**dict(held, **broken)), listed, u, v, corners, layers)
 
-    def tiles_call(table=p, n=2, windows=p, parents=p, n_parents=p, child=8, d=dims(64, 64), corner=f3, u=f3, v=f3, corners=p, layers=1,
-                   step=0.1, r=1.0, counter=p, children=p, evaluations=p):
-        return lib.hu_layer_tiles(table, n, 1, 64, windows, parents, n_parents, 1, child, d, corner, u, v, corners, layers, step, r, counter,
-                                  children, 1, evaluations, None)
+    def leaf_call(u=f3, v=f3, corners=p, layers=1, segments=p, capacity=1, totals=p, **broken):
+        return lib.hu_layer_leaf(cells_abi.launch(**dict(held, **broken)), u, v, corners, layers, segments, capacity, totals)
 
-    def leaf_call(table=p, n=2, windows=p, parents=p, n_parents=p, d=dims(64, 64), corner=f3, u=f3, v=f3, corners=p, layers=1, step=0.1,
-                  segments=p, capacity=1, totals=p, evaluations=p):
-        return lib.hu_layer_leaf(table, n, 1, 64, windows, parents, n_parents, 1, d, corner, u, v, corners, layers, step, segments, capacity,
-                                 totals, evaluations, None)
-
-    common = [{"table": None}, {"windows": None}, {"parents": None}, {"n_parents": None}, {"evaluations": None}, {"d": None}, {"corner": None},
-              {"u": None}, {"v": None}, {"n": 0}, {"n": 65}, {"d": dims(0, 8)}, {"d": dims(8, 65537)}, {"d": dims(65537, 8)},
-              {"step": float("nan")}, {"step": -1.0}, {"u": nan3}, {"v": nan3}, {"corner": nan3},
+    common = [{"table_dev": None}, {"windows_dev": None}, {"parents_dev": None}, {"n_parents_dev": None}, {"evaluations_dev": None},
+              NULL_RECORD, {"u": None}, {"v": None}, {"n": 0}, {"n": 65}, {"dims": (0, 8, 1)}, {"dims": (8, 65537, 1)}, {"dims": (65537, 8, 1)},
+              {"step": float("nan")}, {"step": -1.0}, {"u": nan3}, {"v": nan3}, {"corner": (0, float("nan"), 0)},
               {"corners": None}, {"layers": 0}, {"layers": (1 << 20) + 1}]
-    for kwargs in common + [{"child": 4}, {"child": 12}, {"child": 16384}, {"r": -1.0}, {"r": float("nan")}, {"counter": None}, {"children": None}]:
+    for kwargs in common + [{"child_side": 4}, {"child_side": 12}, {"child_side": 16384}, {"thr": -1.0}, {"thr": float("nan")},
+                            {"counter_dev": None}, {"children_dev": None}, {"children": NULL_RECORD}]:
         assert tiles_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
     for kwargs in common + [{"segments": None}, {"totals": None}]:
         assert leaf_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
+    assert leaf_call(**NULL_RECORD) == -3 and b"NULL" in lib.hu_last_error()
 
 
 def test_the_layer_kernels_use_no_scratch_and_the_registers_recorded(tmp_path):

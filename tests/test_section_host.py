@@ -30,6 +30,7 @@ from test_gpu_interference import _plate_and_shaft, _gear_train, _random_assembl
 from test_gpu_assembly_picture import _grid
 from test_instance_cells_reference_host import far_translation
 import heavy_instances
+import cells_abi
 
 
 # ---- the reference ----------------------------------------------------------------------------------------------------
@@ -568,43 +569,39 @@ def test_abi_of_the_new_entry_points():
         assert len(_lib.PROTOTYPES[name]) == len(_arguments(name))
         with open(os.path.join(os.path.dirname(_lib.HEADER), "..", "INTEGRATION.md")) as f:
             assert ("int %s(" % name) in f.read()
-    # the instance-table arguments of clearance's entry points first, then the lattice with the plane's frame
-    clearance = _arguments("hu_clearance_cells_indirect")
-    tiles, leaf = _arguments("hu_section_tiles"), _arguments("hu_section_leaf")
-    assert tiles[:9] == clearance[:9] and leaf[:8] == clearance[:8]
-    assert tiles[9:] == ["dims", "corner", "u", "v", "with_distance", "step", "radius", "counter_dev", "children_dev", "capacity",
-                         "evaluations_dev", "stream"]
-    assert leaf[8:] == ["dims", "corner", "u", "v", "with_distance", "step", "part_ids_dev", "inside_count_dev", "distance_dev",
-                        "nearest_dev", "acc_dev", "evaluations_dev", "stream"]
+    # the launch records first (test_hip_util_host.py holds them to the header), then the plane's frame and the check's own
+    assert _lib.PROTOTYPES["hu_section_tiles"][:2] == [ctypes.POINTER(_lib.CellsLaunch), ctypes.POINTER(_lib.CellsChildren)]
+    assert _lib.PROTOTYPES["hu_section_leaf"][0] == ctypes.POINTER(_lib.CellsLaunch)
+    assert _arguments("hu_section_tiles") == ["launch", "children", "u", "v", "with_distance"]
+    assert _arguments("hu_section_leaf") == ["launch", "u", "v", "with_distance", "part_ids_dev", "inside_count_dev", "distance_dev",
+                                             "nearest_dev", "acc_dev"]
     # argument checks need no device
     buf = (ctypes.c_uint8 * 64)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
     f3 = (ctypes.c_float * 3)(0, 0, 0)
     nan3 = (ctypes.c_float * 3)(0, float("nan"), 0)
+    held = cells_abi.held(p, (64, 64, 1))
+    NULL_RECORD = cells_abi.NULL_RECORD
 
-    def dims(a, b):
-        return (ctypes.c_uint32 * 2)(a, b)
+    def tiles_call(u=f3, v=f3, child_side=8, thr=1.0, counter_dev=p, children_dev=p, children={}, **broken):
+        listed = cells_abi.children(counter_dev=counter_dev, children_dev=children_dev, capacity=1, child_side=child_side, thr=thr, **children)
+        return lib.hu_section_tiles(cells_abi.launch(**dict(held, **broken)), listed, u, v, 0)
 
-    def tiles_call(table=p, n=2, windows=p, parents=p, n_parents=p, child=8, d=dims(64, 64), corner=f3, u=f3, v=f3, step=0.1, r=1.0,
-                   counter=p, children=p, evaluations=p):
-        return lib.hu_section_tiles(table, n, 1, 64, windows, parents, n_parents, 1, child, d, corner, u, v, 0, step, r, counter,
-                                    children, 1, evaluations, None)
+    def leaf_call(u=f3, v=f3, with_distance=0, part_ids=p, inside_count=p, distance=None, nearest=None, acc=p, **broken):
+        return lib.hu_section_leaf(cells_abi.launch(**dict(held, **broken)), u, v, with_distance, part_ids, inside_count, distance, nearest, acc)
 
-    def leaf_call(table=p, n=2, windows=p, parents=p, n_parents=p, d=dims(64, 64), corner=f3, u=f3, v=f3, step=0.1, with_distance=0,
-                  part_ids=p, inside_count=p, distance=None, nearest=None, acc=p, evaluations=p):
-        return lib.hu_section_leaf(table, n, 1, 64, windows, parents, n_parents, 1, d, corner, u, v, with_distance, step, part_ids,
-                                   inside_count, distance, nearest, acc, evaluations, None)
-
-    common = [{"table": None}, {"windows": None}, {"parents": None}, {"n_parents": None}, {"evaluations": None}, {"d": None}, {"corner": None},
-              {"u": None}, {"v": None}, {"n": 0}, {"n": 65}, {"d": dims(0, 8)}, {"d": dims(8, 65537)}, {"d": dims(65536, 8192)},
-              {"step": float("nan")}, {"step": -1.0}, {"u": nan3}, {"corner": nan3}]
-    for kwargs in common + [{"child": 4}, {"child": 12}, {"child": 16384}, {"r": -1.0}, {"r": float("nan")}, {"counter": None}, {"children": None}]:
+    common = [{"table_dev": None}, {"windows_dev": None}, {"parents_dev": None}, {"n_parents_dev": None}, {"evaluations_dev": None},
+              NULL_RECORD, {"u": None}, {"v": None}, {"n": 0}, {"n": 65}, {"dims": (0, 8, 1)}, {"dims": (8, 65537, 1)},
+              {"dims": (65536, 8192, 1)}, {"step": float("nan")}, {"step": -1.0}, {"u": nan3}, {"corner": (0, float("nan"), 0)}]
+    for kwargs in common + [{"child_side": 4}, {"child_side": 12}, {"child_side": 16384}, {"thr": -1.0}, {"thr": float("nan")},
+                            {"counter_dev": None}, {"children_dev": None}, {"children": NULL_RECORD}]:
         assert tiles_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
     for kwargs in common + [{"part_ids": None}, {"inside_count": None}, {"acc": None}, {"with_distance": 1},
                             {"with_distance": 1, "distance": p}, {"with_distance": 1, "nearest": p}]:
         assert leaf_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
+    assert leaf_call(**NULL_RECORD) == -3 and b"NULL" in lib.hu_last_error()
 
 
 def test_the_kernels_keep_their_records_in_scalar_registers(tmp_path):

@@ -33,6 +33,7 @@ import oracle
 so = sys.modules["codecad_amd.section_outlines"]       # (the package's attribute of that name is the function)
 
 import heavy_instances
+import cells_abi
 import test_section_host as tsh
 from test_gpu_interference import _gear_train
 
@@ -530,37 +531,36 @@ def test_abi_of_the_outline_entry_points():
     for name in ("hu_outline_tiles", "hu_outline_leaf"):
         assert name in declared and name in _lib.PROTOTYPES and hasattr(lib, name)
         assert len(_lib.PROTOTYPES[name]) == len(_arguments(name))
+    assert _lib.PROTOTYPES["hu_outline_tiles"][:2] == [ctypes.POINTER(_lib.CellsLaunch), ctypes.POINTER(_lib.CellsChildren)]
+    assert _lib.PROTOTYPES["hu_outline_leaf"][0] == ctypes.POINTER(_lib.CellsLaunch)
     section_tiles, tiles, leaf = tsh._arguments("hu_section_tiles"), _arguments("hu_outline_tiles"), _arguments("hu_outline_leaf")
     assert tiles == [a for a in section_tiles if a != "with_distance"]
-    assert leaf == section_tiles[:8] + ["dims", "corner", "u", "v", "step", "segments_dev", "segment_capacity", "totals_dev", "evaluations_dev",
-                                        "stream"]
+    assert leaf == ["launch", "u", "v", "segments_dev", "segment_capacity", "totals_dev"]
     buf = (ctypes.c_uint8 * 64)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
     f3 = (ctypes.c_float * 3)(0, 0, 0)
     nan3 = (ctypes.c_float * 3)(0, float("nan"), 0)
+    held = cells_abi.held(p, (64, 64, 1))
+    NULL_RECORD = cells_abi.NULL_RECORD
 
-    def dims(a, b):
-        return (ctypes.c_uint32 * 2)(a, b)
+    def tiles_call(u=f3, v=f3, child_side=8, thr=1.0, counter_dev=p, children_dev=p, children={}, **broken):
+        listed = cells_abi.children(counter_dev=counter_dev, children_dev=children_dev, capacity=1, child_side=child_side, thr=thr, **children)
+        return lib.hu_outline_tiles(cells_abi.launch(**dict(held, **broken)), listed, u, v)
 
-    def tiles_call(table=p, n=2, windows=p, parents=p, n_parents=p, child=8, d=dims(64, 64), corner=f3, u=f3, v=f3, step=0.1, r=1.0,
-                   counter=p, children=p, evaluations=p):
-        return lib.hu_outline_tiles(table, n, 1, 64, windows, parents, n_parents, 1, child, d, corner, u, v, step, r, counter, children, 1,
-                                    evaluations, None)
+    def leaf_call(u=f3, v=f3, segments=p, capacity=1, totals=p, **broken):
+        return lib.hu_outline_leaf(cells_abi.launch(**dict(held, **broken)), u, v, segments, capacity, totals)
 
-    def leaf_call(table=p, n=2, windows=p, parents=p, n_parents=p, d=dims(64, 64), corner=f3, u=f3, v=f3, step=0.1, segments=p, capacity=1,
-                  totals=p, evaluations=p):
-        return lib.hu_outline_leaf(table, n, 1, 64, windows, parents, n_parents, 1, d, corner, u, v, step, segments, capacity, totals,
-                                   evaluations, None)
-
-    common = [{"table": None}, {"windows": None}, {"parents": None}, {"n_parents": None}, {"evaluations": None}, {"d": None}, {"corner": None},
-              {"u": None}, {"v": None}, {"n": 0}, {"n": 65}, {"d": dims(0, 8)}, {"d": dims(8, 65537)}, {"d": dims(65537, 8)},
-              {"step": float("nan")}, {"step": -1.0}, {"u": nan3}, {"v": nan3}, {"corner": nan3}]
-    for kwargs in common + [{"child": 4}, {"child": 12}, {"child": 16384}, {"r": -1.0}, {"r": float("nan")}, {"counter": None}, {"children": None}]:
+    common = [{"table_dev": None}, {"windows_dev": None}, {"parents_dev": None}, {"n_parents_dev": None}, {"evaluations_dev": None},
+              NULL_RECORD, {"u": None}, {"v": None}, {"n": 0}, {"n": 65}, {"dims": (0, 8, 1)}, {"dims": (8, 65537, 1)}, {"dims": (65537, 8, 1)},
+              {"step": float("nan")}, {"step": -1.0}, {"u": nan3}, {"v": nan3}, {"corner": (0, float("nan"), 0)}]
+    for kwargs in common + [{"child_side": 4}, {"child_side": 12}, {"child_side": 16384}, {"thr": -1.0}, {"thr": float("nan")},
+                            {"counter_dev": None}, {"children_dev": None}, {"children": NULL_RECORD}]:
         assert tiles_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
     for kwargs in common + [{"segments": None}, {"totals": None}]:
         assert leaf_call(**kwargs) == -3, kwargs
         assert lib.hu_last_error()
+    assert leaf_call(**NULL_RECORD) == -3 and b"NULL" in lib.hu_last_error()
 
 
 def test_the_outline_kernels_use_no_scratch_and_the_registers_recorded(tmp_path):

@@ -1,6 +1,7 @@
 """separation() without a device: the reference traversal of separation_scenes.py against the dense definition on every
 scenario (so the branch and bound, as specified, loses no minimum and no witness), what the numbers bound, that the
 pruning prunes, the refusals and the empty reports, and the resources of the kernels from their metadata."""
+import ctypes
 import math
 import os
 import re
@@ -142,6 +143,9 @@ def test_abi_of_the_new_entry_points():
         assert name in declared and name in _lib.PROTOTYPES
         proto = re.search(r"int %s\(([^;]*)\);" % name, header).group(1)
         assert len(_lib.PROTOTYPES[name]) == len(proto.split(","))
+        assert _lib.PROTOTYPES[name][0] == ctypes.POINTER(_lib.CellsLaunch)
+        assert [a.split()[-1] for a in proto.split(",")][-2:] == ["top_side", "acc_dev"]
+    assert _lib.PROTOTYPES["hu_separation_cells"][1] == ctypes.POINTER(_lib.CellsChildren)
 
 
 def documented_vgprs():

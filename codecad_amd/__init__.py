@@ -27,7 +27,9 @@ ball, by an exact distance transform on the device, with the thin regions as com
 `overhangs(asm, resolution, axis, up)` says what a print along a lattice axis lays into air, how much support holds it up and
 whether those supports stand on the plate or on a part, by a scan along the lattice lines on the device (overhangs.py);
 `disassembly(asm, resolution)` says which part blocks which along the lattice axes, how far a part travels before it meets
-another and in what order the parts come apart by straight moves, by one scan per axis on the device (disassembly.py).
+another and in what order the parts come apart by straight moves, by one scan per axis on the device (disassembly.py);
+`contacts(asm, resolution)` says which parts touch, over what area, where, facing which way and in what patches, which parts
+form connected groups and which hang loose, by one pass across the faces of that volume on the device (contacts.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -56,6 +58,7 @@ from .assembly_components import (assembly_components, cavities, ComponentsRepor
 from .thin_walls import thin_walls, ThinWallReport  # noqa: F401
 from .overhangs import overhangs, OverhangReport  # noqa: F401
 from .disassembly import disassembly, DisassemblyReport  # noqa: F401
+from .contacts import contacts, ContactReport  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
@@ -63,4 +66,5 @@ __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "m
            "layer_heights", "Layers", "LAYER_SEGMENT", "assembly_mass_properties",
            "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels",
            "assembly_components", "cavities", "ComponentsReport", "CavityReport", "Component", "Cavity", "EMPTY_SPACE", "SOLID",
-           "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport"]
+           "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport",
+           "contacts", "ContactReport"]

@@ -491,6 +491,33 @@ int hu_overhang_columns(const void* ids_dev, const void* overhang_dev, void* sup
 int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t dims[3], uint32_t pitch, int axis, uint32_t n,
                       void* stream);
 
+/* ---- which parts touch, over how many faces and where (codecad_amd/contacts.py) -----------------
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, with ids 0 .. n - 1 and 255 for a sample
+ * inside no part (an id from n up counts as 255); the padding z in [dims[2], pitch) of either volume is neither read nor
+ * written, and nothing outside the lattice is inside any part.  The FACE of axis a at sample p lies between p and p + e_a, both
+ * in the lattice.  rows_dev is the ROW TABLE, hu_contact_row[3][HU_CONTACT_MAX_PARTS][HU_CONTACT_MAX_PARTS], which the caller
+ * sets to zero: row [a][i][j], i != j < n, takes the samples p with id i whose neighbour p + e_a has id j,
+ *   count += their number, sums[k] += their indices on axis k, hi[k] = the highest, not_lo[k] = ~(the lowest) of them,
+ *   not_key = ~(the least p.x << 32 | p.y << 16 | p.z): the lexicographically first p,
+ * so a row of zeros is an empty one and every update is an atomic add or an atomic maximum.  counts_dev is uint64[7][64], the
+ * caller's zeros: [2 a][i] += the samples of id i whose neighbour p + e_a is empty or outside the lattice, [2 a + 1][i] += the
+ * same with p - e_a, [6][i] += the INTERFACE SAMPLES of id i, those with an in-lattice 6-neighbour of another id that is not
+ * 255.  contact_ids_dev, where not NULL, is a volume of the shape of ids_dev: the id on the interface samples, 255 elsewhere.
+ * A wavefront writes a row only when the pair it meets changes or its walk ends, and adds its counts once at the end.
+ * Allocates nothing and synchronises nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL
+ * ids, rows, counts or dims, rows or counts not aligned to 8 bytes, a pitch that is no multiple of 16 or below dims[2], dims
+ * of 0 or above 65536, n outside 1..HU_CONTACT_MAX_PARTS. */
+#define HU_CONTACT_MAX_PARTS 64
+typedef struct hu_contact_row {         /* 64 bytes */
+    uint64_t count;
+    uint64_t sums[3];
+    uint64_t not_key;
+    uint32_t not_lo[3];
+    uint32_t hi[3];
+} hu_contact_row;
+int hu_contact_faces(const void* ids_dev, void* contact_ids_dev /* may be NULL */, void* rows_dev, uint64_t* counts_dev,
+                     const uint32_t dims[3], uint32_t pitch, uint32_t n, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "host.hpp"
 #include "instance_args.hpp"
@@ -133,7 +134,20 @@ int ensure_attrs_n()
     return HU_OK;
 }
 
+// the units' HU_BIG_LDS callbacks: a function's static, so that it exists whichever unit's initialisers run first
+std::vector<hipError_t (*)(size_t)>& big_lds_units()
+{
+    static std::vector<hipError_t (*)(size_t)> units;
+    return units;
+}
+
 }  // namespace
+
+bool hu_big_lds_unit(hipError_t (*allow)(size_t bytes))
+{
+    big_lds_units().push_back(allow);
+    return true;
+}
 
 int hu_fail(int code, const std::string& message)
 {
@@ -151,16 +165,7 @@ int hu_ensure_attrs()
     int rc;
     if ((rc = ensure_attrs_n<1>())) return rc;
     if ((rc = ensure_attrs_n<2>())) return rc;
-    HU_HIP(hu_render::allow_big_lds(kMaxLds));   // the ray caster and the bitmap kernels (render.hip)
-    HU_HIP(hu_cells::allow_big_lds(kMaxLds));          // (instance_pairs.hip)
-    HU_HIP(hu_cells::allow_big_lds_rays(kMaxLds));     // (instance_rays.hip)
-    HU_HIP(hu_cells::allow_big_lds_section(kMaxLds));  // (instance_section.hip)
-    HU_HIP(hu_cells::allow_big_lds_outline(kMaxLds));  // (instance_outline.hip)
-    HU_HIP(hu_cells::allow_big_lds_layers(kMaxLds));   // (instance_layers.hip)
-    HU_HIP(hu_cells::allow_big_lds_mass(kMaxLds));     // (instance_mass.hip)
-    HU_HIP(hu_cells::allow_big_lds_mesh(kMaxLds));     // (instance_mesh.hip)
-    HU_HIP(hu_cells::allow_big_lds_voxels(kMaxLds));   // (instance_voxels.hip)
-    HU_HIP(hu_cells::allow_big_lds_gap(kMaxLds));      // (instance_gap.hip)
+    for (const auto allow : big_lds_units()) HU_HIP(allow(kMaxLds));   // every unit that said HU_BIG_LDS (host.hpp)
     done_for_device = dev;
     return HU_OK;
 }

@@ -22,21 +22,30 @@ int hu_fail(int code, const std::string& message);
 constexpr size_t kMaxLds = 160 * 1024;
 constexpr size_t kScratchBytes = 128;
 
-// hip_util.hip: dynamic LDS above 64 KiB for every interpreter kernel of the library, once per device and thread, through
-// the hook of each unit that holds some
+// hip_util.hip: dynamic LDS above 64 KiB for every interpreter kernel of the library, once per device and thread.  A unit
+// that holds some says HU_BIG_LDS(its kernels, or arrays of them of any rank) once, at namespace scope: a static initialiser
+// appends the unit's callback to a list that hu_ensure_attrs() walks (filled before any call, read only inside one).
 int hu_ensure_attrs();
-namespace hu_render { hipError_t allow_big_lds(size_t bytes); }           // render.hip
-namespace hu_cells {
-hipError_t allow_big_lds(size_t bytes);                                   // instance_pairs.hip
-hipError_t allow_big_lds_rays(size_t bytes);                              // instance_rays.hip
-hipError_t allow_big_lds_section(size_t bytes);                           // instance_section.hip
-hipError_t allow_big_lds_outline(size_t bytes);                           // instance_outline.hip
-hipError_t allow_big_lds_layers(size_t bytes);                            // instance_layers.hip
-hipError_t allow_big_lds_mass(size_t bytes);                             // instance_mass.hip
-hipError_t allow_big_lds_mesh(size_t bytes);                              // instance_mesh.hip
-hipError_t allow_big_lds_voxels(size_t bytes);                            // instance_voxels.hip
-hipError_t allow_big_lds_gap(size_t bytes);                               // instance_gap.hip
-}  // namespace hu_cells
+bool hu_big_lds_unit(hipError_t (*allow)(size_t bytes));
+template <class... A> hipError_t hu_big_lds(size_t bytes, void (*kernel)(A...))
+{
+    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+template <class T, size_t N> hipError_t hu_big_lds(size_t bytes, T (&kernels)[N])
+{
+    hipError_t e = hipSuccess;
+    for (auto& k : kernels)
+        if (e == hipSuccess) e = hu_big_lds(bytes, k);
+    return e;
+}
+template <class... K> hipError_t hu_big_lds_all(size_t bytes, K&... kernels)
+{
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? hu_big_lds(bytes, kernels) : e), ...);
+    return e;
+}
+#define HU_BIG_LDS(...) \
+    static const bool hu_big_lds_listed = hu_big_lds_unit([](size_t bytes) { return hu_big_lds_all(bytes, __VA_ARGS__); })
 
 // The workgroup of a kernel that keeps `lane_bytes` of LDS per lane (the interpreter's register file and what follows it
 // per lane): the largest of 256, 128, 64 lanes that keeps them within 48 KiB (three workgroups or more per CU), else 64;

@@ -242,25 +242,6 @@ __global__ void __launch_bounds__(256) k_comp_roots(const CompArgs k)
     if (root) k.labels[q] = kSlot | (base + (uint32_t)__popcll(roots & ((1ull << lane) - 1ull)));
 }
 
-// OR of a 64-bit value over the 64 lanes of a wavefront, wave-uniform: instance_mass.hip's wave_sum64 with | for +
-template <int CTRL, int ROWS> __device__ __forceinline__ unsigned long long dpp64(unsigned long long v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROWS, 0xf, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xf, false);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long wave_or64(unsigned long long v)
-{
-    v |= dpp64<0x111, 0xf>(v);   // row_shr:1
-    v |= dpp64<0x112, 0xf>(v);   // row_shr:2
-    v |= dpp64<0x114, 0xf>(v);   // row_shr:4
-    v |= dpp64<0x118, 0xf>(v);   // row_shr:8
-    v |= dpp64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v |= dpp64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-}
-
 // the owner bit of the sample at byte offset `at`, or 0 for an empty one
 __device__ __forceinline__ unsigned long long owner_bit(const uint8_t* volume, size_t at)
 {

@@ -35,26 +35,8 @@ using namespace hu_cells;
 
 namespace {
 
-// instance_pairs.hip order_key: the key of v in an order that unsigned comparison keeps, -0 and +0 with the one key of +0
-__device__ __forceinline__ uint32_t order_key(float v)
-{
-    const uint32_t b = __float_as_uint(v == 0.0f ? 0.0f : v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-// ... and the float32 of a key (separation.py decodes it alike); the key of all ones, nothing known yet, is a NaN
+// the float32 of an order_key() (separation.py decodes it alike); the key of all ones, nothing known yet, is a NaN
 __device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// instance_pairs.hip wave_min_to_last_lane: minimum over the 64 lanes of a wavefront; it arrives in lane 63
-__device__ __forceinline__ uint32_t wave_min_to_last_lane(uint32_t v)
-{
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
-    return v;
-}
 
 // Every candidate of `row` evaluated at this lane's point, into the wavefront's LDS area (after the register file) at
 // wl[n * 64 + lane]; live lanes x candidates counted once per wavefront.  The one interpreter call site of a kernel.
@@ -90,22 +72,6 @@ __device__ __forceinline__ void lower_key(uint32_t* next, uint32_t pair, uint32_
 {
     const uint32_t kmin = (uint32_t)__builtin_amdgcn_readlane((int)wave_min_to_last_lane(key), 63);
     if (kmin < known && lane == 0u) atomicMin(next + pair, kmin);
-}
-
-// the child cell a lane takes: its first sample's indices, and whether it has a sample inside dims
-struct ChildLane {
-    uint32_t x, y, z;
-    bool live;
-};
-__device__ __forceinline__ ChildLane child_lane(const Args& a, const CellRow& row, uint32_t lane)
-{
-    const uint32_t s = a.child_side;
-    ChildLane q;
-    q.x = row.x0 + (lane >> 4) * s;
-    q.y = row.y0 + ((lane >> 2) & 3u) * s;
-    q.z = row.z0 + (lane & 3u) * s;
-    q.live = row.have & (q.x < a.dims[0]) & (q.y < a.dims[1]) & (q.z < a.dims[2]);
-    return q;
 }
 
 template <bool DO>
@@ -154,37 +120,19 @@ __global__ void __launch_bounds__(256) k_gap_cells(const GapArgs g)
         a.children[slot[0]] = make_uint4(x | (y << 16), z, (uint32_t)keep, (uint32_t)(keep >> 32));
 }
 
-// the sample of a finest cell this lane takes (instance_pairs.hip leaf_lane)
-struct LeafLane {
-    uint32_t x, y, z;
-    bool live;
-    float px, py, pz;
-};
-__device__ __forceinline__ LeafLane leaf_lane(const Args& a, const CellRow& row)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    LeafLane l;
-    l.x = row.x0 + (lane >> 4);
-    l.y = row.y0 + ((lane >> 2) & 3u);
-    l.z = row.z0 + (lane & 3u);
-    l.live = (l.x < a.dims[0]) & (l.y < a.dims[1]) & (l.z < a.dims[2]);
-    // exactly kernels.hpp sample() (the lattice of oracle.grid_eval)
-    l.px = sample(a.corner[0], a.step, l.x);
-    l.py = sample(a.corner[1], a.step, l.y);
-    l.pz = sample(a.corner[2], a.step, l.z);
-    return l;
-}
-
 template <bool DO>
 __global__ void __launch_bounds__(256) k_gap_leaf(const GapArgs g)
 {
     const Args& a = g.c;
     const CellRow row = cell_row(a);
     if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
-    const LeafLane l = leaf_lane(a, row);
-    const GapLane c = gap_lane<DO>(a, row, l.live, l.px, l.py, l.pz);
+    // instance_cells.hpp leaf_lane, spelled out: the shared struct renames this kernel's registers
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t x = row.x0 + (lane >> 4), y = row.y0 + ((lane >> 2) & 3u), z = row.z0 + (lane & 3u);
+    const bool live = (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
+    const GapLane c = gap_lane<DO>(a, row, live, sample(a.corner[0], a.step, x), sample(a.corner[1], a.step, y), sample(a.corner[2], a.step, z));
     const uint32_t* bound = constant_uniform(g.bound);
-    for_pairs(row.mask, l.live ? row.mask : 0ull, [&](uint32_t i, uint32_t j, bool both, uint64_t) __attribute__((always_inline)) {
+    for_pairs(row.mask, live ? row.mask : 0ull, [&](uint32_t i, uint32_t j, bool both, uint64_t) __attribute__((always_inline)) {
         const uint32_t pair = i * a.n_instances + j;
         const float v = c.v(i, j);
         lower_key(g.next, pair, both && v == v ? order_key(v) : 0xffffffffu, bound[pair], c.lane);
@@ -218,6 +166,7 @@ void (*const kGapTable[3][2])(GapArgs) = {
     {k_gap_leaf<false>, k_gap_leaf<true>},
     {k_gap_witness<false>, k_gap_witness<true>},
 };
+HU_BIG_LDS(kGapTable);
 
 // Where the accumulators keep what: n^2 uint64 witnesses, then the key arrays U_0 .. U_L and the final one, n^2 uint32
 // each, then L uint32: the rows each level listed.  L, the levels above the finest one, comes from the top side 16 * 4^k.
@@ -246,16 +195,12 @@ int gap_layout(void* acc_dev, uint32_t n, uint32_t top_side, GapLayout& out)
     return HU_OK;
 }
 
-// What the three entry points check and fill alike: cells_args() of interference's lattice, and what the witness needs:
-// every index within 16 bits.
+// What the three entry points check and fill alike: cells_args() of a strict lattice (the witness packs an index into 16
+// bits per axis).
 int gap_args(const hu_cells_launch* l, GapArgs& g)
 {
-    int rc;
     std::memset(&g, 0, sizeof(g));
-    if ((rc = cells_args(false, l, g.c))) return rc;
-    if (l->dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(l->step) || l->step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
-    return HU_OK;
+    return cells_args(kStrict, l, g.c);
 }
 
 // a launch over the finest cells: the leaf (level rows and the copy of the keys first) or the witness
@@ -280,11 +225,6 @@ int gap_finest(bool witness, const hu_cells_launch* l, uint32_t top_side, void* 
 }
 
 }  // namespace
-
-hipError_t hu_cells::allow_big_lds_gap(size_t bytes)
-{
-    return allow_big_lds_table(kGapTable, bytes);
-}
 
 extern "C" {
 

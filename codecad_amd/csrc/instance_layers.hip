@@ -27,6 +27,7 @@ void (*const kLayerTable[2][2])(LayerArgs) = {
     {k_layer_tiles<false>, k_layer_tiles<true>},
     {k_layer_leaf<false>, k_layer_leaf<true>},
 };
+HU_BIG_LDS(kLayerTable);
 
 constexpr uint32_t kMaxLayers = 1u << 20;     // (a record keeps the layer in the 20 bits from bit 12)
 
@@ -44,11 +45,6 @@ int layer_args(const hu_cells_launch* l, const float u[3], const float v[3], con
 }
 
 }  // namespace
-
-hipError_t hu_cells::allow_big_lds_layers(size_t bytes)
-{
-    return allow_big_lds_table(kLayerTable, bytes);
-}
 
 extern "C" {
 

@@ -58,26 +58,6 @@ __device__ __forceinline__ MassRow mass_row(const Args& a)
     return r;
 }
 
-// Sum of a 64-bit value over the 64 lanes of a wavefront, wave-uniform: kernels.hpp wave_sum_to_last_lane on both halves,
-// the carry propagated by the 64-bit add of every step (lanes without a source add 0).
-template <int CTRL, int ROWS> __device__ __forceinline__ unsigned long long dpp64(unsigned long long v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROWS, 0xf, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xf, false);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-    v += dpp64<0x111, 0xf>(v);   // row_shr:1
-    v += dpp64<0x112, 0xf>(v);   // row_shr:2
-    v += dpp64<0x114, 0xf>(v);   // row_shr:4
-    v += dpp64<0x118, 0xf>(v);   // row_shr:8: lane 15 of a row = its total
-    v += dpp64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += dpp64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-}
-
 // ten wave-uniform sums added to an accumulator's ten words by one lane: one atomic per word and wavefront
 __device__ __forceinline__ void add_sums(unsigned long long* words, const unsigned long long (&sums)[10], uint32_t lane)
 {
@@ -109,22 +89,21 @@ __global__ void __launch_bounds__(256) k_mass_cells(const Args a)
     const uint32_t lane = threadIdx.x & 63u;
     const MassRow row = mass_row(a);
     const uint32_t s = a.child_side;
-    const uint32_t x = row.x0 + (lane >> 4) * s, y = row.y0 + ((lane >> 2) & 3u) * s, z = row.z0 + (lane & 3u) * s;
-    const bool live = row.have & (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
-    const float h = 0.5f * (float)(s - 1u);                      // the child's centre, as k_instance_cells computes it
-    const float px = a.corner[0] + a.step * ((float)x + h);
-    const float py = a.corner[1] + a.step * ((float)y + h);
-    const float pz = a.corner[2] + a.step * ((float)z + h);
+    const ChildLane q = child_lane(a, row, lane);
+    const uint32_t x = q.x, y = q.y, z = q.z;
+    const bool live = q.live;
+    const Point p = child_centre(a, q);
     const float below = (a.flags & kMassRetire) ? -a.thr : -__builtin_inff();   // wave-uniform: nothing is below -inf
     const uint64_t todo = row.cand & ~row.full;
     uint64_t keep = row.full, full = row.full;                   // a full parent's children are full
     for (uint64_t m = todo; m != 0ull; m &= m - 1ull) {          // wave-uniform; the one interpreter call site
         const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
-        const float w = instance_dist<DO>(a, n, px, py, pz, lds);
+        const float w = instance_dist<DO>(a, n, p.x, p.y, p.z, lds);
         if (!(w >= a.thr)) keep |= 1ull << n;                     // (a NaN keeps its candidate)
         if (w < below) full |= 1ull << n;
     }
     full &= keep;
+    // (the count stays spelled out: with its guard through a shared function this kernel compiles to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && lives && todo) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(todo)));
     const bool retired = live && keep != 0ull && keep == full;
@@ -203,6 +182,7 @@ __global__ void __launch_bounds__(256) k_mass_leaf(const Args a)
     extern __shared__ float4 lds[];
     const MassRow row = mass_row(a);
     if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
+    // (the lane and the count stay spelled out: with instance_cells.hpp leaf_lane or a shared count this kernel compiles to other code)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t dx = lane >> 4, dy = (lane >> 2) & 3u, dz = lane & 3u;
     const uint32_t x = row.x0 + dx, y = row.y0 + dy, z = row.z0 + dz;
@@ -253,17 +233,16 @@ void (*const kMassTable[2][2])(Args) = {
     {k_mass_cells<false>, k_mass_cells<true>},
     {k_mass_leaf<false>, k_mass_leaf<true>},
 };
+HU_BIG_LDS(kMassTable);
 
-// What both entry points of the assembly's mass properties check and fill: cells_args() of interference's lattice, and
-// what the sums need: every index within 16 bits, and a lattice whose second-moment sums fit 64 bits.
+// What both entry points of the assembly's mass properties check and fill: cells_args() of a strict lattice (every index
+// within 16 bits), and what the sums need beyond it: a lattice whose second-moment sums fit 64 bits.
 int mass_args(const hu_cells_launch* l, void* acc_dev, Args& a)
 {
     int rc;
-    if ((rc = cells_args(false, l, a))) return rc;
+    if ((rc = cells_args(kStrict, l, a))) return rc;
     if (!acc_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     const uint32_t* dims = l->dims;
-    if (dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(l->step) || l->step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
     const uint64_t longest = std::max(dims[0], std::max(dims[1], dims[2])) - 1u;
     const unsigned __int128 bound = (unsigned __int128)dims[0] * dims[1] * dims[2] * longest * longest;
     if (bound >> 64) return hu_fail(HU_ERR_BAD_ARG, "the lattice's second-moment index sums would not fit 64 bits");
@@ -273,11 +252,6 @@ int mass_args(const hu_cells_launch* l, void* acc_dev, Args& a)
 
 }  // namespace
 
-hipError_t hu_cells::allow_big_lds_mass(size_t bytes)
-{
-    return allow_big_lds_table(kMassTable, bytes);
-}
-
 extern "C" {
 
 int hu_assembly_mass_cells(const hu_cells_launch* launch, const hu_cells_children* children, int retire, void* acc_dev)
@@ -286,8 +260,7 @@ int hu_assembly_mass_cells(const hu_cells_launch* launch, const hu_cells_childre
     int rc;
     if ((rc = mass_args(launch, acc_dev, a))) return rc;
     if ((rc = cells_children(a, children))) return rc;
-    if (a.child_side < 4u || a.child_side > 16384u || (a.child_side & (a.child_side - 1u)))
-        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
+    if ((rc = check_child_side(a.child_side, 4u, 16384u))) return rc;
     if (!std::isfinite(a.thr) || a.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
     if (a.max_parents > 0x7fffffffu || a.capacity > 0x7fffffffu) return hu_fail(HU_ERR_BAD_ARG, "a list of 32-byte rows holds fewer than 2^31");
     a.flags = retire ? kMassRetire : 0u;

@@ -51,8 +51,9 @@ __global__ void __launch_bounds__(256) k_mesh_cells(const MeshArgs t)
     const uint32_t lane = threadIdx.x & 63u;
     const CellRow row = cell_row(a);
     const uint32_t s = a.child_side;
-    const uint32_t x = row.x0 + (lane >> 4) * s, y = row.y0 + ((lane >> 2) & 3u) * s, z = row.z0 + (lane & 3u) * s;
-    const bool live = row.have & (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
+    const ChildLane q = child_lane(a, row, lane);
+    const uint32_t x = q.x, y = q.y, z = q.z;
+    const bool live = q.live;
     const float h = 0.5f * (float)s;
     const float px = ring_sample(a.corner[0], a.step, (float)x + h);
     const float py = ring_sample(a.corner[1], a.step, (float)y + h);
@@ -62,11 +63,11 @@ __global__ void __launch_bounds__(256) k_mesh_cells(const MeshArgs t)
     for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {      // wave-uniform; the one interpreter call site
         const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
         const uint32_t* win = windows + 6u * n;
-        const bool reach = (x <= win[3]) & (x + s - 1u >= win[0]) & (y <= win[4]) & (y + s - 1u >= win[1]) & (z <= win[5]) &
-                           (z + s - 1u >= win[2]);
+        const bool reach = reaches(win, q, s);
         const float w = instance_dist<DO>(a, n, px, py, pz, lds);
         if (reach && !(w >= a.thr) && !(w <= -a.thr)) keep |= 1ull << n;   // may cross an edge of the child (a NaN keeps its candidate)
     }
+    // (the count and the child-row store stay spelled out: through a shared function this kernel compiles to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && lives) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
     const bool flag[1] = {live && keep != 0ull};
@@ -128,8 +129,9 @@ __global__ void __launch_bounds__(256) k_mesh_leaf(const MeshArgs t)
     // the wavefront's 125 values, [25 i + 5 j + k] of the sample (a0 + i, b0 + j, c0 + k), in its 128 floats after the register file
     float* wl = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + a.scratch_offset) + (threadIdx.x >> 6) * 128u;
     const uint32_t i = lane >> 4, j = (lane >> 2) & 3u, k = lane & 3u;
-    const uint32_t x = row.x0 + i, y = row.y0 + j, z = row.z0 + k;
-    const bool live = (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);     // the lane's cube exists: so do its eight samples
+    const LeafLane l = leaf_lane(a, row);
+    const uint32_t x = l.x, y = l.y, z = l.z;
+    const bool live = l.live;                                     // the lane's cube exists: so do its eight samples
     // the second pass: lanes 0..24 take the face i = 4, lanes 25..44 the rest of j = 4, lanes 45..60 the rest of k = 4; the
     // others repeat their own sample
     const bool far = lane < 61u;
@@ -201,13 +203,9 @@ void (*const kMeshTable[2][2])(MeshArgs) = {
     {k_mesh_cells<false>, k_mesh_cells<true>},
     {k_mesh_leaf<false>, k_mesh_leaf<true>},
 };
+HU_BIG_LDS(kMeshTable);
 
 }  // namespace
-
-hipError_t hu_cells::allow_big_lds_mesh(size_t bytes)
-{
-    return allow_big_lds_table(kMeshTable, bytes);
-}
 
 extern "C" {
 
@@ -216,10 +214,9 @@ int hu_mesh_cells(const hu_cells_launch* launch, const hu_cells_children* childr
     MeshArgs t;
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, launch, t.c))) return rc;
+    if ((rc = cells_args(kWindows | kStrict, launch, t.c))) return rc;
     if ((rc = cells_children(t.c, children))) return rc;
-    if (t.c.child_side < 4u || t.c.child_side > 16384u || (t.c.child_side & (t.c.child_side - 1u)))
-        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
+    if ((rc = check_child_side(t.c.child_side, 4u, 16384u))) return rc;
     if (std::isnan(t.c.thr) || t.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
     return cells_launch(kMeshTable[0][launch->distance_only != 0], t, t.c, *launch, 0u);
 }
@@ -229,7 +226,7 @@ int hu_mesh_leaf_instances(const hu_cells_launch* launch, void* triangles_dev, u
     MeshArgs t;
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, launch, t.c))) return rc;
+    if ((rc = cells_args(kWindows | kStrict, launch, t.c))) return rc;
     if (!totals_dev || (!triangles_dev && triangle_capacity)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     t.c.child_side = 1u;
     t.c.pairs = totals_dev;

@@ -20,13 +20,9 @@ void (*const kOutlineTable[2][2])(OutlineArgs) = {
     {k_outline_tiles<false>, k_outline_tiles<true>},
     {k_outline_leaf<false>, k_outline_leaf<true>},
 };
+HU_BIG_LDS(kOutlineTable);
 
 }  // namespace
-
-hipError_t hu_cells::allow_big_lds_outline(size_t bytes)
-{
-    return allow_big_lds_table(kOutlineTable, bytes);
-}
 
 extern "C" {
 

@@ -42,14 +42,12 @@ __global__ void __launch_bounds__(256) k_instance_cells(const Args a)
     const uint32_t lane = threadIdx.x & 63u;
     const CellRow row = cell_row(a);
     const uint32_t s = a.child_side;
-    const uint32_t x = row.x0 + (lane >> 4) * s, y = row.y0 + ((lane >> 2) & 3u) * s, z = row.z0 + (lane & 3u) * s;
-    const bool live = row.have & (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
+    const ChildLane q = child_lane(a, row, lane);
+    const uint32_t x = q.x, y = q.y, z = q.z;
+    const bool live = q.live;
     // the child's centre; its samples lie within (s - 1) * step * sqrt(3) / 2 of it, a.thr is t (interference: 0) plus
     // more than that (interference.py)
-    const float h = 0.5f * (float)(s - 1u);
-    const float px = a.corner[0] + a.step * ((float)x + h);
-    const float py = a.corner[1] + a.step * ((float)y + h);
-    const float pz = a.corner[2] + a.step * ((float)z + h);
+    const Point p = child_centre(a, q);
     const uint32_t* windows = WINDOWED ? constant_uniform(a.windows) : nullptr;
     uint64_t keep = 0ull;
     for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {      // wave-uniform
@@ -57,12 +55,12 @@ __global__ void __launch_bounds__(256) k_instance_cells(const Args a)
         bool reach = true;
         if constexpr (WINDOWED) {
             const uint32_t* win = windows + 6u * n;
-            reach = (x <= win[3]) & (x + s - 1u >= win[0]) & (y <= win[4]) & (y + s - 1u >= win[1]) & (z <= win[5]) &
-                    (z + s - 1u >= win[2]);
+            reach = reaches(win, q, s);
         }
-        const float w = instance_dist<DO>(a, n, px, py, pz, lds);
+        const float w = instance_dist<DO>(a, n, p.x, p.y, p.z, lds);
         if (reach && !(w >= a.thr)) keep |= 1ull << n;            // (a NaN keeps its candidate)
     }
+    // (the count and the child-row store stay spelled out: through a shared function this kernel compiles to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && lives) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
     const bool flag[1] = {live && __popcll(keep) >= 2};
@@ -70,34 +68,6 @@ __global__ void __launch_bounds__(256) k_instance_cells(const Args a)
     wg_compact_slots<1>(flag, a.counter, scratch, slot);         // every wavefront of the workgroup gets here (barriers)
     if (flag[0] && slot[0] < a.capacity)
         a.children[slot[0]] = make_uint4(x | (y << 16), z, (uint32_t)keep, (uint32_t)(keep >> 32));
-}
-
-// the sample of a finest cell this lane takes
-struct LeafLane {
-    uint32_t lane, x, y, z;
-    bool live;
-    float px, py, pz;
-};
-__device__ __forceinline__ LeafLane leaf_lane(const Args& a, const CellRow& row)
-{
-    LeafLane l;
-    l.lane = threadIdx.x & 63u;
-    l.x = row.x0 + (l.lane >> 4);
-    l.y = row.y0 + ((l.lane >> 2) & 3u);
-    l.z = row.z0 + (l.lane & 3u);
-    l.live = (l.x < a.dims[0]) & (l.y < a.dims[1]) & (l.z < a.dims[2]);
-    // exactly kernels.hpp sample() (the lattice of oracle.grid_eval)
-    l.px = sample(a.corner[0], a.step, l.x);
-    l.py = sample(a.corner[1], a.step, l.y);
-    l.pz = sample(a.corner[2], a.step, l.z);
-    return l;
-}
-
-// one evaluation per live lane and candidate, counted once per wavefront
-__device__ __forceinline__ void count_evaluations(const Args& a, const CellRow& row, const LeafLane& l)
-{
-    const uint64_t lives = __ballot(l.live);
-    if (l.lane == 0u) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
 }
 
 // the lanes of `b` (this lane: `both`) added to a pair's count, index sums and index box
@@ -129,30 +99,10 @@ __global__ void __launch_bounds__(256) k_interference_leaf(const Args a)
         inside |= in ? 1ull << n : 0ull;
         present |= __ballot(in) ? 1ull << n : 0ull;
     }
-    count_evaluations(a, row, l);
+    count_evaluations(a, l.live, row.mask);
     for_pairs(present, inside, [&](uint32_t i, uint32_t j, bool both, uint64_t b) __attribute__((always_inline)) {
         add_samples(static_cast<OverlapAcc*>(a.pairs) + (size_t)i * a.n_instances + j, both, b, l, row);
     });
-}
-
-// the key of v in an order that unsigned comparison keeps: -0 and +0 get the one key of +0 (clearance.py decodes it)
-__device__ __forceinline__ uint32_t order_key(float v)
-{
-    const uint32_t b = __float_as_uint(v == 0.0f ? 0.0f : v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// Minimum over the 64 lanes of a wavefront; it arrives in lane 63.  kernels.hpp wave_sum_to_last_lane with min for +
-// (lanes without a source take 0xffffffff, the identity).
-__device__ __forceinline__ uint32_t wave_min_to_last_lane(uint32_t v)
-{
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
-    return v;
 }
 
 // Clearance's finest cell: every candidate evaluated at the lane's sample, w into the wavefront's LDS area (after the
@@ -182,7 +132,7 @@ template <bool DO> __device__ __forceinline__ NearLeaf near_leaf(const Args& a, 
         r.wl[n * 64u + l.lane] = w;
         r.near |= (in & (w < a.t)) ? 1ull << n : 0ull;
     }
-    count_evaluations(a, row, l);
+    count_evaluations(a, l.live, row.mask);
     for (uint64_t m = row.mask; m != 0ull; m &= m - 1ull) {
         const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
         r.present |= __ballot((r.near >> n) & 1ull) ? 1ull << n : 0ull;
@@ -227,15 +177,16 @@ void (*const kKernels[])(Args) = {
     k_instance_cells<false, true>,  k_instance_cells<true, true>,  k_clearance_leaf<false>,    k_clearance_leaf<true>,
     k_clearance_witness<false>,     k_clearance_witness<true>,
 };
+HU_BIG_LDS(kKernels);
 
 // a level of cells above the finest one, of either check
 int cells_level(bool clearance, const hu_cells_launch* l, const hu_cells_children* c)
 {
     Args a;
     int rc;
-    if ((rc = cells_args(clearance, l, a))) return rc;
+    if ((rc = cells_args(clearance ? kWindows | kStrict : 0u, l, a))) return rc;
     if ((rc = cells_children(a, c))) return rc;
-    if (a.child_side < 4u || a.child_side > 16384u) return hu_fail(HU_ERR_BAD_ARG, "child_side must be in 4..16384");
+    if ((rc = check_child_side(a.child_side, 4u, 16384u, false))) return rc;   // (released without the power-of-two test)
     if (clearance && (!std::isfinite(a.thr) || a.thr < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
     const auto kernel = clearance ? (l->distance_only ? k_instance_cells<true, true> : k_instance_cells<false, true>)
                                   : (l->distance_only ? k_instance_cells<true, false> : k_instance_cells<false, false>);
@@ -247,7 +198,7 @@ int cells_finest(void (*const (&kernels)[2])(Args), bool clearance, const hu_cel
 {
     Args a;
     int rc;
-    if ((rc = cells_args(clearance, l, a))) return rc;
+    if ((rc = cells_args(clearance ? kWindows | kStrict : 0u, l, a))) return rc;
     if (!pairs_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     if (clearance && (!std::isfinite(t) || t < 0.0f)) return hu_fail(HU_ERR_BAD_ARG, "t must be finite and not negative");
     a.child_side = 1u;
@@ -257,14 +208,6 @@ int cells_finest(void (*const (&kernels)[2])(Args), bool clearance, const hu_cel
 }
 
 }  // namespace
-
-hipError_t hu_cells::allow_big_lds(size_t bytes)
-{
-    hipError_t e = hipSuccess;
-    for (const auto kernel : kKernels)
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
-}
 
 extern "C" {
 

@@ -133,10 +133,7 @@ __global__ void __launch_bounds__(256) k_ray_caster_instances(const RayArgs t, c
 
 }  // namespace
 
-hipError_t hu_cells::allow_big_lds_rays(size_t bytes)
-{
-    return hipFuncSetAttribute((const void*)k_ray_caster_instances, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+HU_BIG_LDS(k_ray_caster_instances);
 
 extern "C" int hu_ray_caster_instances(const void* table_dev, uint32_t n, int distance_only_kernel, uint32_t lane_bytes, const float origin[4],
                                        const float forward[4], const float up[4], const float right[4], float pixel_tolerance,

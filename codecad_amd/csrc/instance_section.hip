@@ -35,9 +35,6 @@ using namespace hu_cells;
 namespace {
 
 // the point of the plane at the lattice indices (fi, fj): whole numbers for a sample, half-integers for a tile's centre
-struct Point {
-    float x, y, z;
-};
 __device__ __forceinline__ Point plane_point(const SectionArgs& t, float fi, float fj)
 {
     const float a = t.c.step * fi, b = t.c.step * fj;
@@ -85,6 +82,7 @@ __global__ void __launch_bounds__(256) k_section_tiles(const SectionArgs t)
             if (!(wl[n * 64u + lane] > bound)) keep |= 1ull << n; // may be the least, or tie with it, somewhere in the child
         }
     }
+    // (the count and the child-row store stay spelled out: through a shared function this kernel compiles to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && lives) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
     const bool flag[1] = {live && keep != 0ull};
@@ -137,6 +135,7 @@ __global__ void __launch_bounds__(256) k_section_leaf(const SectionArgs t)
             none = false;
         }
     }
+    // (spelled out: through instance_cells.hpp count_evaluations this kernel compiles to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
     if (live) {
@@ -168,6 +167,7 @@ void (*const kSectionTable[2][2][2])(SectionArgs) = {
     {{k_section_tiles<false, false>, k_section_tiles<false, true>}, {k_section_tiles<true, false>, k_section_tiles<true, true>}},
     {{k_section_leaf<false, false>, k_section_leaf<false, true>}, {k_section_leaf<true, false>, k_section_leaf<true, true>}},
 };
+HU_BIG_LDS(kSectionTable);
 
 // What both entry points of the section check and fill: cells_args() of a lattice {dims u, dims v, 1} with windows, and the
 // plane's frame.
@@ -176,7 +176,7 @@ int section_args(const hu_cells_launch* l, const float u[3], const float v[3], S
     if (!u || !v) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, l, t.c, true))) return rc;
+    if ((rc = cells_args(kWindows | kStrict | kPlanar, l, t.c))) return rc;
     if ((uint64_t)l->dims[0] * l->dims[1] > (1ull << 28)) return hu_fail(HU_ERR_BAD_ARG, "a section holds at most 2^28 samples");
     for (int i = 0; i < 3; ++i) {
         if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(l->corner[i])) return hu_fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
@@ -188,16 +188,6 @@ int section_args(const hu_cells_launch* l, const float u[3], const float v[3], S
 
 }  // namespace
 
-hipError_t hu_cells::allow_big_lds_section(size_t bytes)
-{
-    hipError_t e = hipSuccess;
-    for (const auto& level : kSectionTable)
-        for (const auto& programs : level)
-            for (const auto variant : programs)
-                if (e == hipSuccess) e = hipFuncSetAttribute((const void*)variant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
-}
-
 extern "C" {
 
 int hu_section_tiles(const hu_cells_launch* launch, const hu_cells_children* children, const float u[3], const float v[3],
@@ -207,8 +197,7 @@ int hu_section_tiles(const hu_cells_launch* launch, const hu_cells_children* chi
     int rc;
     if ((rc = section_args(launch, u, v, t))) return rc;
     if ((rc = cells_children(t.c, children))) return rc;
-    if (t.c.child_side < 8u || t.c.child_side > 8192u || (t.c.child_side & (t.c.child_side - 1u)))
-        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 8..8192");
+    if ((rc = check_child_side(t.c.child_side, 8u, 8192u))) return rc;
     if (std::isnan(t.c.thr) || t.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
     // WITH_DISTANCE keeps every candidate's w at the children's centres: 4 bytes per instance and lane after the register file
     return cells_launch(kSectionTable[0][launch->distance_only != 0][with_distance != 0], t, t.c, *launch, with_distance ? 4u * launch->n : 0u);

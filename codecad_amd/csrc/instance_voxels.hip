@@ -61,26 +61,6 @@ __device__ __forceinline__ VoxelRow voxel_row(const Args& a)
     return VoxelRow{r.x0, r.y0, r.z0 & 0x7fffffffu, r.mask, (r.z0 >> 31) != 0u, r.have};
 }
 
-// instance_mass.hip's sum of a 64-bit value over the 64 lanes of a wavefront, wave-uniform: kernels.hpp
-// wave_sum_to_last_lane on both halves, the carry propagated by the 64-bit add of every step
-template <int CTRL, int ROWS> __device__ __forceinline__ unsigned long long dpp64(unsigned long long v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROWS, 0xf, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xf, false);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-    v += dpp64<0x111, 0xf>(v);   // row_shr:1
-    v += dpp64<0x112, 0xf>(v);   // row_shr:2
-    v += dpp64<0x114, 0xf>(v);   // row_shr:4
-    v += dpp64<0x118, 0xf>(v);   // row_shr:8: lane 15 of a row = its total
-    v += dpp64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += dpp64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-}
-
 // the byte offset of sample (x, y, z): 64 bits (65536^2 runs of up to 65536 bytes)
 __device__ __forceinline__ size_t voxel_offset(const VoxelArgs& k, uint32_t x, uint32_t y, uint32_t z)
 {
@@ -96,12 +76,10 @@ __global__ void __launch_bounds__(256) k_voxel_cells(const VoxelArgs k)
     const uint32_t lane = threadIdx.x & 63u;
     const VoxelRow row = voxel_row(a);
     const uint32_t s = a.child_side;
-    const uint32_t x = row.x0 + (lane >> 4) * s, y = row.y0 + ((lane >> 2) & 3u) * s, z = row.z0 + (lane & 3u) * s;
-    const bool live = row.have & (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
-    const float h = 0.5f * (float)(s - 1u);                      // the child's centre, as k_instance_cells computes it
-    const float px = a.corner[0] + a.step * ((float)x + h);
-    const float py = a.corner[1] + a.step * ((float)y + h);
-    const float pz = a.corner[2] + a.step * ((float)z + h);
+    const ChildLane q = child_lane(a, row, lane);
+    const uint32_t x = q.x, y = q.y, z = q.z;
+    const bool live = q.live;
+    const Point p = child_centre(a, q);
     const float below = k.retire ? -a.thr : -__builtin_inff();   // wave-uniform: nothing is below -inf
     const uint32_t top = row.cand ? 63u - (uint32_t)__builtin_clzll(row.cand) : 0u;
     const uint64_t todo = row.capped ? row.cand & ~(1ull << top) : row.cand;
@@ -111,7 +89,7 @@ __global__ void __launch_bounds__(256) k_voxel_cells(const VoxelArgs k)
     for (uint64_t m = todo; m != 0ull; m &= m - 1ull) {          // wave-uniform, ascending; the one interpreter call site
         if (__ballot(live && owner == kNone) == 0ull) break;     // every live lane has a full candidate below this one
         const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
-        const float w = instance_dist<DO>(a, n, px, py, pz, lds);
+        const float w = instance_dist<DO>(a, n, p.x, p.y, p.z, lds);
         ++evaluated;
         const bool open = owner == kNone;                        // (nothing above a full candidate is kept)
         keep |= (open && !(w >= a.thr)) ? 1ull << n : 0ull;      // (a NaN keeps its candidate)
@@ -121,6 +99,7 @@ __global__ void __launch_bounds__(256) k_voxel_cells(const VoxelArgs k)
         keep |= 1ull << top;
         owner = top;
     }
+    // (the store stays spelled out: through a shared function this kernel compiles to other code; the count is its own product)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && evaluated) atomicAdd(a.evaluations, (unsigned long long)__popcll(lives) * evaluated);
     const bool capped = owner != kNone;
@@ -200,18 +179,18 @@ __global__ void __launch_bounds__(256) k_voxel_leaf(const VoxelArgs k)
     if (!row.have) return;                                        // wave-uniform; this kernel has no barrier
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t dz = lane & 3u;
-    const uint32_t x = row.x0 + (lane >> 4), y = row.y0 + ((lane >> 2) & 3u), z = row.z0 + dz;
-    const bool live = (x < a.dims[0]) & (y < a.dims[1]) & (z < a.dims[2]);
-    // exactly kernels.hpp sample() (the lattice of oracle.grid_eval)
-    const float px = sample(a.corner[0], a.step, x), py = sample(a.corner[1], a.step, y), pz = sample(a.corner[2], a.step, z);
+    const LeafLane l = leaf_lane(a, row);
+    const uint32_t x = l.x, y = l.y;
+    const bool live = l.live;
     const uint32_t top = row.cand ? 63u - (uint32_t)__builtin_clzll(row.cand) : 0u;
     const uint64_t todo = row.capped ? row.cand & ~(1ull << top) : row.cand;
     uint32_t id = kEmpty;
     for (uint64_t m = todo; m != 0ull; m &= m - 1ull) {           // wave-uniform, ascending; the one interpreter call site
         const uint32_t n = uniform((uint32_t)__builtin_ctzll(m));
-        const float w = instance_dist<DO>(a, n, px, py, pz, lds);
+        const float w = instance_dist<DO>(a, n, l.px, l.py, l.pz, lds);
         id = (id == kEmpty && live && w < 0.0f) ? n : id;         // the lowest inside
     }
+    // (the count stays spelled out: with its guard through a shared function this kernel compiles to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && todo) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(todo)));
     if (row.capped) id = (id == kEmpty && live) ? top : id;       // every sample of the cell is inside the capped candidate
@@ -234,17 +213,16 @@ void (*const kVoxelTable[2][2])(VoxelArgs) = {
     {k_voxel_cells<false>, k_voxel_cells<true>},
     {k_voxel_leaf<false>, k_voxel_leaf<true>},
 };
+HU_BIG_LDS(kVoxelTable);
 
-// What both entry points of the part-id volume check and fill: cells_args() of interference's lattice, every index within
-// 16 bits, and a volume whose z runs are `pitch` bytes: a multiple of 16 that holds dims z.
+// What both entry points of the part-id volume check and fill: cells_args() of a strict lattice (every index within
+// 16 bits), and a volume whose z runs are `pitch` bytes: a multiple of 16 that holds dims z.
 int voxel_args(const hu_cells_launch* l, void* volume_dev, uint32_t pitch, void* acc_dev, VoxelArgs& k)
 {
     int rc;
     k = VoxelArgs{};
-    if ((rc = cells_args(false, l, k.c))) return rc;
+    if ((rc = cells_args(kStrict, l, k.c))) return rc;
     if (!volume_dev || !acc_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (l->dims[2] > 65536u) return hu_fail(HU_ERR_BAD_ARG, "lattice dims must be in 1..65536");
-    if (!std::isfinite(l->step) || l->step < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "step must be finite and not negative");
     if ((rc = check_pitch(l->dims, pitch))) return rc;
     if (reinterpret_cast<uintptr_t>(volume_dev) % 16u) return hu_fail(HU_ERR_BAD_ARG, "the volume must be aligned to 16 bytes");
     k.volume = static_cast<uint8_t*>(volume_dev);
@@ -255,11 +233,6 @@ int voxel_args(const hu_cells_launch* l, void* volume_dev, uint32_t pitch, void*
 
 }  // namespace
 
-hipError_t hu_cells::allow_big_lds_voxels(size_t bytes)
-{
-    return allow_big_lds_table(kVoxelTable, bytes);
-}
-
 extern "C" {
 
 int hu_assembly_voxels_cells(const hu_cells_launch* launch, const hu_cells_children* children, int retire, void* volume_dev,
@@ -269,8 +242,7 @@ int hu_assembly_voxels_cells(const hu_cells_launch* launch, const hu_cells_child
     int rc;
     if ((rc = voxel_args(launch, volume_dev, pitch, acc_dev, k))) return rc;
     if ((rc = cells_children(k.c, children))) return rc;
-    if (k.c.child_side < 4u || k.c.child_side > 16384u || (k.c.child_side & (k.c.child_side - 1u)))
-        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 4..16384");
+    if ((rc = check_child_side(k.c.child_side, 4u, 16384u))) return rc;
     if (!std::isfinite(k.c.thr) || k.c.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "thr must be finite and not negative");
     k.retire = retire ? 1u : 0u;
     return cells_launch(kVoxelTable[0][launch->distance_only != 0], k, k.c, *launch, 0u);

@@ -21,6 +21,12 @@
 //                 both wrap the one kernel body of outline_kernels.hpp, each with its own Args type;
 //   instance_mass.hip   the mass properties of an assembly (codecad_amd/assembly_mass.py), likewise;
 //   instance_mesh.hip   the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py), likewise;
+//   instance_voxels.hip the part-id volume of an assembly (codecad_amd/assembly_voxels.py), likewise;
+//   instance_gap.hip    the least gap of every pair of parts (codecad_amd/separation.py), likewise; these eight share
+//                 instance_cells.hpp;
+//   instance_components.hip, instance_thickness.hip, instance_overhang.hip, instance_blocking.hip, instance_contacts.hip
+//                 the kernels that walk the part-id volume (id_volume.hpp): connected components, distance transforms,
+//                 overhangs, which part blocks which, which parts touch;
 //   sort.hip, exchange.hip, mesh.hip  the sort of a block list, the exchange step of the multi-GPU levels, marching cubes.
 #pragma once
 

@@ -39,8 +39,6 @@
 
 namespace hu_cells {
 
-struct Point { float x, y, z; };
-
 // the row of this wavefront: absent (`have` false, mask 0, layer 0) past the list's end and where it names no layer
 __device__ __forceinline__ CellRow outline_row(const OutlineArgs& t) { return cell_row(t.c); }
 __device__ __forceinline__ CellRow outline_row(const LayerArgs& t)
@@ -98,6 +96,7 @@ template <bool DO, class A> __device__ __forceinline__ void outline_tiles(const 
         const float w = instance_dist<DO>(a, n, p.x, p.y, p.z, lds);
         if (reach && !(w >= a.thr) && !(w <= -a.thr)) keep |= 1ull << n;   // may cross an edge of the child (a NaN keeps its candidate)
     }
+    // (the count stays spelled out: through a shared function the tiles compile to other code)
     const uint64_t lives = __ballot(live);
     if (lane == 0u && lives) atomicAdd(a.evaluations, (unsigned long long)(__popcll(lives) * __popcll(row.mask)));
     const bool flag[1] = {live && keep != 0ull};
@@ -197,7 +196,7 @@ int outline_frame_args(const hu_cells_launch* l, const float u[3], const float v
     if (!u || !v) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     std::memset(&t, 0, sizeof(t));
     int rc;
-    if ((rc = cells_args(true, l, t.c, true))) return rc;
+    if ((rc = cells_args(kWindows | kStrict | kPlanar, l, t.c))) return rc;
     for (int i = 0; i < 3; ++i) {
         if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || !std::isfinite(l->corner[i])) return hu_fail(HU_ERR_BAD_ARG, "the plane's frame must be finite");
         t.u[i] = u[i];
@@ -211,8 +210,7 @@ inline int outline_children(Args& a, const hu_cells_children* c)
 {
     int rc;
     if ((rc = cells_children(a, c))) return rc;
-    if (a.child_side < 8u || a.child_side > 8192u || (a.child_side & (a.child_side - 1u)))
-        return hu_fail(HU_ERR_BAD_ARG, "child_side must be a power of two in 8..8192");
+    if ((rc = check_child_side(a.child_side, 8u, 8192u))) return rc;
     if (std::isnan(a.thr) || a.thr < 0.0f) return hu_fail(HU_ERR_BAD_ARG, "radius must not be negative");
     return HU_OK;
 }

@@ -153,15 +153,9 @@ __global__ void __launch_bounds__(256) k_selftest_minmax3(unsigned long long* co
 
 }  // namespace
 
-namespace hu_render {
+HU_BIG_LDS(k_ray_caster<InterpEval<false>>, k_bitmap<InterpEval<false>>, k_bitmap<InterpEval<true>>);
 
-hipError_t allow_big_lds(size_t bytes)
-{
-    hipError_t e = hipFuncSetAttribute((const void*)k_ray_caster<InterpEval<false>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_bitmap<InterpEval<false>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_bitmap<InterpEval<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
-}
+namespace hu_render {
 
 hipError_t ray_caster(const InterpEval<false>& ev, const RayCasterArgs& a, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream)
 {

@@ -29,7 +29,10 @@ whether those supports stand on the plate or on a part, by a scan along the latt
 `disassembly(asm, resolution)` says which part blocks which along the lattice axes, how far a part travels before it meets
 another and in what order the parts come apart by straight moves, by one scan per axis on the device (disassembly.py);
 `contacts(asm, resolution)` says which parts touch, over what area, where, facing which way and in what patches, which parts
-form connected groups and which hang loose, by one pass across the faces of that volume on the device (contacts.py).
+form connected groups and which hang loose, by one pass across the faces of that volume on the device (contacts.py);
+`drainage(asm, resolution, axis, up)` says what the assembly holds when it is drained with a lattice axis pointing up -- cups,
+blind holes, U-bends, pockets between parts --, on which parts each pool stands and how high it fills, by a labelling of the
+layers and a scan with a carry along the lattice lines on the device (drainage.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -59,6 +62,7 @@ from .thin_walls import thin_walls, ThinWallReport  # noqa: F401
 from .overhangs import overhangs, OverhangReport  # noqa: F401
 from .disassembly import disassembly, DisassemblyReport  # noqa: F401
 from .contacts import contacts, ContactReport  # noqa: F401
+from .drainage import drainage, DrainageReport, Pool  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
@@ -67,4 +71,4 @@ __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "m
            "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels",
            "assembly_components", "cavities", "ComponentsReport", "CavityReport", "Component", "Cavity", "EMPTY_SPACE", "SOLID",
            "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport",
-           "contacts", "ContactReport"]
+           "contacts", "ContactReport", "drainage", "DrainageReport", "Pool"]

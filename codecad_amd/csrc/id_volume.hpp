@@ -48,6 +48,40 @@ template <class A> __device__ __forceinline__ ColumnUnit column_unit(const A& a,
 #define HU_FOR_UNITS(unit, units) \
     for (uint64_t unit = (uint64_t)blockIdx.x * 4u + hu_cells::uniform(threadIdx.x >> 6); unit < (units); unit += (uint64_t)gridDim.x * 4u)
 
+// THE UNION-FIND over a uint32 label volume (instance_components.hip states THE INVARIANT: label[q] <= q, entries only ever fall,
+// labels are buffer indices), for every kernel that labels: the components, and the layers of instance_drain.hip.
+// The root of p: labels strictly decrease along the walk (THE INVARIANT, label[p] <= p), so it ends.  A value read here may
+// be stale (a plain load may be served by L1 while another workgroup's atomic has lowered the entry since): a stale parent
+// is still an ancestor -- whoever replaced the link p -> v took on uniting v with what it wrote --, so the walk still ends
+// in p's component, merely not at its newest root.  unite() does not rest on it.
+__device__ __forceinline__ uint32_t find(const uint32_t* label, uint32_t p)
+{
+    for (uint32_t l; (l = label[p]) != p; p = l) {}
+    return p;
+}
+
+// Unites the components of a and b.  The value atomicMin RETURNS decides, never a plain load: old == a says a was a root
+// and now points to b (done); anything else says label[a] was old < a already, and whether the atomic replaced it by b
+// (old > b) or left it (old <= b), what remains is to unite old with b -- retried from the returned value.  max(a, b)
+// strictly decreases from one iteration to the next (old < a by THE INVARIANT), every iteration progresses on this lane's
+// own values, and label[a] is only ever lowered.
+__device__ __forceinline__ void unite(uint32_t* label, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = find(label, a);
+        b = find(label, b);
+        if (a == b) return;
+        if (a < b) {
+            const uint32_t t = a;
+            a = b;
+            b = t;
+        }
+        const uint32_t old = atomicMin(&label[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
 // host side (`dims` is not NULL): the checks, and the fill of the lattice's fields
 inline int check_pitch(const uint32_t dims[3], uint32_t pitch)
 {

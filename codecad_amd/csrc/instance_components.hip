@@ -32,7 +32,7 @@
 //     units while the slot stays the same, and lane 0 issues one atomic per accumulator word when it changes and at the
 //     end.  Slots >= capacity are counted and not touched: the host regrows the table and runs k_comp_stats again.
 //   5 k_comp_finish: an entry becomes the LINEAR index of its root.
-// No kernel has a private array or scratch.  The entry points are at the end of this file.
+// No kernel has a private array or scratch.  find and unite: id_volume.hpp.  The entry points are at the end of this file.
 #include <algorithm>
 
 #include "id_volume.hpp"
@@ -67,38 +67,6 @@ struct CompArgs {
     CompRow* table;
     uint32_t capacity;
 };
-
-// The root of p: labels strictly decrease along the walk (THE INVARIANT, label[p] <= p), so it ends.  A value read here may
-// be stale (a plain load may be served by L1 while another workgroup's atomic has lowered the entry since): a stale parent
-// is still an ancestor -- whoever replaced the link p -> v took on uniting v with what it wrote --, so the walk still ends
-// in p's component, merely not at its newest root.  unite() does not rest on it.
-__device__ __forceinline__ uint32_t find(const uint32_t* label, uint32_t p)
-{
-    for (uint32_t l; (l = label[p]) != p; p = l) {}
-    return p;
-}
-
-// Unites the components of a and b.  The value atomicMin RETURNS decides, never a plain load: old == a says a was a root
-// and now points to b (done); anything else says label[a] was old < a already, and whether the atomic replaced it by b
-// (old > b) or left it (old <= b), what remains is to unite old with b -- retried from the returned value.  max(a, b)
-// strictly decreases from one iteration to the next (old < a by THE INVARIANT), every iteration progresses on this lane's
-// own values, and label[a] is only ever lowered.
-__device__ __forceinline__ void unite(uint32_t* label, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = find(label, a);
-        b = find(label, b);
-        if (a == b) return;
-        if (a < b) {
-            const uint32_t t = a;
-            a = b;
-            b = t;
-        }
-        const uint32_t old = atomicMin(&label[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 __device__ __forceinline__ bool in_flagged_set(uint32_t id, uint32_t solid) { return (id != kEmpty) == (solid != 0u); }
 

@@ -518,6 +518,37 @@ typedef struct hu_contact_row {         /* 64 bytes */
 int hu_contact_faces(const void* ids_dev, void* contact_ids_dev /* may be NULL */, void* rows_dev, uint64_t* counts_dev,
                      const uint32_t dims[3], uint32_t pitch, uint32_t n, void* stream);
 
+/* ---- what an assembly holds when drained along a lattice axis (codecad_amd/drainage.py) ----------
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, aligned to 16 bytes: E is its samples
+ * z < dims[2] with id == 255, S those with another id; nothing outside the lattice is in S, and the padding z in [dims[2], pitch)
+ * of any volume is neither read nor written as data.  Up runs along `axis` (up != 0: the layer of a sample is its index on that
+ * axis; else dims[axis] - 1 - index), "below" is one layer less, the other two axes are the lateral ones.  labels_dev is
+ * uint32[dims[0]][dims[1]][pitch], aligned to 4 bytes, dims[0] * dims[1] * pitch at most 2^31, under the invariant of the
+ * component labelling above: an entry of a sample of E is the index into the buffer of a sample of its LAYER'S component (E
+ * under the edges of the two lateral axes alone) that is not above its own, 0xffffffff outside E, and no call raises an entry.
+ * Bit 31 of a root's entry is its ESCAPE FLAG.  The calls are made in this order on one stream:
+ * hu_drain_layers: labels every layer at once: local != 0 in tiles of HU_COMPONENTS_TILE_X x _Y x _Z samples in LDS, then a
+ *   merge across the tile faces of the two lateral axes; local == 0 from label = own index, a merge of every lateral pair.
+ * hu_components_flatten (above): every entry becomes the index of its root.
+ * hu_drain_seed: a sample of E in layer 0, or with a lateral index of 0 or dims - 1, sets the flag of its root.
+ * hu_drain_rise: one PASS: walks every line of the axis from layer 0 up and sets the flag of the root of every sample of E
+ *   whose sample below is in E under a flagged root, the flags it has set itself on the way included; stores 1 to *changed_dev
+ *   (aligned to 4 bytes; the caller zeroes it before the call) when a flag was newly set.  The caller repeats the call until a
+ *   pass leaves the word zero: at most dims[axis] + 1 passes.  The flagged roots are then those of the samples that ESCAPE.
+ * hu_drain_floor: trapped_dev, a volume of the shape of ids_dev: on a sample of E whose root is not flagged the id of the
+ *   nearest sample of S below it on its line (its FLOOR), 255 on every other sample of the lattice: every in-lattice byte is
+ *   written.  counts_dev[p] (64 uint64, aligned to 8, the caller's zeros) += the samples written with id p (ids are 0..63 or
+ *   255).  One atomic per accumulator and wavefront.
+ * All allocate nothing and synchronise nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL
+ * pointers, a pitch that is no multiple of 16 or below dims[2], dims of 0 or above 65536, an axis outside 0..2, more than 2^31
+ * entries, ids not aligned to 16, labels or the word not to 4 or counts not to 8 bytes. */
+int hu_drain_layers(const void* ids_dev, void* labels_dev, const uint32_t dims[3], uint32_t pitch, int axis, int local,
+                    void* stream);
+int hu_drain_seed(void* labels_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, void* stream);
+int hu_drain_rise(void* labels_dev, uint32_t* changed_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, void* stream);
+int hu_drain_floor(const void* ids_dev, const void* labels_dev, void* trapped_dev, uint64_t* counts_dev, const uint32_t dims[3],
+                   uint32_t pitch, int axis, int up, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

@@ -128,7 +128,8 @@ __global__ void __launch_bounds__(256) k_thick_axis(const ThickArgs a)
             const uint32_t id = active ? a.ids[at] : kEmpty;
             // 1: best is depth_sq, the core is where it reaches the cap R2 + 1 >= 1 (outside S it is 0)
             // 2: best is the capped distance to the core: a sample of S that reaches the cap C2 + 1 is thin
-            const bool counted = active && best == cap && (FINISH == 1 || in_set(id, a.of));
+            // (an empty sample reaches the cap only on inputs no transform makes; it is nobody's, not part 63's)
+            const bool counted = active && best == cap && (FINISH == 1 ? id != kEmpty : in_set(id, a.of));
             if (FINISH == 1) {
                 if (active) a.out[at] = (uint16_t)best;
             } else {

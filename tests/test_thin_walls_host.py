@@ -51,7 +51,7 @@ def test_the_offsets_agree_with_three_capped_passes(name):
     assert numpy.array_equal(depth, ref.depth_sq) and numpy.array_equal(core, ref.core)
     assert numpy.array_equal(thin, ref.thin_ids != EMPTY)
     assert numpy.array_equal(ref.thin_ids[thin], ref.ids[thin]) and (ref.depth_sq[~ref.in_set] == 0).all()
-    assert ref.depth_sq.max() <= c.r2 + 1 and max(ref.ids.shape) <= 64
+    assert ref.depth_sq.max() <= c.r2 + 1 and max(ref.ids.shape) <= (70 if c.scene == "tower" else 64)
     assert sum(r.count for r in ref.regions) == int(thin.sum()) == sum(ref.thin_counts)
 
 
@@ -121,6 +121,38 @@ def test_ragged_reaches_every_border_and_the_largest_radii():
     far = BY_NAME["ragged_far"]
     assert scenes.isqrt(far.r2) > max(dims) and far.c2 == tw.MAX_COVER_SQ == 65534 and scenes.isqrt(far.c2) == 255
     assert tw.axis_tile(255, True) == (64, 0) and tw.axis_tile(scenes.isqrt(far.r2), True) == (216, 1)
+
+
+def test_the_tower_is_thin_exactly_across_the_edge_of_two_segments():
+    dims = [int(d) for d in scene("tower")[5]]
+    assert dims == [12, 12, 70] and av.volume_shape(dims, 2 ** 32)[2] == 80 and (dims[2] + 63) // 64 == 2
+    c, ref = BY_NAME["tower"], reference("tower")
+    assert (c.r2, c.c2) == (4, 12)
+    plate = ref.in_set[:, :, 63:65]
+    assert plate.all() and not ref.in_set[:, :, 56:63].any() and ref.in_set[:, :, :56].all()
+    thin = ref.thin_ids != EMPTY
+    assert set(numpy.argwhere(thin)[:, 2].tolist()) == {63, 64}                      # nothing else is thin, and both layers are
+    assert thin[:, :, 63].sum() > 72 and thin[:, :, 64].sum() > 72 and not thin[:, :, 63].all() and not thin[:, :, 64].all()
+    assert ref.core[:, :, :56].any() and ref.core[:, :, 65:].any() and not ref.core[:, :, 63:65].all()
+    assert int(ref.depth_sq[0, 0, 63]) == 1 == int(ref.depth_sq[0, 0, 64])          # each layer has the other and then background
+    # the thin plate's distances cross z = 63 | 64: the z pass of either segment takes a tap from the other
+    above = scenes.min_plus_1d(numpy.where(ref.in_set, c.r2 + 1, 0)[:, :, 64:], 2, 2, c.r2 + 1, 0)
+    whole = scenes.min_plus_1d(numpy.where(ref.in_set, c.r2 + 1, 0), 2, 2, c.r2 + 1, 0)
+    assert not numpy.array_equal(above[:, :, :2], whole[:, :, 64:66])                # under the pillar z = 64 is two steps from z = 62
+    (region,) = ref.regions
+    assert region.box[0][2] == 63 and region.box[1][2] == 64
+
+
+def test_ragged_crosses_the_switch_from_lds_tiles_to_global_taps():
+    low, high = BY_NAME["ragged_k96"], BY_NAME["ragged_k97"]
+    assert (low.scene, high.scene) == ("ragged", "ragged") and (low.r2, high.r2) == (2, 2)
+    assert (low.c2, high.c2) == (96 * 96, 97 * 97) and (scenes.isqrt(low.c2), scenes.isqrt(high.c2)) == (96, 97)
+    assert scenes.isqrt(low.c2 - 1) == 95 and tw._MAX_LDS_K == 96
+    assert tw.axis_tile(96, True) == (64, 1) and tw.axis_tile(97, True) == (64, 0) and tw.axis_tile(96, False) == (64, 0)
+    for c in (low, high):
+        ref = reference(c.name)
+        assert ref.core.any() and ref.cover.sum() == ref.in_set.sum() and ref.thin_counts == [0] and ref.regions == []
+        assert numpy.array_equal(ref.depth_sq, reference("ragged").depth_sq)         # the first transform is that of `ragged`
 
 
 def test_ownership_decides_between_two_parts():

@@ -131,6 +131,7 @@ RIB = (24, 12, 16)
 WEDGE = (8, 12, 16)
 RAGGED = (13, 9, 11)
 TWO = (12, 12, 12)
+TOWER = (12, 12, 70)
 
 
 def _one(name, shape):
@@ -171,6 +172,13 @@ def _ragged():
     return _one("ragged", _cut(RAGGED, [((2, 0, 6), (10, 9, 11))]))
 
 
+def _tower():
+    """12 x 12 x 70 samples, so that a column holds a second 64-sample segment: a base 56 high, a gap of 7, a plate of the
+    two layers z = 63 and z = 64 -- a wall that is thin exactly across the segments' edge 63 | 64 -- and on the plate a pillar
+    of 5 x 5 up to the top, which keeps the lattice 70 high and covers the plate's corner around it."""
+    return _one("tower", _cut(TOWER, [((0, 0, 56), (12, 12, 63)), ((0, 0, 65), (7, 12, 70)), ((7, 0, 65), (12, 7, 70))]))
+
+
 def _plate_on_block():
     """A plate of 2 samples (part 0) glued to a block of 10 (part 1)."""
     return cc.assembly("glued", [_box(TWO, (0, 0, 0), (2, 12, 12)).make_part("plate"), _box(TWO, (2, 0, 0), (12, 12, 12)).make_part("block")])
@@ -181,7 +189,7 @@ def _pin_in_block():
     return cc.assembly("pressed", [_box(TWO, (5, 5, 0), (7, 7, 12)).make_part("pin"), _box(TWO, (0, 0, 0), TWO).make_part("block")])
 
 
-SCENES = {"bars": _bars, "rib": _rib, "wedge": _wedge, "ragged": _ragged, "plate_on_block": _plate_on_block,
+SCENES = {"bars": _bars, "rib": _rib, "tower": _tower, "wedge": _wedge, "ragged": _ragged, "plate_on_block": _plate_on_block,
           "pin_in_block": _pin_in_block, "shell": comp._shell,
           "cuboid_5": functools.partial(_cuboid, (5, 5, 5)), "cuboid_4": functools.partial(_cuboid, (5, 4, 5))}
 for _axis, (_k, _w) in itertools.product(range(3), SLABS):
@@ -211,6 +219,9 @@ CASES += [
     Case("pressed_pin", "pin_in_block", 0, 4, 12, ALL_THIN),
     Case("pressed_block", "pin_in_block", 1, 4, 12, NONE_THIN),
     Case("shell", "shell", SOLID, 16, 48, ALL_THIN),
+    Case("tower", "tower", SOLID, 4, 12, MIXED),                           # nz = 70: the z passes stage a halo from another segment
+    Case("ragged_k96", "ragged", SOLID, 2, 9216, NONE_THIN),               # K2 = 96: the last K whose y and x passes stage a tile in LDS
+    Case("ragged_k97", "ragged", SOLID, 2, 9409, NONE_THIN),               # K2 = 97: the first whose taps come from global memory
 ]
 BY_NAME = {c.name: c for c in CASES}
 NAMES = [c.name for c in CASES]

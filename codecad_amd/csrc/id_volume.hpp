@@ -44,6 +44,25 @@ template <class A> __device__ __forceinline__ ColumnUnit column_unit(const A& a,
     return u;
 }
 
+// unit `unit` of line_units(a), axis 0 or 1: 64 consecutive z of the LINES of one y (along x) or one x (along y); lane `lane`
+// has z, and its sample of layer index t along the axis is the byte base + t * stride (`line` is wave-uniform, z may be >= nz)
+template <class I> struct LineUnitOf {
+    uint32_t line, z;
+    I base, stride;
+};
+using LineUnit = LineUnitOf<size_t>;
+// (device and host: at most 65536 lines of 1024 words)
+template <class A> __host__ __device__ __forceinline__ uint64_t line_units(const A& a) { return (uint64_t)(a.axis == 0u ? a.ny : a.nx) * a.segments; }
+template <class I = size_t, class A> __device__ __forceinline__ LineUnitOf<I> line_unit(const A& a, uint64_t unit, uint32_t lane)
+{
+    LineUnitOf<I> u;
+    u.line = (uint32_t)(unit / a.segments);
+    u.z = (((uint32_t)(unit - (uint64_t)u.line * a.segments)) << 6) + lane;
+    u.stride = a.axis == 0u ? (I)a.ny * a.pitch : (I)a.pitch;
+    u.base = (a.axis == 0u ? (I)u.line * a.pitch : (I)u.line * a.ny * a.pitch) + u.z;
+    return u;
+}
+
 // a wavefront takes the units w, w + W, w + 2 W, ... of `units`, W the wavefronts of the grid (wave-uniform), and gathers over all
 #define HU_FOR_UNITS(unit, units) \
     for (uint64_t unit = (uint64_t)blockIdx.x * 4u + hu_cells::uniform(threadIdx.x >> 6); unit < (units); unit += (uint64_t)gridDim.x * 4u)
@@ -96,7 +115,7 @@ template <class A> int lattice_of(const uint32_t dims[3], uint32_t pitch, A& a)
     a.nx = dims[0], a.ny = dims[1], a.nz = dims[2], a.pitch = pitch;
     return check_pitch(dims, pitch);
 }
-template <class A> int lattice_units(int axis, A& a)
+template <class A> int lattice_axis(int axis, A& a)
 {
     if (axis < 0 || axis > 2) return hu_fail(HU_ERR_BAD_ARG, "axis must be 0 (x), 1 (y) or 2 (z)");
     a.na = axis == 0 ? a.nx : axis == 1 ? a.ny : a.nz, a.segments = (a.nz + 63u) / 64u;

@@ -96,19 +96,17 @@ __global__ void __launch_bounds__(256) k_block_lines(const BlockArgs a)
     uint16_t* last = reinterpret_cast<uint16_t*>(block_lds + a.n * a.n) + threadIdx.x;   // [part][256]: this lane's column
     const uint32_t lane = threadIdx.x & 63u;
     reset_table(table, a.n * a.n);
-    const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
-    const size_t stride = a.axis == 0u ? (size_t)a.ny * a.pitch : (size_t)a.pitch;
-    HU_FOR_UNITS(unit, (uint64_t)lines * a.segments) {
-        const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
-        const bool active = z < a.nz;
-        const uint8_t* at = a.ids + (a.axis == 0u ? (size_t)line * a.pitch : (size_t)line * a.ny * a.pitch) + z;
+    HU_FOR_UNITS(unit, line_units(a)) {
+        const LineUnit u = line_unit(a, unit, lane);
+        const bool active = u.z < a.nz;
+        const uint8_t* at = a.ids + u.base;
         uint32_t prev = kEmpty;                                                   // the id of the sample below
         uint64_t seen = 0ull;                                                     // the parts with a last index
         for (uint32_t t0 = 0u; t0 < a.na; t0 += kBatch) {                         // wave-uniform: up the axis
             uint32_t batch[kBatch];                                               // (unrolled: registers)
 #pragma unroll
             for (uint32_t k = 0u; k < kBatch; ++k)
-                batch[k] = active && t0 + k < a.na ? id_at(at + (size_t)(t0 + k) * stride, a.n) : kEmpty;
+                batch[k] = active && t0 + k < a.na ? id_at(at + (size_t)(t0 + k) * u.stride, a.n) : kEmpty;
 #pragma unroll
             for (uint32_t k = 0u; k < kBatch; ++k) {
                 const uint32_t id = batch[k], t = t0 + k;                         // (past the line's end: 255, which starts nothing)
@@ -121,7 +119,7 @@ __global__ void __launch_bounds__(256) k_block_lines(const BlockArgs a)
                     if (id != kEmpty)                                             // a run of `id` starts at t
                         for (uint64_t m = seen & ~(1ull << id); m != 0ull; m &= m - 1ull) {
                             const uint32_t i = (uint32_t)__builtin_ctzll(m), p = last[i * 256u];
-                            lower(&table[i * a.n + id], a.axis == 0u ? key_of(t - p, p, line, z) : key_of(t - p, line, p, z));
+                            lower(&table[i * a.n + id], a.axis == 0u ? key_of(t - p, p, u.line, u.z) : key_of(t - p, u.line, p, u.z));
                         }
                     prev = id;
                 }
@@ -172,7 +170,7 @@ int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t di
     if (reinterpret_cast<uintptr_t>(keys_dev) % 8u) return hu_fail(HU_ERR_BAD_ARG, "the key table must be aligned to 8 bytes");
     BlockArgs a{};
     if (int rc = lattice_of(dims, pitch, a)) return rc;
-    if (int rc = lattice_units(axis, a)) return rc;
+    if (int rc = lattice_axis(axis, a)) return rc;
     if (n == 0u || n > kParts) return hu_fail(HU_ERR_BAD_ARG, "n must be in 1..64");
     a.ids = static_cast<const uint8_t*>(ids_dev);
     a.keys = reinterpret_cast<unsigned long long*>(keys_dev) + (size_t)axis * kParts * kParts;
@@ -184,8 +182,7 @@ int hu_blocking_lines(const void* ids_dev, uint64_t* keys_dev, const uint32_t di
     if (axis == 2) {                                                              // four columns a wavefront at the least
         hipLaunchKernelGGL(k_block_columns, dim3(walking_blocks((uint64_t)a.nx * a.ny, 4u)), dim3(256), table, s, a);
     } else {                                                                      // a unit is a whole walk up the axis: one each
-        const uint64_t units = (uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments;
-        hipLaunchKernelGGL(k_block_lines, dim3(walking_blocks(units, 1u)), dim3(256), table + (size_t)n * 512u, s, a);
+        hipLaunchKernelGGL(k_block_lines, dim3(walking_blocks(line_units(a), 1u)), dim3(256), table + (size_t)n * 512u, s, a);
     }
     HU_HIP(hipGetLastError());
     return HU_OK;

@@ -17,13 +17,13 @@
 // Every loop over global memory (find, unite) follows labels that strictly decrease, so it ends after at most q steps
 // whatever other wavefronts do; there is no lock, no flag and no wait for anybody's progress.
 //
-//   1 k_comp_local<true>: a workgroup of 256 owns a tile of 8 x 8 x 16 samples (z a whole aligned 16-byte run of the
-//     volume: the bytes come in as one 16-byte load per column, 64 lanes).  The tile's part of S is labelled in LDS by the
-//     same union-find (4 KiB of labels, 256 B of column masks), every sample unites with its three forward neighbours
-//     inside the tile, and writes the buffer index of its tile-local root; NONE outside S and in the padding.
+// Stages 1 and 2 are THE ONE LABELLING BODY of label_kernels.hpp, which describes it, wrapped with the predicate of `solid`
+// and every edge (edges = 7, a constant); instance_drain.hip wraps the same body for its layers.
+//   1 k_comp_local<true>: label_tile, a tile of 8 x 8 x 16 samples labelled in LDS (4 KiB of labels, 256 B of column
+//     masks), every sample united with its three forward neighbours inside the tile; NONE outside S and in the padding.
 //     k_comp_local<false> (the comparison arm) writes label = own index.
-//   2 k_comp_merge_faces: a lane per pair of samples across a tile face (x = 8 k - 1, y = 8 k - 1, z = 16 k - 1), three
-//     ranges of one launch; k_comp_merge_all (the comparison arm): a lane per sample, its three forward neighbours.
+//   2 k_comp_merge_faces: label_merge_faces, a lane per pair of samples across a tile face, three ranges of one launch
+//     (blockIdx.y is the axis); k_comp_merge_all (the comparison arm): label_merge_all, a lane per sample.
 //   3 k_comp_flatten: every sample of S replaces its label by its root.
 //   4 k_comp_roots: a root (label == own index) takes a slot from *counter (one atomic per wavefront) and keeps
 //     0x80000000 | slot in its own entry -- no third volume.  k_comp_stats: a unit is 64 consecutive z of one (x, y)
@@ -32,21 +32,18 @@
 //     units while the slot stays the same, and lane 0 issues one atomic per accumulator word when it changes and at the
 //     end.  Slots >= capacity are counted and not touched: the host regrows the table and runs k_comp_stats again.
 //   5 k_comp_finish: an entry becomes the LINEAR index of its root.
-// No kernel has a private array or scratch.  find and unite: id_volume.hpp.  The entry points are at the end of this file.
+// No kernel has a private array or scratch.  find and unite: id_volume.hpp; kNone, the tiles, blocks_of: label_kernels.hpp.  The entry points are at the end of this file.
 #include <algorithm>
 
-#include "id_volume.hpp"
+#include "id_volume.hpp"            // stages 3 to 5: find, the volume's contract
+#include "label_kernels.hpp"        // stages 1 and 2
 
 using namespace sdfk;
 using namespace hu_cells;
 
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;     // the label of a sample outside S
 constexpr uint32_t kSlot = 0x80000000u;     // stage 4: the entry of a root holds kSlot | slot
-constexpr uint32_t kTileX = HU_COMPONENTS_TILE_X, kTileY = HU_COMPONENTS_TILE_Y, kTileZ = HU_COMPONENTS_TILE_Z;
-constexpr uint32_t kTile = kTileX * kTileY * kTileZ;
-static_assert(kTileX == 8u && kTileY == 8u && kTileZ == 16u && kTile == 1024u, "the index arithmetic of k_comp_local");
 
 // the accumulators of a component (72 bytes; the host's dtype is assembly_components._ROW).  A zeroed row is an empty one:
 // the low corner of the box is kept COMPLEMENTED, so that it grows by atomicMax from 0 like everything else.
@@ -73,119 +70,13 @@ __device__ __forceinline__ bool in_flagged_set(uint32_t id, uint32_t solid) { re
 template <bool LOCAL>
 __global__ void __launch_bounds__(256) k_comp_local(const CompArgs k)
 {
-    __shared__ uint32_t lab[kTile];
-    __shared__ uint32_t column[kTileX * kTileY];     // bit dz: sample dz of the column is in S
-    const uint32_t t = threadIdx.x;
-    const uint32_t x0 = blockIdx.z * kTileX, y0 = blockIdx.y * kTileY, z0 = blockIdx.x * kTileZ;   // z0 < pitch
-    if (t < kTileX * kTileY) {
-        const uint32_t x = x0 + (t >> 3), y = y0 + (t & 7u);
-        uint32_t mask = 0u;
-        if (x < k.nx && y < k.ny) {
-            // z0 and the pitch are multiples of 16 and the volume is aligned: one aligned 16-byte load inside the row
-            const uint4 v = *reinterpret_cast<const uint4*>(k.volume + ((size_t)x * k.ny + y) * k.pitch + z0);
-#pragma unroll
-            for (uint32_t dz = 0; dz < 16u; ++dz) {
-                const uint32_t word = dz < 4u ? v.x : dz < 8u ? v.y : dz < 12u ? v.z : v.w;
-                const bool in = z0 + dz < k.nz && in_flagged_set((word >> (8u * (dz & 3u))) & 0xffu, k.solid);   // (the padding is not in S)
-                mask |= in ? 1u << dz : 0u;
-            }
-        }
-        column[t] = mask;
-    }
-    __syncthreads();
-    // tile-local index i = (dx * 8 + dy) * 16 + dz: ordered like the buffer index, so the least i is the least q.
-    // THE INVARIANT is established here, in LDS: lab[i] = i.
-#pragma unroll
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t i = t + 256u * j;
-        lab[i] = ((column[i >> 4] >> (i & 15u)) & 1u) ? i : kNone;
-    }
-    __syncthreads();
-    if (LOCAL) {
-#pragma unroll
-        for (uint32_t j = 0; j < 4u; ++j) {
-            const uint32_t i = t + 256u * j, c = i >> 4, dz = i & 15u;
-            const uint32_t mine = column[c];
-            if (!((mine >> dz) & 1u)) continue;
-            if (dz < 15u && ((mine >> (dz + 1u)) & 1u)) unite(lab, i, i + 1u);
-            if ((c & 7u) < 7u && ((column[c + 1u] >> dz) & 1u)) unite(lab, i, i + 16u);
-            if (c < 56u && ((column[c + 8u] >> dz) & 1u)) unite(lab, i, i + 128u);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t i = t + 256u * j;
-        const uint32_t x = x0 + (i >> 7), y = y0 + ((i >> 4) & 7u), z = z0 + (i & 15u);
-        if (x >= k.nx || y >= k.ny) continue;                   // (z < pitch: the tiles along z cover the pitch exactly)
-        uint32_t out = kNone;
-        if (lab[i] != kNone) {
-            const uint32_t r = LOCAL ? find(lab, i) : i;         // r <= i, so the root's buffer index is <= this sample's
-            out = ((x0 + (r >> 7)) * k.ny + (y0 + ((r >> 4) & 7u))) * k.pitch + z0 + (r & 15u);
-        }
-        k.labels[((size_t)x * k.ny + y) * k.pitch + z] = out;   // THE INVARIANT in global memory: label[q] <= q
-    }
+    label_tile<LOCAL>(k, k.volume, [solid = k.solid](uint32_t id) { return in_flagged_set(id, solid); }, 7u);
 }
 
-// blockIdx.y = the axis.  Faces between tiles: fx = (nx - 1) / 8 planes x = 8 (f + 1) - 1 (whose x + 1 exists), and so on.
-__global__ void __launch_bounds__(256) k_comp_merge_faces(const CompArgs k)
-{
-    const uint32_t axis = blockIdx.y;
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint32_t faces = axis == 0u ? (k.nx - 1u) / kTileX : axis == 1u ? (k.ny - 1u) / kTileY : (k.nz - 1u) / kTileZ;
-    uint32_t x, y, z, stride;
-    uint64_t count;
-    if (axis == 0u) {
-        const uint64_t plane = (uint64_t)k.ny * k.nz;
-        count = faces * plane;
-        if (i >= count) return;
-        const uint32_t f = (uint32_t)(i / plane), rest = (uint32_t)(i - f * plane);
-        x = kTileX * (f + 1u) - 1u, y = rest / k.nz, z = rest - y * k.nz;
-        stride = k.ny * k.pitch;
-    } else if (axis == 1u) {
-        const uint64_t slab = (uint64_t)faces * k.nz;
-        count = k.nx * slab;
-        if (i >= count) return;
-        x = (uint32_t)(i / slab);
-        const uint32_t rest = (uint32_t)(i - x * slab), f = rest / k.nz;
-        y = kTileY * (f + 1u) - 1u, z = rest - f * k.nz;
-        stride = k.pitch;
-    } else {
-        const uint64_t slab = (uint64_t)k.ny * faces;
-        count = k.nx * slab;
-        if (i >= count) return;
-        x = (uint32_t)(i / slab);
-        const uint32_t rest = (uint32_t)(i - x * slab);
-        y = rest / faces;
-        z = kTileZ * (rest - y * faces + 1u) - 1u;
-        stride = 1u;
-    }
-    const uint32_t q = (x * k.ny + y) * k.pitch + z;             // q + stride is the sample one step on: it exists
-    const uint32_t a = k.labels[q], b = k.labels[q + stride];
-    if (a != kNone && b != kNone) unite(k.labels, a, b);          // (a label is an ancestor: a start as good as q)
-}
+// blockIdx.y = the axis
+__global__ void __launch_bounds__(256) k_comp_merge_faces(const CompArgs k) { label_merge_faces(k, blockIdx.y); }
 
-__global__ void __launch_bounds__(256) k_comp_merge_all(const CompArgs k)
-{
-    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-    if (q >= k.total) return;
-    const uint32_t row = q / k.pitch, z = q - row * k.pitch, x = row / k.ny, y = row - x * k.ny;
-    if (z >= k.nz) return;
-    const uint32_t a = k.labels[q];
-    if (a == kNone) return;
-    if (z + 1u < k.nz) {
-        const uint32_t b = k.labels[q + 1u];
-        if (b != kNone) unite(k.labels, a, b);
-    }
-    if (y + 1u < k.ny) {
-        const uint32_t b = k.labels[q + k.pitch];
-        if (b != kNone) unite(k.labels, a, b);
-    }
-    if (x + 1u < k.nx) {
-        const uint32_t b = k.labels[q + k.ny * k.pitch];
-        if (b != kNone) unite(k.labels, a, b);
-    }
-}
+__global__ void __launch_bounds__(256) k_comp_merge_all(const CompArgs k) { label_merge_all(k, 7u); }
 
 __global__ void __launch_bounds__(256) k_comp_flatten(const CompArgs k)
 {
@@ -323,18 +214,13 @@ int comp_args(const void* volume_dev, void* labels_dev, const uint32_t dims[3], 
 {
     k = CompArgs{};
     if (!labels_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (int rc = lattice_of(dims, pitch, k)) return rc;
-    const unsigned __int128 total = (unsigned __int128)dims[0] * dims[1] * pitch;
-    if (total > ((unsigned __int128)1 << 31)) return hu_fail(HU_ERR_BAD_ARG, "a label volume holds at most 2^31 entries");
-    if (reinterpret_cast<uintptr_t>(volume_dev) % 16u || reinterpret_cast<uintptr_t>(labels_dev) % 4u)
-        return hu_fail(HU_ERR_BAD_ARG, "the volume must be aligned to 16 bytes, the labels to 4");
+    const char* misaligned = "the volume must be aligned to 16 bytes, the labels to 4";
+    int rc;
+    if ((rc = lattice_of(dims, pitch, k)) || (rc = labels_of(labels_dev, misaligned, k))) return rc;
+    if (reinterpret_cast<uintptr_t>(volume_dev) % 16u) return hu_fail(HU_ERR_BAD_ARG, misaligned);
     k.volume = static_cast<const uint8_t*>(volume_dev);
-    k.labels = static_cast<uint32_t*>(labels_dev);
-    k.total = (uint32_t)total;
     return HU_OK;
 }
-
-inline uint32_t blocks_of(uint64_t lanes) { return (uint32_t)((lanes + 255u) / 256u); }
 
 }  // namespace
 
@@ -348,11 +234,10 @@ int hu_components_local(const void* volume_dev, void* labels_dev, const uint32_t
     if ((rc = comp_args(volume_dev, labels_dev, dims, pitch, k))) return rc;
     if (!volume_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     k.solid = solid ? 1u : 0u;
-    const dim3 grid(pitch / kTileZ, (k.ny + kTileY - 1u) / kTileY, (k.nx + kTileX - 1u) / kTileX);
     if (local)
-        hipLaunchKernelGGL(k_comp_local<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), k);
+        hipLaunchKernelGGL(k_comp_local<true>, tile_grid(k), dim3(256), 0, static_cast<hipStream_t>(stream), k);
     else
-        hipLaunchKernelGGL(k_comp_local<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), k);
+        hipLaunchKernelGGL(k_comp_local<false>, tile_grid(k), dim3(256), 0, static_cast<hipStream_t>(stream), k);
     HU_HIP(hipGetLastError());
     return HU_OK;
 }
@@ -363,9 +248,7 @@ int hu_components_merge(void* labels_dev, const uint32_t dims[3], uint32_t pitch
     int rc;
     if ((rc = comp_args(nullptr, labels_dev, dims, pitch, k))) return rc;
     if (local) {
-        const uint64_t fx = (uint64_t)((k.nx - 1u) / kTileX) * k.ny * k.nz, fy = (uint64_t)k.nx * ((k.ny - 1u) / kTileY) * k.nz,
-                       fz = (uint64_t)k.nx * k.ny * ((k.nz - 1u) / kTileZ);
-        const uint64_t most = std::max(fx, std::max(fy, fz));
+        const uint64_t most = std::max(face_pairs(k, 0u), std::max(face_pairs(k, 1u), face_pairs(k, 2u)));
         if (most == 0u) return HU_OK;                              // one tile: nothing to merge
         hipLaunchKernelGGL(k_comp_merge_faces, dim3(blocks_of(most), 3), dim3(256), 0, static_cast<hipStream_t>(stream), k);
     } else {

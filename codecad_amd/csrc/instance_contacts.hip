@@ -49,7 +49,7 @@ struct ContactArgs {
     unsigned long long* counts;         // [7][64]: exposed [a][0], [a][1] per axis a, then the interface samples
     uint32_t nx, ny, nz, pitch;
     uint32_t n;
-    uint32_t na;                        // (lattice_units: nz)
+    uint32_t na;                        // (lattice_axis: nz)
     uint32_t segments;                  // ceil(nz / 64)
 };
 
@@ -177,7 +177,7 @@ int hu_contact_faces(const void* ids_dev, void* contact_ids_dev, void* rows_dev,
         return hu_fail(HU_ERR_BAD_ARG, "the rows and the counts must be aligned to 8 bytes");
     ContactArgs a{};
     if (int rc = lattice_of(dims, pitch, a)) return rc;
-    if (int rc = lattice_units(2, a)) return rc;
+    if (int rc = lattice_axis(2, a)) return rc;
     if (n == 0u || n > kParts) return hu_fail(HU_ERR_BAD_ARG, "n must be in 1..64");
     a.ids = static_cast<const uint8_t*>(ids_dev);
     a.contact = static_cast<uint8_t*>(contact_ids_dev);

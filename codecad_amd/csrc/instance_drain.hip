@@ -10,8 +10,9 @@
 // Nothing outside the lattice is in S, and no byte of the padding z in [nz, pitch) is read or written as data.
 //
 // MONOTONE REACHABILITY: connected within a layer, handed on from layer to layer in one direction only.
-//   1 k_drain_local / k_drain_merge_*: the union-find of instance_components.hip (id_volume.hpp has find and unite, that file
-//     THE INVARIANT) over E with the edges of the two lateral axes only: every layer is labelled at once, no edge crosses layers.
+//   1 k_drain_local / k_drain_merge_*: the union-find of instance_components.hip BY CONSTRUCTION: they wrap the one labelling
+//     body of label_kernels.hpp (instance_components.hip states THE INVARIANT, id_volume.hpp has find and unite) with the predicate id == 255
+//     and edges = lateral(): the two lateral axes only, so every layer is labelled at once and no edge crosses layers.
 //     k_drain_local<true>: a tile of 8 x 8 x 16 samples in LDS (4 KiB of labels, 256 B of column masks), then k_drain_merge_faces,
 //     a lane per pair across the tile faces of the two lateral axes.  k_drain_local<false> writes label = own index and
 //     k_drain_merge_all, a lane per sample, unites its two forward lateral neighbours: the comparison arm, the same bytes.
@@ -22,7 +23,7 @@
 //   3 k_drain_rise, one PASS a launch: every p of E whose sample below is in E under a flagged root flags its own root, and
 //     *changed is set when a flag was newly set (the value atomicOr returns decides).  A pass walks every line of the axis from
 //     layer 0 upwards and carries "the sample below escapes", so a straight shaft rises through all its layers in one pass.
-//     <false> (axis 0 or 1): a wavefront owns 64 consecutive z of one line, the carry is a register per lane, kBatch entries and
+//     <false> (axis 0 or 1): a wavefront owns 64 consecutive z of one line (line_unit of id_volume.hpp), the carry is a register per lane, kBatch entries and
 //     then their roots' entries are in flight.  <true> (axis 2): the line is the wavefront itself; it takes the ballots of E and of
 //     the flags it read (bit-reversed for s < 0, so that a higher bit is always ABOVE), floods the flag bits upwards through the
 //     runs of E by the carry of one addition and hands the top bit on into the next word.  Along one line every sample lies in
@@ -40,17 +41,14 @@
 // No kernel has a private array or scratch (the batches are unrolled: registers).  Entry points: at the end.
 #include <algorithm>
 
-#include "id_volume.hpp"
+#include "id_volume.hpp"            // stages 2 to 4: the units, their walk, gather_counts
+#include "label_kernels.hpp"        // stage 1
 
 using namespace hu_cells;
 
 namespace {
 
-constexpr uint32_t kNone = 0xffffffffu;     // the label of a sample outside E
 constexpr uint32_t kFlag = 0x80000000u;     // a root's entry: index | kFlag once its component escapes
-constexpr uint32_t kTileX = HU_COMPONENTS_TILE_X, kTileY = HU_COMPONENTS_TILE_Y, kTileZ = HU_COMPONENTS_TILE_Z;
-constexpr uint32_t kTile = kTileX * kTileY * kTileZ;
-static_assert(kTileX == 8u && kTileY == 8u && kTileZ == 16u && kTile == 1024u, "the index arithmetic of k_drain_local");
 constexpr uint32_t kBatch = 4u;             // layers a lane of the walks along x and y has in flight
 
 struct DrainArgs {
@@ -68,118 +66,22 @@ struct DrainArgs {
 
 // ---- stage 1: the layers' components ----------------------------------------------------------------------------------
 
+// the edges of the two lateral axes: the forward neighbour along the axis lies in another layer
+__device__ __forceinline__ uint32_t lateral(const DrainArgs& k) { return 7u & ~(1u << k.axis); }
+
 template <bool LOCAL>
 __global__ void __launch_bounds__(256) k_drain_local(const DrainArgs k)
 {
-    __shared__ uint32_t lab[kTile];
-    __shared__ uint32_t column[kTileX * kTileY];     // bit dz: sample dz of the column is in E
-    const uint32_t t = threadIdx.x;
-    const uint32_t x0 = blockIdx.z * kTileX, y0 = blockIdx.y * kTileY, z0 = blockIdx.x * kTileZ;   // z0 < pitch
-    if (t < kTileX * kTileY) {
-        const uint32_t x = x0 + (t >> 3), y = y0 + (t & 7u);
-        uint32_t mask = 0u;
-        if (x < k.nx && y < k.ny) {
-            // z0 and the pitch are multiples of 16 and the volume is aligned: one aligned 16-byte load inside the row
-            const uint4 v = *reinterpret_cast<const uint4*>(k.ids + ((size_t)x * k.ny + y) * k.pitch + z0);
-#pragma unroll
-            for (uint32_t dz = 0; dz < 16u; ++dz) {
-                const uint32_t word = dz < 4u ? v.x : dz < 8u ? v.y : dz < 12u ? v.z : v.w;
-                const bool in = z0 + dz < k.nz && ((word >> (8u * (dz & 3u))) & 0xffu) == kEmpty;   // (the padding is not in E)
-                mask |= in ? 1u << dz : 0u;
-            }
-        }
-        column[t] = mask;
-    }
-    __syncthreads();
-    // tile-local index i = (dx * 8 + dy) * 16 + dz: ordered like the buffer index, so the least i is the least q
-#pragma unroll
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t i = t + 256u * j;
-        lab[i] = ((column[i >> 4] >> (i & 15u)) & 1u) ? i : kNone;
-    }
-    __syncthreads();
-    if (LOCAL) {
-#pragma unroll
-        for (uint32_t j = 0; j < 4u; ++j) {
-            const uint32_t i = t + 256u * j, c = i >> 4, dz = i & 15u;
-            const uint32_t mine = column[c];
-            if (!((mine >> dz) & 1u)) continue;
-            // the forward neighbours of the two lateral axes: the one along the axis lies in another layer
-            if (k.axis != 2u && dz < 15u && ((mine >> (dz + 1u)) & 1u)) unite(lab, i, i + 1u);
-            if (k.axis != 1u && (c & 7u) < 7u && ((column[c + 1u] >> dz) & 1u)) unite(lab, i, i + 16u);
-            if (k.axis != 0u && c < 56u && ((column[c + 8u] >> dz) & 1u)) unite(lab, i, i + 128u);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t i = t + 256u * j;
-        const uint32_t x = x0 + (i >> 7), y = y0 + ((i >> 4) & 7u), z = z0 + (i & 15u);
-        if (x >= k.nx || y >= k.ny) continue;                   // (z < pitch: the tiles along z cover the pitch exactly)
-        uint32_t out = kNone;
-        if (lab[i] != kNone) {
-            const uint32_t r = LOCAL ? find(lab, i) : i;         // r <= i, so the root's buffer index is <= this sample's
-            out = ((x0 + (r >> 7)) * k.ny + (y0 + ((r >> 4) & 7u))) * k.pitch + z0 + (r & 15u);
-        }
-        k.labels[((size_t)x * k.ny + y) * k.pitch + z] = out;   // THE INVARIANT in global memory: label[q] <= q
-    }
+    label_tile<LOCAL>(k, k.ids, [](uint32_t id) { return id == kEmpty; }, lateral(k));
 }
 
-// blockIdx.y = 0, 1: the lateral axes in ascending order.  Faces between tiles: as k_comp_merge_faces has them.
+// blockIdx.y = 0, 1: the lateral axes in ascending order
 __global__ void __launch_bounds__(256) k_drain_merge_faces(const DrainArgs k)
 {
-    const uint32_t axis = blockIdx.y == 0u ? (k.axis == 0u ? 1u : 0u) : (k.axis == 2u ? 1u : 2u);
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint32_t faces = axis == 0u ? (k.nx - 1u) / kTileX : axis == 1u ? (k.ny - 1u) / kTileY : (k.nz - 1u) / kTileZ;
-    uint32_t x, y, z, stride;
-    if (axis == 0u) {
-        const uint64_t plane = (uint64_t)k.ny * k.nz;
-        if (i >= faces * plane) return;
-        const uint32_t f = (uint32_t)(i / plane), rest = (uint32_t)(i - f * plane);
-        x = kTileX * (f + 1u) - 1u, y = rest / k.nz, z = rest - y * k.nz;
-        stride = k.ny * k.pitch;
-    } else if (axis == 1u) {
-        const uint64_t slab = (uint64_t)faces * k.nz;
-        if (i >= k.nx * slab) return;
-        x = (uint32_t)(i / slab);
-        const uint32_t rest = (uint32_t)(i - x * slab), f = rest / k.nz;
-        y = kTileY * (f + 1u) - 1u, z = rest - f * k.nz;
-        stride = k.pitch;
-    } else {
-        const uint64_t slab = (uint64_t)k.ny * faces;
-        if (i >= k.nx * slab) return;
-        x = (uint32_t)(i / slab);
-        const uint32_t rest = (uint32_t)(i - x * slab);
-        y = rest / faces;
-        z = kTileZ * (rest - y * faces + 1u) - 1u;
-        stride = 1u;
-    }
-    const uint32_t q = (x * k.ny + y) * k.pitch + z;             // q + stride is the sample one step on: it exists
-    const uint32_t a = k.labels[q], b = k.labels[q + stride];
-    if (a != kNone && b != kNone) unite(k.labels, a, b);          // (a label is an ancestor: a start as good as q)
+    label_merge_faces(k, blockIdx.y == 0u ? (k.axis == 0u ? 1u : 0u) : (k.axis == 2u ? 1u : 2u));
 }
 
-__global__ void __launch_bounds__(256) k_drain_merge_all(const DrainArgs k)
-{
-    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-    if (q >= k.total) return;
-    const uint32_t row = q / k.pitch, z = q - row * k.pitch, x = row / k.ny, y = row - x * k.ny;
-    if (z >= k.nz) return;
-    const uint32_t a = k.labels[q];
-    if (a == kNone) return;
-    if (k.axis != 2u && z + 1u < k.nz) {
-        const uint32_t b = k.labels[q + 1u];
-        if (b != kNone) unite(k.labels, a, b);
-    }
-    if (k.axis != 1u && y + 1u < k.ny) {
-        const uint32_t b = k.labels[q + k.pitch];
-        if (b != kNone) unite(k.labels, a, b);
-    }
-    if (k.axis != 0u && x + 1u < k.nx) {
-        const uint32_t b = k.labels[q + k.ny * k.pitch];
-        if (b != kNone) unite(k.labels, a, b);
-    }
-}
+__global__ void __launch_bounds__(256) k_drain_merge_all(const DrainArgs k) { label_merge_all(k, lateral(k)); }
 
 // ---- stages 2 and 3: the flags ----------------------------------------------------------------------------------------
 
@@ -243,12 +145,10 @@ __global__ void __launch_bounds__(256) k_drain_rise(const DrainArgs a)
     if (!ALONG_Z) {
         // a line along x is one y, along y one x; 64 consecutive z of it, one such unit a wavefront
         const uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6);
-        const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
-        if (unit >= (uint64_t)lines * a.segments) return;
-        const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
-        const bool active = z < a.nz;
-        const uint32_t stride = a.axis == 0u ? a.ny * a.pitch : a.pitch;
-        const uint32_t base = (a.axis == 0u ? line * a.pitch : line * a.ny * a.pitch) + z;
+        if (unit >= line_units(a)) return;
+        const auto u = line_unit<uint32_t>(a, unit, lane);                  // (at most 2^31 entries: 32-bit indices)
+        const bool active = u.z < a.nz;
+        const uint32_t stride = u.stride, base = u.base;
         bool below = false;                                                   // the sample below is in E and escapes
         for (uint32_t t0 = 0u; t0 < a.na; t0 += kBatch) {                     // wave-uniform: from layer 0 up
             uint32_t entry[kBatch], root[kBatch];                             // (unrolled: registers)
@@ -308,12 +208,10 @@ __global__ void __launch_bounds__(256) k_drain_floor(const DrainArgs a)
     unsigned long long mine = 0ull;
     if (!ALONG_Z) {
         const uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6);
-        const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
-        if (unit < (uint64_t)lines * a.segments) {
-            const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
-            const bool active = z < a.nz;
-            const uint32_t stride = a.axis == 0u ? a.ny * a.pitch : a.pitch;
-            const uint32_t base = (a.axis == 0u ? line * a.pitch : line * a.ny * a.pitch) + z;
+        if (unit < line_units(a)) {
+            const auto u = line_unit<uint32_t>(a, unit, lane);                  // (at most 2^31 entries: 32-bit indices)
+            const bool active = u.z < a.nz;
+            const uint32_t stride = u.stride, base = u.base;
             uint32_t floor = kEmpty;                                          // the id of the last sample of S below
             for (uint32_t t0 = 0u; t0 < a.na; t0 += kBatch) {                 // wave-uniform: from layer 0 up
                 uint32_t id[kBatch], entry[kBatch], root[kBatch];             // (unrolled: registers)
@@ -374,20 +272,15 @@ int drain_args(void* labels_dev, const uint32_t dims[3], uint32_t pitch, int axi
     a = DrainArgs{};
     if (!labels_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     int rc;
-    if ((rc = lattice_of(dims, pitch, a)) || (rc = lattice_units(axis, a))) return rc;
-    const unsigned __int128 total = (unsigned __int128)dims[0] * dims[1] * pitch;
-    if (total > ((unsigned __int128)1 << 31)) return hu_fail(HU_ERR_BAD_ARG, "a label volume holds at most 2^31 entries");
-    if (reinterpret_cast<uintptr_t>(labels_dev) % 4u) return hu_fail(HU_ERR_BAD_ARG, "the labels must be aligned to 4 bytes");
-    a.labels = static_cast<uint32_t*>(labels_dev);
-    a.total = (uint32_t)total;
+    if ((rc = lattice_of(dims, pitch, a)) || (rc = lattice_axis(axis, a)) ||
+        (rc = labels_of(labels_dev, "the labels must be aligned to 4 bytes", a)))
+        return rc;
     a.axis = (uint32_t)axis, a.up = up != 0;
     return HU_OK;
 }
 
-inline uint32_t blocks_of(uint64_t lanes) { return (uint32_t)((lanes + 255u) / 256u); }
-
-// a wavefront a unit of 64 z of a line along x or y: at most 65536 lines of 1024 words
-inline uint32_t line_blocks(const DrainArgs& a) { return (uint32_t)(((uint64_t)(a.axis == 0u ? a.ny : a.nx) * a.segments + 3u) / 4u); }
+// a wavefront a unit of 64 z of a line along x or y
+inline uint32_t line_blocks(const DrainArgs& a) { return (uint32_t)((line_units(a) + 3u) / 4u); }
 
 }  // namespace
 
@@ -402,17 +295,14 @@ int hu_drain_layers(const void* ids_dev, void* labels_dev, const uint32_t dims[3
     if (reinterpret_cast<uintptr_t>(ids_dev) % 16u) return hu_fail(HU_ERR_BAD_ARG, "the volume must be aligned to 16 bytes");
     a.ids = static_cast<const uint8_t*>(ids_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(pitch / kTileZ, (a.ny + kTileY - 1u) / kTileY, (a.nx + kTileX - 1u) / kTileX);
     if (local) {
-        hipLaunchKernelGGL(k_drain_local<true>, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_drain_local<true>, tile_grid(a), dim3(256), 0, s, a);
         HU_HIP(hipGetLastError());
-        const uint64_t fx = (uint64_t)((a.nx - 1u) / kTileX) * a.ny * a.nz, fy = (uint64_t)a.nx * ((a.ny - 1u) / kTileY) * a.nz,
-                       fz = (uint64_t)a.nx * a.ny * ((a.nz - 1u) / kTileZ);
-        const uint64_t most = axis == 0 ? std::max(fy, fz) : axis == 1 ? std::max(fx, fz) : std::max(fx, fy);
+        const uint64_t most = std::max(face_pairs(a, axis == 0 ? 1u : 0u), face_pairs(a, axis == 2 ? 1u : 2u));
         if (most == 0u) return HU_OK;                              // one tile across both lateral axes: nothing to merge
         hipLaunchKernelGGL(k_drain_merge_faces, dim3(blocks_of(most), 2), dim3(256), 0, s, a);
     } else {
-        hipLaunchKernelGGL(k_drain_local<false>, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_drain_local<false>, tile_grid(a), dim3(256), 0, s, a);
         HU_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_drain_merge_all, dim3(blocks_of(a.total)), dim3(256), 0, s, a);
     }

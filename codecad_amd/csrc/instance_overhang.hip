@@ -124,17 +124,14 @@ __global__ void __launch_bounds__(256) k_over_columns(const OverArgs a)
     if (!ALONG_Z) {
         // a line along x is one y, along y one x; 64 consecutive z of it, one such unit a wavefront
         const uint64_t unit = (uint64_t)blockIdx.x * 4u + uniform(threadIdx.x >> 6);
-        const uint32_t lines = a.axis == 0u ? a.ny : a.nx;
-        if (unit >= (uint64_t)lines * a.segments) return;
-        const uint32_t line = (uint32_t)(unit / a.segments), z = (((uint32_t)(unit - (uint64_t)line * a.segments)) << 6) + lane;
-        const bool active = z < a.nz;
-        const size_t stride = a.axis == 0u ? (size_t)a.ny * a.pitch : (size_t)a.pitch;
-        const size_t base = (a.axis == 0u ? (size_t)line * a.pitch : (size_t)line * a.ny * a.pitch) + z;
+        if (unit >= line_units(a)) return;
+        const LineUnit u = line_unit(a, unit, lane);
+        const bool active = u.z < a.nz;
         uint32_t holder = kEmpty;                                     // the id of the overhang that holds this lane's column up
         bool above_held = false;                                      // the sample above is in P
         for (uint32_t t = 0u; t < a.na; ++t) {                        // wave-uniform: from the top layer down
             const uint32_t h = a.na - 1u - t;
-            const size_t at = base + (size_t)(a.up ? h : t) * stride;
+            const size_t at = u.base + (size_t)(a.up ? h : t) * u.stride;
             const uint32_t id = active ? a.ids[at] : kEmpty;
             const bool over = active && a.over[at] != kEmpty;
             const bool in = active && in_set(id, a.of);
@@ -195,7 +192,7 @@ int over_args(const void* ids_dev, uint32_t* word_dev, const uint32_t dims[3], u
     a = OverArgs{};
     if (!ids_dev || !word_dev || !dims) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     int rc;
-    if ((rc = lattice_of(dims, pitch, a)) || (rc = lattice_units(axis, a))) return rc;
+    if ((rc = lattice_of(dims, pitch, a)) || (rc = lattice_axis(axis, a))) return rc;
     if (reach_sq > kMaxReach) return hu_fail(HU_ERR_BAD_ARG, "reach_sq must be at most 8");
     if ((rc = check_of(of, "HU_OVERHANG_SOLID"))) return rc;
     if (reinterpret_cast<uintptr_t>(word_dev) % 4u) return hu_fail(HU_ERR_BAD_ARG, "the depth word must be aligned to 4 bytes");
@@ -253,9 +250,8 @@ int hu_overhang_columns(const void* ids_dev, const void* overhang_dev, void* sup
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (axis == 2) {
         hipLaunchKernelGGL((k_over_columns<true>), dim3(walking_blocks((uint64_t)a.nx * a.ny, 4u)), dim3(256), 0, s, a);
-    } else {                                                          // a wavefront a unit: at most 65536 lines of 1024 words
-        const uint64_t units = (uint64_t)(axis == 0 ? a.ny : a.nx) * a.segments;
-        hipLaunchKernelGGL((k_over_columns<false>), dim3((uint32_t)((units + 3u) / 4u)), dim3(256), 0, s, a);
+    } else {                                                          // a wavefront a unit
+        hipLaunchKernelGGL((k_over_columns<false>), dim3((uint32_t)((line_units(a) + 3u) / 4u)), dim3(256), 0, s, a);
     }
     HU_HIP(hipGetLastError());
     return HU_OK;

@@ -1,0 +1,168 @@
+// codecad_amd/csrc/label_kernels.hpp -- the ONE body of the kernels that LABEL a subset S of the part-id volume by union-find:
+// instance_components.hip (the connected components of S, CompArgs) and instance_drain.hip (the components of every layer of an
+// axis at once, DrainArgs) wrap it in their kernels.  id_volume.hpp has the volume's contract, find and unite;
+// instance_components.hip states THE INVARIANT (label[q] <= q, entries only ever fall) and what a label is: until a caller's
+// last kernel the index q = (x * ny + y) * pitch + z of a sample of its own component INTO THE LABEL BUFFER, kNone outside S
+// and in the padding.  Args has labels, nx, ny, nz, pitch and total under these names.
+//
+// WHAT THE TWO DIFFER IN: `in`, the predicate on an id that says what S is, and `edges`, a 3-bit mask of the axes whose forward
+// neighbour connects (bit a: the sample one step on along axis a).  The components pass 7, a constant: the guards fold away.
+// The layers of axis a pass 7 & ~(1 << a): the neighbour along the axis lies in another layer.
+//   label_tile<true>: a workgroup of 256 owns a tile of 8 x 8 x 16 samples (z a whole aligned 16-byte run of the volume: the
+//     bytes come in as one 16-byte load per column, 64 lanes).  The tile's part of S is labelled in LDS by the same union-find
+//     (4 KiB of labels, 256 B of column masks), every sample unites with its forward neighbours of `edges` inside the tile, and
+//     writes the buffer index of its tile-local root.  label_tile<false> (the comparison arm) writes label = own index.
+//   label_merge_faces: a lane per pair of samples across a tile face of `axis` (x = 8 k - 1, y = 8 k - 1 or z = 16 k - 1);
+//     label_merge_all (the comparison arm): a lane per sample, its forward neighbours of `edges`.
+// Host side: the checks of a label volume, the grids, and the pairs across the tile faces of an axis.
+#pragma once
+
+#include "id_volume.hpp"
+
+namespace hu_cells {
+
+constexpr uint32_t kNone = 0xffffffffu;     // the label of a sample outside S
+constexpr uint32_t kTileX = HU_COMPONENTS_TILE_X, kTileY = HU_COMPONENTS_TILE_Y, kTileZ = HU_COMPONENTS_TILE_Z;
+constexpr uint32_t kTile = kTileX * kTileY * kTileZ;
+static_assert(kTileX == 8u && kTileY == 8u && kTileZ == 16u && kTile == 1024u, "the index arithmetic of label_tile");
+
+// `volume`: the ids, uint8[nx][ny][pitch].  The grid is tile_grid's.
+template <bool LOCAL, class A, class In>
+__device__ __forceinline__ void label_tile(const A& k, const uint8_t* volume, In in_set_of, uint32_t edges)
+{
+    __shared__ uint32_t lab[kTile];
+    __shared__ uint32_t column[kTileX * kTileY];     // bit dz: sample dz of the column is in S
+    const uint32_t t = threadIdx.x;
+    const uint32_t x0 = blockIdx.z * kTileX, y0 = blockIdx.y * kTileY, z0 = blockIdx.x * kTileZ;   // z0 < pitch
+    if (t < kTileX * kTileY) {
+        const uint32_t x = x0 + (t >> 3), y = y0 + (t & 7u);
+        uint32_t mask = 0u;
+        if (x < k.nx && y < k.ny) {
+            // z0 and the pitch are multiples of 16 and the volume is aligned: one aligned 16-byte load inside the row
+            const uint4 v = *reinterpret_cast<const uint4*>(volume + ((size_t)x * k.ny + y) * k.pitch + z0);
+#pragma unroll
+            for (uint32_t dz = 0; dz < 16u; ++dz) {
+                const uint32_t word = dz < 4u ? v.x : dz < 8u ? v.y : dz < 12u ? v.z : v.w;
+                const bool in = z0 + dz < k.nz && in_set_of((word >> (8u * (dz & 3u))) & 0xffu);   // (the padding is not in S)
+                mask |= in ? 1u << dz : 0u;
+            }
+        }
+        column[t] = mask;
+    }
+    __syncthreads();
+    // tile-local index i = (dx * 8 + dy) * 16 + dz: ordered like the buffer index, so the least i is the least q.
+    // THE INVARIANT is established here, in LDS: lab[i] = i.
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t i = t + 256u * j;
+        lab[i] = ((column[i >> 4] >> (i & 15u)) & 1u) ? i : kNone;
+    }
+    __syncthreads();
+    if (LOCAL) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t i = t + 256u * j, c = i >> 4, dz = i & 15u;
+            const uint32_t mine = column[c];
+            if (!((mine >> dz) & 1u)) continue;
+            if ((edges & 4u) && dz < 15u && ((mine >> (dz + 1u)) & 1u)) unite(lab, i, i + 1u);
+            if ((edges & 2u) && (c & 7u) < 7u && ((column[c + 1u] >> dz) & 1u)) unite(lab, i, i + 16u);
+            if ((edges & 1u) && c < 56u && ((column[c + 8u] >> dz) & 1u)) unite(lab, i, i + 128u);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t i = t + 256u * j;
+        const uint32_t x = x0 + (i >> 7), y = y0 + ((i >> 4) & 7u), z = z0 + (i & 15u);
+        if (x >= k.nx || y >= k.ny) continue;                   // (z < pitch: the tiles along z cover the pitch exactly)
+        uint32_t out = kNone;
+        if (lab[i] != kNone) {
+            const uint32_t r = LOCAL ? find(lab, i) : i;         // r <= i, so the root's buffer index is <= this sample's
+            out = ((x0 + (r >> 7)) * k.ny + (y0 + ((r >> 4) & 7u))) * k.pitch + z0 + (r & 15u);
+        }
+        k.labels[((size_t)x * k.ny + y) * k.pitch + z] = out;   // THE INVARIANT in global memory: label[q] <= q
+    }
+}
+
+// lane blockIdx.x * 256 + threadIdx.x takes a pair of face_pairs(k, axis).  Faces between tiles: fx = (nx - 1) / 8 planes
+// x = 8 (f + 1) - 1 (whose x + 1 exists), and so on.
+template <class A> __device__ __forceinline__ void label_merge_faces(const A& k, uint32_t axis)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t faces = axis == 0u ? (k.nx - 1u) / kTileX : axis == 1u ? (k.ny - 1u) / kTileY : (k.nz - 1u) / kTileZ;
+    uint32_t x, y, z, stride;
+    if (axis == 0u) {
+        const uint64_t plane = (uint64_t)k.ny * k.nz;
+        if (i >= faces * plane) return;
+        const uint32_t f = (uint32_t)(i / plane), rest = (uint32_t)(i - f * plane);
+        x = kTileX * (f + 1u) - 1u, y = rest / k.nz, z = rest - y * k.nz;
+        stride = k.ny * k.pitch;
+    } else if (axis == 1u) {
+        const uint64_t slab = (uint64_t)faces * k.nz;
+        if (i >= k.nx * slab) return;
+        x = (uint32_t)(i / slab);
+        const uint32_t rest = (uint32_t)(i - x * slab), f = rest / k.nz;
+        y = kTileY * (f + 1u) - 1u, z = rest - f * k.nz;
+        stride = k.pitch;
+    } else {
+        const uint64_t slab = (uint64_t)k.ny * faces;
+        if (i >= k.nx * slab) return;
+        x = (uint32_t)(i / slab);
+        const uint32_t rest = (uint32_t)(i - x * slab);
+        y = rest / faces;
+        z = kTileZ * (rest - y * faces + 1u) - 1u;
+        stride = 1u;
+    }
+    const uint32_t q = (x * k.ny + y) * k.pitch + z;             // q + stride is the sample one step on: it exists
+    const uint32_t a = k.labels[q], b = k.labels[q + stride];
+    if (a != kNone && b != kNone) unite(k.labels, a, b);          // (a label is an ancestor: a start as good as q)
+}
+
+// lane blockIdx.x * 256 + threadIdx.x takes a sample of the `total`
+template <class A> __device__ __forceinline__ void label_merge_all(const A& k, uint32_t edges)
+{
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= k.total) return;
+    const uint32_t row = q / k.pitch, z = q - row * k.pitch, x = row / k.ny, y = row - x * k.ny;
+    if (z >= k.nz) return;
+    const uint32_t a = k.labels[q];
+    if (a == kNone) return;
+    if ((edges & 4u) && z + 1u < k.nz) {
+        const uint32_t b = k.labels[q + 1u];
+        if (b != kNone) unite(k.labels, a, b);
+    }
+    if ((edges & 2u) && y + 1u < k.ny) {
+        const uint32_t b = k.labels[q + k.pitch];
+        if (b != kNone) unite(k.labels, a, b);
+    }
+    if ((edges & 1u) && x + 1u < k.nx) {
+        const uint32_t b = k.labels[q + k.ny * k.pitch];
+        if (b != kNone) unite(k.labels, a, b);
+    }
+}
+
+// host side, after lattice_of: the checks of the label volume and the fill of labels and total.  `misaligned`: the caller's
+// words for labels that are not aligned to 4 bytes
+template <class A> int labels_of(void* labels_dev, const char* misaligned, A& k)
+{
+    const unsigned __int128 total = (unsigned __int128)k.nx * k.ny * k.pitch;
+    if (total > ((unsigned __int128)1 << 31)) return hu_fail(HU_ERR_BAD_ARG, "a label volume holds at most 2^31 entries");
+    if (reinterpret_cast<uintptr_t>(labels_dev) % 4u) return hu_fail(HU_ERR_BAD_ARG, misaligned);
+    k.labels = static_cast<uint32_t*>(labels_dev);
+    k.total = (uint32_t)total;
+    return HU_OK;
+}
+
+inline uint32_t blocks_of(uint64_t lanes) { return (uint32_t)((lanes + 255u) / 256u); }
+
+template <class A> dim3 tile_grid(const A& k) { return dim3(k.pitch / kTileZ, (k.ny + kTileY - 1u) / kTileY, (k.nx + kTileX - 1u) / kTileX); }
+
+// the pairs of samples across the tile faces of `axis`: 0 where one tile spans the lattice along it
+template <class A> uint64_t face_pairs(const A& k, uint32_t axis)
+{
+    return axis == 0u   ? (uint64_t)((k.nx - 1u) / kTileX) * k.ny * k.nz
+           : axis == 1u ? (uint64_t)k.nx * ((k.ny - 1u) / kTileY) * k.nz
+                        : (uint64_t)k.nx * k.ny * ((k.nz - 1u) / kTileZ);
+}
+
+}  // namespace hu_cells

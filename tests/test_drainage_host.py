@@ -415,13 +415,29 @@ def test_the_kernels_use_no_scratch_and_the_resources_the_design_states(tmp_path
     assert "instance_drain.hip" in builder.SOURCES and "instance_drain.hip" not in builder.FLAGGED_SOURCES
     with open(os.path.join(builder.CSRC, "instance_drain.hip")) as f:
         source = f.read()
-    assert '#include "id_volume.hpp"' in source
+    assert '#include "id_volume.hpp"' in source and '#include "label_kernels.hpp"' in source
     with open(os.path.join(builder.CSRC, "id_volume.hpp")) as f:
         shared = f.read()
+    with open(os.path.join(builder.CSRC, "label_kernels.hpp")) as f:
+        labelling = f.read()
+    assert '#include "id_volume.hpp"' in labelling
     with open(os.path.join(builder.CSRC, "instance_components.hip")) as f:
         components = f.read()
-    for function in ("uint32_t find(", "void unite("):                              # one copy of them
-        assert shared.count(function) == 1 and function not in source and function not in components
+    assert '#include "label_kernels.hpp"' in components
+    everything = {name: open(os.path.join(builder.CSRC, name)).read() for name in sorted(os.listdir(builder.CSRC))
+                  if name.endswith((".hip", ".hpp", ".h"))}
+    # one copy of each: find, unite and the line walk in id_volume.hpp; the tile labelling, the merges, the tile's index
+    # arithmetic and the grid of a lane per sample in label_kernels.hpp; nothing of them in either unit
+    for home, text, functions in (("id_volume.hpp", shared, ("uint32_t find(", "void unite(", "LineUnitOf<I> line_unit(", "uint64_t line_units(")),
+                                  ("label_kernels.hpp", labelling, ("void label_tile(", "void label_merge_faces(", "void label_merge_all(",
+                                                                    "uint32_t blocks_of(", "uint64_t face_pairs(", "int labels_of(",
+                                                                    "constexpr uint32_t kNone = 0xffffffffu", "constexpr uint32_t kTileX",
+                                                                    "__shared__ uint32_t lab[kTile]"))):
+        for function in functions:
+            assert text.count(function) == 1, function
+            assert [name for name, other in everything.items() if function in other] == [home], function
+    for text in (source, components):                                              # no tile arithmetic, no face ranges
+        assert "kTileX" not in text and "kTileZ" not in text and "line * a.segments" not in text and "2^31 entries\"" not in text
     documented = documented_resources()
     hipcc = builder.find_hipcc()
     if hipcc is None:

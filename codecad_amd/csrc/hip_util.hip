@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -705,10 +706,10 @@ int launch_classify(hu_tape t, ClassifyArgs& a, uint32_t n_parents, const uint32
     if (dims[0] > 256 || dims[1] > 256 || dims[2] > 256)
         return hu_fail(HU_ERR_BAD_ARG, "grid size > 256 would overflow the uchar4 cell index (reference subdivision.py:206-208)");
     if (n_parents == 0) return HU_OK;
+    a.sx = dims[0]; a.sy = dims[1]; a.sz = dims[2];
+    a.dy = make_dim(dims[1]); a.dz = make_dim(dims[2]);
     if (t->spec && t->spec->classify[MASS ? 1 : 0][BATCH ? 1 : 0]) {
         const uint32_t per_block = kSpecBlock * kSpecVoxelsPerLane;
-        a.sx = dims[0]; a.sy = dims[1]; a.sz = dims[2];
-        a.dy = make_dim(dims[1]); a.dz = make_dim(dims[2]);
         a.chunks = (uint32_t)((cells + per_block - 1) / per_block);
         a.scratch_offset = 0;
         a.boxes = 0;
@@ -759,11 +760,6 @@ int launch_classify(hu_tape t, ClassifyArgs& a, uint32_t n_parents, const uint32
     LaunchShape ls;
     if ((rc = launch_shape(t, ls, distance_only(t)))) return rc;
     if ((rc = hu_ensure_attrs())) return rc;
-    a.sx = dims[0];
-    a.sy = dims[1];
-    a.sz = dims[2];
-    a.dy = make_dim(dims[1]);
-    a.dz = make_dim(dims[2]);
     const uint32_t per_block = ls.block * ls.voxels_per_lane;
     a.chunks = (uint32_t)((cells + per_block - 1) / per_block);
     a.scratch_offset = (uint32_t)ls.regfile_bytes;
@@ -791,17 +787,49 @@ int launch_classify(hu_tape t, ClassifyArgs& a, uint32_t n_parents, const uint32
     return HU_OK;
 }
 
-// what the six entry points of a level fill alike
-ClassifyArgs level_args(const void* parents_dev, const uint32_t* n_parents_dev, float step, float threshold, uint32_t* counter_dev,
-                        void* children_dev, uint32_t capacity)
+ClassifyArgs zeroed_args()
 {
     ClassifyArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.parents = parents_dev;
-    a.n_parents_dev = n_parents_dev;
-    a.step = step; a.thr = threshold;
-    a.counter = counter_dev; a.list = children_dev; a.capacity = capacity;
     return a;
+}
+
+// what the two single-block entry points fill alike (the caller has checked the pointers)
+ClassifyArgs block_args(const float corner[4], float step, float threshold, uint32_t* counter_dev, void* list_dev)
+{
+    ClassifyArgs a = zeroed_args();
+    a.cx = corner[0]; a.cy = corner[1]; a.cz = corner[2];
+    a.step = step; a.thr = threshold;
+    a.counter = counter_dev; a.list = list_dev; a.capacity = 0xffffffffu;
+    return a;
+}
+
+// the launch record of a level (hip_util.h): hip_util/_lib.py mirrors it field by field
+static_assert(sizeof(hu_level_launch) == HU_LEVEL_LAUNCH_BYTES, "hu_level_launch must have the size hip_util.h states");
+static_assert(offsetof(hu_level_launch, max_parents) == 48 && offsetof(hu_level_launch, dims) == 64 && offsetof(hu_level_launch, thr) == 80,
+              "hu_level_launch: six pointers, then 32-bit fields without padding between them");
+
+// A level's record, checked for NULLs, as the kernels' arguments; `own` is the entry point's own pointer (the origin, the
+// sums), refused with the record's.  world = 1 leaves `own` zero: every cell is kept (kernels.hpp owned()).
+int level_args(const hu_level_launch* l, const void* own, ClassifyArgs& a)
+{
+    if (!l || !l->tape || !own || !l->counter_dev || (!l->children_dev && l->capacity) || (!l->parents_dev && l->max_parents))
+        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    a = zeroed_args();
+    a.parents = l->parents_dev;
+    a.n_parents_dev = l->n_parents_dev;
+    a.step = l->step; a.thr = l->thr;
+    a.counter = l->counter_dev; a.list = l->children_dev; a.capacity = l->capacity;
+    if (l->world >= 2u) { a.own = make_dim(l->world); a.own_rank = l->rank; }
+    return HU_OK;
+}
+
+// ... and its launch, after the entry point's own checks: n_parents_dev == NULL means exactly max_parents parents
+template <bool MASS>
+int launch_level(const hu_level_launch* l, ClassifyArgs& a)
+{
+    if (l->world == 0 || l->rank >= l->world) return hu_fail(HU_ERR_BAD_ARG, "rank must be below world");
+    return launch_classify<MASS, true>(l->tape, a, l->max_parents, l->dims, l->stream);
 }
 
 }  // namespace
@@ -812,11 +840,7 @@ int hu_subdivision_step(hu_tape t, const float corner[4], float step, float thre
                         uint32_t* counter_dev, void* list_dev, void* stream)
 {
     if (!t || !corner || !counter_dev || !list_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    ClassifyArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cx = corner[0]; a.cy = corner[1]; a.cz = corner[2];
-    a.step = step; a.thr = threshold;
-    a.counter = counter_dev; a.list = list_dev; a.capacity = 0xffffffffu;
+    ClassifyArgs a = block_args(corner, step, threshold, counter_dev, list_dev);
     return launch_classify<false, false>(t, a, 1, dims, stream);
 }
 
@@ -824,97 +848,30 @@ int hu_mass_properties(hu_tape t, const float corner[4], float step, float thres
                        uint32_t* sum_dev, uint32_t* counter_dev, void* list_dev, void* stream)
 {
     if (!t || !corner || !sum_dev || !counter_dev || !list_dev) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    ClassifyArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cx = corner[0]; a.cy = corner[1]; a.cz = corner[2];
-    a.step = step; a.thr = threshold;
-    a.counter = counter_dev; a.list = list_dev; a.capacity = 0xffffffffu;
+    ClassifyArgs a = block_args(corner, step, threshold, counter_dev, list_dev);
     a.sums = sum_dev;
     return launch_classify<true, false>(t, a, 1, dims, stream);
 }
 
-int hu_subdivision_level(hu_tape t, const int32_t* parents_dev, uint32_t n_parents, int32_t int_step,
-                         const uint32_t dims[3], int dimension, double resolution, const double origin[3],
-                         float step, float threshold, uint32_t* counter_dev, int32_t* children_dev,
-                         uint32_t capacity, void* stream)
+int hu_subdivision_level(const hu_level_launch* launch, int32_t int_step, int dimension, double resolution, const double origin[3])
 {
-    if (!t || !origin || !counter_dev || (!children_dev && capacity) || (!parents_dev && n_parents))
-        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    ClassifyArgs a;
+    int rc;
+    if ((rc = level_args(launch, origin, a))) return rc;
     if (dimension != 2 && dimension != 3) return hu_fail(HU_ERR_BAD_ARG, "dimension must be 2 or 3");
-    ClassifyArgs a = level_args(parents_dev, nullptr, step, threshold, counter_dev, children_dev, capacity);
     a.int_step = int_step; a.dimension = dimension;
     a.res = resolution; a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-    return launch_classify<false, true>(t, a, n_parents, dims, stream);
+    return launch_level<false>(launch, a);
 }
 
-int hu_subdivision_level_indirect(hu_tape t, const int32_t* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                  int32_t int_step, const uint32_t dims[3], int dimension, double resolution,
-                                  const double origin[3], float step, float threshold, uint32_t* counter_dev,
-                                  int32_t* children_dev, uint32_t capacity, void* stream)
+int hu_mass_properties_level(const hu_level_launch* launch, double s, uint32_t* sums_dev)
 {
-    if (!t || !origin || !counter_dev || !n_parents_dev || (!children_dev && capacity) || (!parents_dev && max_parents))
-        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (dimension != 2 && dimension != 3) return hu_fail(HU_ERR_BAD_ARG, "dimension must be 2 or 3");
-    ClassifyArgs a = level_args(parents_dev, n_parents_dev, step, threshold, counter_dev, children_dev, capacity);
-    a.int_step = int_step; a.dimension = dimension;
-    a.res = resolution; a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-    return launch_classify<false, true>(t, a, max_parents, dims, stream);
-}
-
-// ... and with OWNERSHIP (kernels.hpp ClassifyArgs::own): the launch of a level that `world` ranks classify in full, each keeping
-// the cells it owns
-int hu_subdivision_level_owned(hu_tape t, const int32_t* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                               int32_t int_step, const uint32_t dims[3], int dimension, double resolution,
-                               const double origin[3], float step, float threshold, uint32_t* counter_dev,
-                               int32_t* children_dev, uint32_t capacity, uint32_t world, uint32_t rank, void* stream)
-{
-    if (!t || !origin || !counter_dev || !n_parents_dev || (!children_dev && capacity) || (!parents_dev && max_parents))
-        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (dimension != 2 && dimension != 3) return hu_fail(HU_ERR_BAD_ARG, "dimension must be 2 or 3");
-    if (world == 0 || rank >= world) return hu_fail(HU_ERR_BAD_ARG, "rank must be below world");
-    ClassifyArgs a = level_args(parents_dev, n_parents_dev, step, threshold, counter_dev, children_dev, capacity);
-    a.int_step = int_step; a.dimension = dimension;
-    a.res = resolution; a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-    a.own = make_dim(world); a.own_rank = rank;
-    return launch_classify<false, true>(t, a, max_parents, dims, stream);
-}
-
-int hu_mass_properties_level_owned(hu_tape t, const double* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, double s,
-                                   const uint32_t dims[3], float step, float threshold, uint32_t* sums_dev,
-                                   uint32_t* counter_dev, double* children_dev, uint32_t capacity, uint32_t world, uint32_t rank, void* stream)
-{
-    if (!t || !sums_dev || !counter_dev || !n_parents_dev || (!children_dev && capacity) || (!parents_dev && max_parents))
-        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    if (world == 0 || rank >= world) return hu_fail(HU_ERR_BAD_ARG, "rank must be below world");
-    ClassifyArgs a = level_args(parents_dev, n_parents_dev, step, threshold, counter_dev, children_dev, capacity);
+    ClassifyArgs a;
+    int rc;
+    if ((rc = level_args(launch, sums_dev, a))) return rc;
     a.s = s;
     a.sums = sums_dev;
-    a.own = make_dim(world); a.own_rank = rank;
-    return launch_classify<true, true>(t, a, max_parents, dims, stream);
-}
-
-int hu_mass_properties_level(hu_tape t, const double* parents_dev, uint32_t n_parents, double s,
-                             const uint32_t dims[3], float step, float threshold, uint32_t* sums_dev,
-                             uint32_t* counter_dev, double* children_dev, uint32_t capacity, void* stream)
-{
-    if (!t || !sums_dev || !counter_dev || (!children_dev && capacity) || (!parents_dev && n_parents))
-        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    ClassifyArgs a = level_args(parents_dev, nullptr, step, threshold, counter_dev, children_dev, capacity);
-    a.s = s;
-    a.sums = sums_dev;
-    return launch_classify<true, true>(t, a, n_parents, dims, stream);
-}
-
-int hu_mass_properties_level_indirect(hu_tape t, const double* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents, double s,
-                                      const uint32_t dims[3], float step, float threshold, uint32_t* sums_dev,
-                                      uint32_t* counter_dev, double* children_dev, uint32_t capacity, void* stream)
-{
-    if (!t || !sums_dev || !counter_dev || !n_parents_dev || (!children_dev && capacity) || (!parents_dev && max_parents))
-        return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    ClassifyArgs a = level_args(parents_dev, n_parents_dev, step, threshold, counter_dev, children_dev, capacity);
-    a.s = s;
-    a.sums = sums_dev;
-    return launch_classify<true, true>(t, a, max_parents, dims, stream);
+    return launch_level<true>(launch, a);
 }
 
 int hu_instance_table(const hu_tape* tapes, uint32_t n, int full_programs, void* table_host, size_t bytes, int* distance_only_out,

@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(1024)
 k_mass_integrals(const double4* __restrict__ parents, const uint32_t* __restrict__ sums, uint32_t n, uint32_t per_row,
                  const uint32_t* __restrict__ n_dev, double s, double* __restrict__ out)
 {
-    // indirect form (hu_mass_integrals_indirect): the number of parents lives on the device (at most `n`, the list's
+    // n_dev != NULL (hu_mass_integrals' n_parents_dev): the number of parents lives on the device (at most `n`, the list's
     // capacity, are there); the slices are cut from it, so the rows mean the same as in the direct form
     if (n_dev) {
         const uint32_t have = *n_dev;
@@ -273,17 +273,10 @@ int hu_process_polygon_blocks(const void* corners_dev, const int32_t* blocks_dev
     return launch_process_polygon(true, a, n_blocks, stream);
 }
 
-int hu_mass_integrals(const double* parents_dev, const uint32_t* sums_dev, uint32_t n_parents, double s,
-                      double* out_dev, uint32_t rows, void* stream)
+int hu_mass_integrals(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
+                      double s, double* out_dev, uint32_t rows, void* stream)
 {
-    if (!out_dev || ((!parents_dev || !sums_dev) && n_parents)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
-    return launch_mass_integrals(parents_dev, sums_dev, n_parents, nullptr, s, out_dev, rows, stream);
-}
-
-int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                               double s, double* out_dev, uint32_t rows, void* stream)
-{
-    if (!out_dev || !n_parents_dev || ((!parents_dev || !sums_dev) && max_parents)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
+    if (!out_dev || ((!parents_dev || !sums_dev) && max_parents)) return hu_fail(HU_ERR_BAD_ARG, "NULL argument");
     return launch_mass_integrals(parents_dev, sums_dev, max_parents, n_parents_dev, s, out_dev, rows, stream);
 }
 

@@ -199,7 +199,7 @@ def run_levels(top_parents, n_levels, classify_level, hints=None):
 # REPLICATED LEVELS.  The first levels of a hierarchy are tiny (the bench's: 27 cells, then 27 parents of 4096 cells): cutting
 # their parent lists into slices, all-gathering the survivors and slicing again costs far more than the work.  Every rank
 # classifies such a level IN FULL instead -- no exchange --, and in the last replicated level keeps only the cells it OWNS
-# (hu_*_level_owned: owner = mix(hash of the parent's row, the cell's linear index) mod world): the ranks' lists then partition
+# (the level's launch with world >= 2: owner = mix(hash of the parent's row, the cell's linear index) mod world): the ranks' lists then partition
 # that level's survivors evenly -- a cell's owner is as good as random -- whatever order each rank's atomics left its own
 # lists in.  A level is replicated while (parents' capacity x cells) stays below this many samples.
 REPLICATE_MAX_SAMPLES = int(os.environ.get("CODECAD_AMD_REPLICATE_SAMPLES", 4 << 20))
@@ -279,8 +279,8 @@ class LevelPipeline:
     the gathered lists -- is what a step consists of (a 512^3 level is ~10 us of kernel per rank).  Here every
     list is a fixed-capacity device buffer [header row | rows...] whose header holds its length:
 
-      classify(level)  counts into the header of `send[level]`, appends to its rows   (hu_subdivision_level_indirect,
-                                                                                        hu_mass_properties_level_indirect)
+      classify(level)  counts into the header of `send[level]`, appends to its rows   (hu_subdivision_level,
+                                                                                        hu_mass_properties_level)
       all-gather       of the whole fixed-size piece, one collective, no sizes on the host     (when `exchanging()`)
       slice            the rank's balanced share of the concatenation -> `mine[level]`, again
                        [header | rows], on the device                                             (hu_slice_rows)
@@ -301,7 +301,7 @@ class LevelPipeline:
         """replicate = k: the first k levels are REPLICATED (see REPLICATE_MAX_SAMPLES): every rank classifies all of their
         parents itself, without an exchange; in the last of them the classification is called with own=(world, rank) and
         lists only the cells this rank owns, so that from there on every rank holds a share.  `classify` must then take
-        that keyword (the HIP ones do: hu_*_level_owned).  Levels after the replicated ones are exchanged as described above
+        that keyword (the HIP ones do: the launch record's world and rank).  Levels after the replicated ones are exchanged as described above
         -- there the all-gather re-balances the shares."""
         assert top_rows.dtype == torch.int32, "rows are int32 words (view 32-byte double rows as (n, 8) int32)"
         self.rank, self.world = rank_world()
@@ -462,30 +462,28 @@ def subdivision_pipeline(tape, levels, resolution, origin, dimension, capacities
     collectives follow that: LevelPipeline.enqueue asserts it)."""
     import ctypes
     import math
-    import numpy
     from .hip_util import manager as hip_manager, check
+    from .hip_util._lib import LevelLaunch
 
     lib = hip_manager.lib
     o = (ctypes.c_double * 3)(*[float(v) for v in origin])
 
     def bind(level, parents, n_parents, max_parents, out, own=None):
-        """-> the launch without arguments (LevelPipeline._make_plan): pointers, sizes and converted scalars worked out once;
-        own = (world, rank): a replicated level of which this rank lists the cells it owns (hu_subdivision_level_owned)"""
+        """-> the launch without arguments (LevelPipeline._make_plan): the record and the converted scalars worked out once;
+        own = (world, rank): a replicated level of which this rank lists the cells it owns"""
         int_step, dims = levels[level]
-        d = (ctypes.c_uint32 * 3)(int(dims[0]), int(dims[1]), int(dims[2]))
         box_step = int_step * resolution
-        thr = box_step * math.sqrt(dimension) / 2
-        args = (tape.device_ptr, parents.data_ptr(), n_parents.data_ptr(), int(max_parents), int(int_step), d, dimension,
-                float(resolution), o, numpy.float32(box_step), numpy.float32(thr), out.data_ptr(), out[1:].data_ptr(),
-                int(out.shape[0]) - 1)
-        keep = (parents, n_parents, out, d)
-        if own is None:
-            fn, name, args = lib.hu_subdivision_level_indirect, "hu_subdivision_level_indirect", args + (stream,)
-        else:
-            fn, name, args = lib.hu_subdivision_level_owned, "hu_subdivision_level_owned", args + (int(own[0]), int(own[1]), stream)
+        world, rank = own or (1, 0)
+        launch = LevelLaunch(tape=tape.device_ptr, parents_dev=parents.data_ptr(), n_parents_dev=n_parents.data_ptr(),
+                             counter_dev=out.data_ptr(), children_dev=out[1:].data_ptr(), stream=stream, max_parents=int(max_parents),
+                             capacity=int(out.shape[0]) - 1, world=int(world), rank=int(rank),
+                             dims=(int(dims[0]), int(dims[1]), int(dims[2])), step=box_step, thr=box_step * math.sqrt(dimension) / 2)
+        args = (ctypes.byref(launch), int(int_step), dimension, float(resolution), o)
+        keep = (parents, n_parents, out, launch)
+        fn = lib.hu_subdivision_level
 
         def run():
-            check(fn(*args), name)
+            check(fn(*args), "hu_subdivision_level")
             return keep
         return run
 
@@ -503,17 +501,16 @@ def subdivision_pipeline(tape, levels, resolution, origin, dimension, capacities
 
 class MassPipeline:
     """mass_properties over the ranks without a host round trip inside the traversal: a LevelPipeline whose rows are
-    the 32-byte `double[4]` rows of hu_mass_properties_level_indirect (seen as eight int32 words), every level also
-    reducing its inside cells' ten integrals on the device (hu_mass_integrals_indirect) into its own small buffer.
+    the 32-byte `double[4]` rows of hu_mass_properties_level (seen as eight int32 words), every level also
+    reducing its inside cells' ten integrals on the device (hu_mass_integrals) into its own small buffer.
     `enqueue()` puts the whole integration on the stream; `finish()` waits once, validates the lists (Overflow ->
     rebuild with larger ones, every rank alike) and returns this rank's ten partial integrals, a (10,) float64 tensor
     on the device, for ONE all-reduce: the sum of the levels that `LevelPipeline.sums_level` gives this rank.  `levels` = [(cell size, dims)], the last one being the leaf level."""
 
     def __init__(self, tape, levels, box_a, capacities, device, stream):
-        import ctypes
         import math
-        import numpy
         from .hip_util import manager as hip_manager, check
+        from .hip_util._lib import LevelLaunch
         from .mass_properties import integral_rows
 
         lib = hip_manager.lib
@@ -534,27 +531,22 @@ class MassPipeline:
             s, dims = levels[level]
             leaf = level + 1 == len(levels)
             thr = 0.0 if leaf else s * math.sqrt(3) / 2
-            d = (ctypes.c_uint32 * 3)(int(dims[0]), int(dims[1]), int(dims[2]))
+            world, rank = own or (1, 0)     # own: a replicated level, this rank's sums and list hold the cells it owns
             sums, pieces = self.sums[level], self.pieces[level]
             assert int(sums.shape[0]) >= int(max_parents)
+            launch = LevelLaunch(tape=tape.device_ptr, parents_dev=parents.data_ptr(), n_parents_dev=n_parents.data_ptr(),
+                                 counter_dev=out.data_ptr(), children_dev=out[1:].data_ptr(), stream=stream, max_parents=int(max_parents),
+                                 capacity=int(out.shape[0]) - 1, world=int(world), rank=int(rank),
+                                 dims=(int(dims[0]), int(dims[1]), int(dims[2])), step=s, thr=thr)
             sums.zero_()
             events = (self.timing or {}).get(level)       # bench.py: HIP events around one level's classification launch
             if events:
                 check(lib.hu_event_record(events[0], stream), "hu_event_record")
-            if own is None:
-                check(lib.hu_mass_properties_level_indirect(tape.device_ptr, parents.data_ptr(), n_parents.data_ptr(), int(max_parents),
-                                                            float(s), d, numpy.float32(s), numpy.float32(thr), sums.data_ptr(),
-                                                            out.data_ptr(), out[1:].data_ptr(), int(out.shape[0]) - 1, stream),
-                      "hu_mass_properties_level_indirect")
-            else:   # a replicated level: this rank's sums and list hold the cells it owns
-                check(lib.hu_mass_properties_level_owned(tape.device_ptr, parents.data_ptr(), n_parents.data_ptr(), int(max_parents),
-                                                         float(s), d, numpy.float32(s), numpy.float32(thr), sums.data_ptr(),
-                                                         out.data_ptr(), out[1:].data_ptr(), int(out.shape[0]) - 1, int(own[0]), int(own[1]), stream),
-                      "hu_mass_properties_level_owned")
+            check(lib.hu_mass_properties_level(launch, float(s), sums.data_ptr()), "hu_mass_properties_level")
             if events:
                 check(lib.hu_event_record(events[1], stream), "hu_event_record")
-            check(lib.hu_mass_integrals_indirect(parents.data_ptr(), sums.data_ptr(), n_parents.data_ptr(), int(max_parents), float(s),
-                                                 pieces.data_ptr(), int(pieces.shape[0]), stream), "hu_mass_integrals_indirect")
+            check(lib.hu_mass_integrals(parents.data_ptr(), sums.data_ptr(), n_parents.data_ptr(), int(max_parents), float(s),
+                                        pieces.data_ptr(), int(pieces.shape[0]), stream), "hu_mass_integrals")
 
         self.pipe = LevelPipeline(top.view(torch.int32).reshape(1, 8), capacities, classify, _hip_slice_rows(lib, check, stream),
                                   device, stream, replicate=self.replicated(levels, capacities[:-1]))
@@ -642,7 +634,7 @@ def mass_hierarchy(box, resolution, grid_size):
 
 def mass_properties(shape, resolution, grid_size=None):
     """`codecad_amd.mass_properties` sharded over the ranks of the process group (one GPU each): every level's parent
-    list is cut into balanced slices, `hu_mass_properties_level_indirect` + `hu_mass_integrals_indirect` run on the
+    list is cut into balanced slices, `hu_mass_properties_level` + `hu_mass_integrals` run on the
     slice, the ambiguous cells go through ONE fixed-size all-gather per level and `hu_slice_rows`, the ten integrals are
     all-reduced once -- the whole integration enqueued without a host round trip (MassPipeline).  Every level's integrals
     count once over the ranks (LevelPipeline.sums_level: a replicated level before the last one on rank 0 only, every other
@@ -668,7 +660,7 @@ def mass_properties(shape, resolution, grid_size=None):
 
 def subdivision(shape, resolution, overlap_edge_samples=True, grid_size=None):
     """`codecad_amd.subdivision.subdivision_device` sharded over the ranks of the process group: every
-    level's parent list is cut into balanced slices, `hu_subdivision_level_indirect` classifies and compacts the
+    level's parent list is cut into balanced slices, `hu_subdivision_level` classifies and compacts the
     slice, the survivors go through one fixed-size all-gather and `hu_slice_rows` (LevelPipeline).  Returns (leaves, info): `leaves` an (n, 4) int32 device tensor of
     integer leaf corners, identical (as a set; ordered by rank slice) on every rank, and `info` with
     `dims`, `int_step`, `step`, `resolution`, `origin`, `level_counts` like LeafBlocks, plus `share`: this rank's

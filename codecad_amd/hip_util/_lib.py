@@ -25,7 +25,14 @@ class CellsChildren(_c.Structure):
     _fields_ = [("counter_dev", _vp), ("children_dev", _vp), ("capacity", _u32), ("child_side", _u32), ("thr", _f)]
 
 
-_L, _C = _c.POINTER(CellsLaunch), _c.POINTER(CellsChildren)
+class LevelLaunch(_c.Structure):
+    """hu_level_launch: what every level launch of a tape takes (n_parents_dev None: exactly max_parents parents; world 1, rank 0:
+    every cell is kept)."""
+    _fields_ = [("tape", _vp), ("parents_dev", _vp), ("n_parents_dev", _vp), ("counter_dev", _vp), ("children_dev", _vp), ("stream", _vp),
+                ("max_parents", _u32), ("capacity", _u32), ("world", _u32), ("rank", _u32), ("dims", _u32 * 3), ("step", _f), ("thr", _f)]
+
+
+_L, _C, _V = _c.POINTER(CellsLaunch), _c.POINTER(CellsChildren), _c.POINTER(LevelLaunch)
 
 # name -> argtypes; every function returns int except hu_last_error
 PROTOTYPES = {
@@ -61,17 +68,12 @@ PROTOTYPES = {
     "hu_mass_properties": [_vp, _f4, _f, _f, _u3, _vp, _vp, _vp, _vp],
     "hu_grid_eval_slab": [_vp, _f4, _f, _u3, _u32, _u32, _i, _vp, _vp],
     "hu_grid_eval_blocks": [_vp, _vp, _u32, _d, _d3, _f, _u3, _i, _vp, _vp],
-    "hu_subdivision_level": [_vp, _vp, _u32, _c.c_int32, _u3, _i, _d, _d3, _f, _f, _vp, _vp, _u32, _vp],
-    "hu_subdivision_level_indirect": [_vp, _vp, _vp, _u32, _c.c_int32, _u3, _i, _d, _d3, _f, _f, _vp, _vp, _u32, _vp],
-    "hu_subdivision_level_owned": [_vp, _vp, _vp, _u32, _c.c_int32, _u3, _i, _d, _d3, _f, _f, _vp, _vp, _u32, _u32, _u32, _vp],
+    "hu_subdivision_level": [_V, _c.c_int32, _i, _d, _d3],
     "hu_grid_eval_blocks_indirect": [_vp, _vp, _vp, _u32, _d, _d3, _f, _u3, _i, _vp, _vp],
     "hu_slice_rows": [_vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp],
     "hu_slice_rows_of": [_vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp],
-    "hu_mass_properties_level": [_vp, _vp, _u32, _d, _u3, _f, _f, _vp, _vp, _vp, _u32, _vp],
-    "hu_mass_integrals": [_vp, _vp, _u32, _d, _vp, _u32, _vp],
-    "hu_mass_properties_level_indirect": [_vp, _vp, _vp, _u32, _d, _u3, _f, _f, _vp, _vp, _vp, _u32, _vp],
-    "hu_mass_properties_level_owned": [_vp, _vp, _vp, _u32, _d, _u3, _f, _f, _vp, _vp, _vp, _u32, _u32, _u32, _vp],
-    "hu_mass_integrals_indirect": [_vp, _vp, _vp, _u32, _d, _vp, _u32, _vp],
+    "hu_mass_properties_level": [_V, _d, _vp],
+    "hu_mass_integrals": [_vp, _vp, _vp, _u32, _d, _vp, _u32, _vp],
     "hu_instance_table": [_c.POINTER(_vp), _u32, _i, _vp, _sz, _c.POINTER(_i), _c.POINTER(_u32)],
     "hu_interference_cells_indirect": [_L, _C],
     "hu_interference_leaf_indirect": [_L, _vp],
@@ -184,7 +186,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_char_p if name == "hu_last_error" else ctypes.c_int
-    if lib.hu_abi_version() != 2:
+    if lib.hu_abi_version() != 3:
         raise RuntimeError("libhip_util.so ABI version mismatch")
     _lib = lib
     return lib

@@ -5,14 +5,13 @@ inertia_tensor)` with the reference's semantics (reference mass_properties.py:30
 provably inside contribute closed-form moments of their integer indices, ambiguous cells are
 subdivided, the finest level classifies by the sign at the cell centre.
 
-Device side: one launch per LEVEL (`hu_mass_properties_level_indirect`) instead of one per block with
+Device side: one launch per LEVEL (`hu_mass_properties_level`) instead of one per block with
 three fresh allocations and two blocking reads each (reference :75-114), all levels enqueued back to
 back with their list lengths on the device and ONE synchronisation at the end; per-parent moment
 sums stay uint32 exactly like the reference's kernel so the integers are identical, and the
-fp64 conversion (`hu_mass_integrals_indirect`) applies the same formulas (reference :119-148).
+fp64 conversion (`hu_mass_integrals`) applies the same formulas (reference :119-148).
 """
 import collections
-import ctypes
 import math
 
 import numpy
@@ -22,6 +21,7 @@ from . import nodes
 from . import hip_util
 from . import subdivision
 from .hip_util import manager as hip_manager, check
+from .hip_util._lib import LevelLaunch
 
 
 class MassProperties(collections.namedtuple("MassProperties", "volume centroid inertia_tensor")):
@@ -90,8 +90,8 @@ def _enqueue_levels(tape, levels, box_a, capacities, queue):
     """Every level of the integration enqueued back to back, no host round trip between them: a list is a
     `[header row | rows...]` buffer of 32-byte rows whose header word 0 is its length; a level counts its ambiguous cells
     into the header of its child list, the next launch -- sized for the capacity -- reads its parent count from there
-    (`hu_mass_properties_level_indirect`), and the level's ten integrals are reduced on the device from the same count
-    (`hu_mass_integrals_indirect`).  The reference waits for the host after every block (mass_properties.py:98-114).
+    (`hu_mass_properties_level` with `n_parents_dev`), and the level's ten integrals are reduced on the device from the same
+    count (`hu_mass_integrals`).  The reference waits for the host after every block (mass_properties.py:98-114).
     What the host wants to see afterwards -- every list's header and every level's rows of integrals -- is gathered in ONE
     small device buffer (a 32-byte device-to-device copy per level; the integrals are written there directly) and read
     once, into its pinned shadow.  (Round 3 copied headers and integrals level by level into pageable numpy arrays: such a
@@ -115,22 +115,23 @@ def _enqueue_levels(tape, levels, box_a, capacities, queue):
     results = hip_util.Buffer(numpy.float64, (offsets[-1],), queue=queue)
     parents, max_parents = top, 1
     buffers = [top, results]
+    launch = LevelLaunch(tape=tape.device_ptr, stream=queue.handle, world=1, rank=0)
     for i, (s, dims) in enumerate(levels):
         leaf = i == len(levels) - 1
         capacity = 0 if leaf else capacities[i]
         thr = 0.0 if leaf else s * math.sqrt(3) / 2  # reference mass_properties.py:87-90
-        d = (ctypes.c_uint32 * 3)(int(dims[0]), int(dims[1]), int(dims[2]))
         children = hip_util.Buffer(numpy.float64, (capacity + 1, 4), queue=queue)
         sums = hip_util.Buffer(numpy.uint32, (max_parents, 10), queue=queue)
         out_ptr = results.device_ptr + 8 * (offsets[i] + 4)
         check(lib.hu_memset(children.device_ptr, 0, 32, queue.handle), "hu_memset")
         check(lib.hu_memset(sums.device_ptr, 0, max_parents * 40, queue.handle), "hu_memset")
-        check(lib.hu_mass_properties_level_indirect(tape.device_ptr, parents.device_ptr + 32, parents.device_ptr, max_parents, float(s), d,
-                                                    numpy.float32(s), numpy.float32(thr), sums.device_ptr, children.device_ptr,
-                                                    children.device_ptr + 32, capacity, queue.handle),
-              "hu_mass_properties_level_indirect")
-        check(lib.hu_mass_integrals_indirect(parents.device_ptr + 32, sums.device_ptr, parents.device_ptr, max_parents, float(s),
-                                             out_ptr, rows_of[i], queue.handle), "hu_mass_integrals_indirect")
+        launch.parents_dev, launch.n_parents_dev, launch.max_parents = parents.device_ptr + 32, parents.device_ptr, max_parents
+        launch.counter_dev, launch.children_dev, launch.capacity = children.device_ptr, children.device_ptr + 32, capacity
+        launch.dims = (int(dims[0]), int(dims[1]), int(dims[2]))
+        launch.step, launch.thr = s, thr
+        check(lib.hu_mass_properties_level(launch, float(s), sums.device_ptr), "hu_mass_properties_level")
+        check(lib.hu_mass_integrals(parents.device_ptr + 32, sums.device_ptr, parents.device_ptr, max_parents, float(s),
+                                    out_ptr, rows_of[i], queue.handle), "hu_mass_integrals")
         check(lib.hu_memcpy_d2d(results.device_ptr + 8 * offsets[i], children.device_ptr, 32, queue.handle), "hu_memcpy_d2d")
         buffers += [children, sums]
         if leaf:

@@ -23,6 +23,7 @@ from . import util
 from . import nodes
 from . import hip_util
 from .hip_util import manager as hip_manager, check
+from .hip_util._lib import LevelLaunch
 
 
 def calculate_block_sizes(box, dimension, resolution, grid_size, overlap, level_size_multiplier=1):
@@ -170,18 +171,18 @@ def _level_launch(tape, parents, n_parents, int_step, dims, dimension, resolutio
     cells = int(dims[0]) * int(dims[1]) * int(dims[2])
     box_step = int_step * resolution
     thr = box_step * math.sqrt(dimension) / 2  # reference subdivision.py:67
-    d = (ctypes.c_uint32 * 3)(int(dims[0]), int(dims[1]), int(dims[2]))
     o = (ctypes.c_double * 3)(origin.x, origin.y, origin.z)
     upper = n_parents * cells
     capacity = child_capacity(n_parents, cells) if capacity_hint is None else min(upper, capacity_hint)
+    launch = LevelLaunch(tape=tape.device_ptr, parents_dev=parents.device_ptr, n_parents_dev=None, counter_dev=counter.device_ptr,
+                         stream=queue.handle, max_parents=n_parents, world=1, rank=0, dims=(int(dims[0]), int(dims[1]), int(dims[2])),
+                         step=box_step, thr=thr)
     while True:
         children = hip_util.Buffer(numpy.int32, (max(capacity, 1), 4), queue=queue)
         counter.enqueue_fill(0)
         tape.note_samples(n_parents * int(dims[0]) * int(dims[1]) * int(dims[2]), hip_util.SPEC_CLASSIFY)
-        check(lib.hu_subdivision_level(tape.device_ptr, parents.device_ptr, n_parents, int(int_step), d,
-                                       dimension, float(resolution), o, numpy.float32(box_step),
-                                       numpy.float32(thr), counter.device_ptr, children.device_ptr,
-                                       capacity, queue.handle), "hu_subdivision_level")
+        launch.children_dev, launch.capacity = children.device_ptr, capacity
+        check(lib.hu_subdivision_level(launch, int(int_step), dimension, float(resolution), o), "hu_subdivision_level")
         count = int(counter.read()[0])
         if count <= capacity:
             return children, count
@@ -193,23 +194,23 @@ def _traverse_device_counted(tape, levels, dimension, resolution, origin, capaci
     """All classification levels enqueued back to back, no host round trip between them: every list is a
     `[header row | rows...]` buffer whose header word 0 is its length; a level counts into the header of its child
     list and the next launch -- sized for the capacity -- reads its parent count from there
-    (`hu_subdivision_level_indirect`).  Returns (buffers, counts) after ONE synchronisation; counts above the
+    (`hu_subdivision_level` with `n_parents_dev`).  Returns (buffers, counts) after ONE synchronisation; counts above the
     capacities mean "repeat with larger lists"."""
     lib = hip_manager.lib
     o = (ctypes.c_double * 3)(origin.x, origin.y, origin.z)
     top = hip_util.Buffer(numpy.int32, (2, 4), queue=queue)
     top.enqueue_write(numpy.array([[1, 0, 0, 0], [0, 0, 0, 0]], dtype=numpy.int32))
     buffers, parents, max_parents = [], top, 1
+    launch = LevelLaunch(tape=tape.device_ptr, stream=queue.handle, world=1, rank=0)
     for (int_step, dims), capacity in zip(levels[:-1], capacities):
         children = hip_util.Buffer(numpy.int32, (capacity + 1, 4), queue=queue)
         check(lib.hu_memset(children.device_ptr, 0, 16, queue.handle), "hu_memset")
         box_step = int_step * resolution
-        thr = box_step * math.sqrt(dimension) / 2  # reference subdivision.py:67
-        d = (ctypes.c_uint32 * 3)(int(dims[0]), int(dims[1]), int(dims[2]))
-        check(lib.hu_subdivision_level_indirect(tape.device_ptr, parents.device_ptr + 16, parents.device_ptr, max_parents,
-                                                int(int_step), d, dimension, float(resolution), o, numpy.float32(box_step),
-                                                numpy.float32(thr), children.device_ptr, children.device_ptr + 16, capacity,
-                                                queue.handle), "hu_subdivision_level_indirect")
+        launch.parents_dev, launch.n_parents_dev, launch.max_parents = parents.device_ptr + 16, parents.device_ptr, max_parents
+        launch.counter_dev, launch.children_dev, launch.capacity = children.device_ptr, children.device_ptr + 16, capacity
+        launch.dims = (int(dims[0]), int(dims[1]), int(dims[2]))
+        launch.step, launch.thr = box_step, box_step * math.sqrt(dimension) / 2  # reference subdivision.py:67
+        check(lib.hu_subdivision_level(launch, int(int_step), dimension, float(resolution), o), "hu_subdivision_level")
         buffers.append(children)
         parents, max_parents = children, capacity
     # the headers: small asynchronous reads, one wait

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HU_ABI_VERSION 2
+#define HU_ABI_VERSION 3
 
 enum hu_status {
     HU_OK = 0,
@@ -107,32 +107,46 @@ int hu_grid_eval_blocks(hu_tape t, const int32_t* blocks_dev, uint32_t n_blocks,
                         double resolution, const double origin[3], float step,
                         const uint32_t dims[3], int layout, void* out_dev, void* stream);
 
-/* One level of subdivision() for ALL parents at once (subdivision.py:48-113).
- * parents_dev: int32[4]*n_parents integer box corners; per parent the sample corner is
- * (int_corner + int_step/2)*resolution + origin in fp64 (z unshifted when dimension==2),
- * threshold = step*sqrt(dimension)/2 is computed by the caller.  Ambiguous cells are
- * appended (wavefront ballot scan, one atomic per workgroup) to children_dev as
- * int32[4] = parent + (x,y,z)*int_step, ready to be the next level's parents; the 4th
- * component is a caller tag (e.g. an object id) copied from parent to child untouched.
- * counter_dev (uint32, caller zeroes) ends up as the number of ambiguous cells even when it
- * exceeds `capacity` (extra cells are dropped: the caller re-runs with a larger list). */
-int hu_subdivision_level(hu_tape t, const int32_t* parents_dev, uint32_t n_parents,
-                         int32_t int_step, const uint32_t dims[3], int dimension,
-                         double resolution, const double origin[3], float step, float threshold,
-                         uint32_t* counter_dev, int32_t* children_dev, uint32_t capacity,
-                         void* stream);
+/* ---- the launch record of a level of a tape's hierarchy ----------------------------------------------
+ * hu_subdivision_level and hu_mass_properties_level classify one level for ALL its parents in one launch and take what such
+ * a launch needs as ONE record; then come the entry point's own arguments.  The record is read during the call and not
+ * kept: a caller may fill one and change its list fields from level to level.  A NULL record is HU_ERR_BAD_ARG.
+ * The list lengths.  n_parents_dev == NULL: exactly max_parents parents.  Else the length is ON THE DEVICE, so that a whole
+ * traversal can be enqueued without a host round trip between its levels: the launch covers max_parents (the list's
+ * capacity) and workgroups past *n_parents_dev leave at once.  Typical chaining: counter_dev = word 0 of a [header row |
+ * rows...] buffer and children_dev = its row 1, which makes the buffer the next level's (parents_dev = row 1, n_parents_dev
+ * = word 0) and, on several GPUs, the fixed-size piece of the all-gather (hu_slice_rows).  counter_dev (the caller zeroes
+ * it) ends up as the number of ambiguous cells even when it exceeds `capacity` (extra cells are dropped); the caller checks
+ * counter <= capacity -- once, at the end of a traversal -- and re-runs with a larger list.
+ * Ownership.  world = 1, rank = 0: every cell is kept.  world >= 2: a level that SEVERAL ranks classify in full (multi-GPU,
+ * codecad_amd/dist.py "replicated levels"; the reference has one device, cl_util/opencl_manager.py:89-98): of every parent's
+ * cells a rank lists -- and sums -- only those it OWNS: owner = mix(hash of the parent's row, the cell's linear index z + sz *
+ * (y + sy * x)) mod world.  The ranks' lists then partition the level's survivors (their moment sums add up to the level's)
+ * without any exchange, whatever order each rank's parents were in.  rank must be below world. */
+typedef struct hu_level_launch {        /* what every level launch of a tape takes */
+    hu_tape tape;
+    const void* parents_dev;            /* rows after the list's header: int32[4] (subdivision) or double[4] (mass properties) */
+    const uint32_t* n_parents_dev;      /* word 0 of the list's header; NULL: exactly max_parents parents */
+    uint32_t* counter_dev;              /* word 0 of the children's header */
+    void* children_dev;                 /* rows after it, of the parents' type; may be NULL for a capacity of 0 */
+    void* stream;
+    uint32_t max_parents, capacity;
+    uint32_t world, rank;
+    uint32_t dims[3];                   /* cells of a parent per axis, at most 256 each */
+    float step, thr;                    /* the cells' spacing and the threshold that makes a cell ambiguous */
+} hu_level_launch;
+#define HU_LEVEL_LAUNCH_BYTES 88
 
-/* The same with the list lengths ON THE DEVICE, so that a whole traversal can be enqueued without a host
- * round trip between its levels: the launch covers max_parents (the list's capacity) and workgroups past
- * *n_parents_dev leave at once.  Typical chaining: counter_dev = word 0 of a [header row | rows...] buffer and
- * children_dev = its row 1, which makes the buffer the next level's (parents_dev = row 1, n_parents_dev = word
- * 0) and, on several GPUs, the fixed-size piece of the all-gather (hu_slice_rows).  The caller checks
- * counter <= capacity once, at the end of the traversal. */
-int hu_subdivision_level_indirect(hu_tape t, const int32_t* parents_dev, const uint32_t* n_parents_dev,
-                                  uint32_t max_parents, int32_t int_step, const uint32_t dims[3],
-                                  int dimension, double resolution, const double origin[3], float step,
-                                  float threshold, uint32_t* counter_dev, int32_t* children_dev,
-                                  uint32_t capacity, void* stream);
+/* One level of subdivision() (subdivision.py:48-113).  parents_dev: int32[4] integer box corners; per parent the sample
+ * corner is (int_corner + int_step/2)*resolution + origin in fp64 (z unshifted when dimension==2), thr =
+ * step*sqrt(dimension)/2 is computed by the caller.  Ambiguous cells are appended (wavefront ballot scan, one atomic per
+ * workgroup) to children_dev as int32[4] = parent + (x,y,z)*int_step, ready to be the next level's parents; the 4th
+ * component is a caller tag (e.g. an object id) copied from parent to child untouched. */
+int hu_subdivision_level(const hu_level_launch* launch, int32_t int_step, int dimension, double resolution,
+                         const double origin[3]);
+
+/* hu_grid_eval_blocks with the number of blocks on the device, like a level's parents: the launch covers max_blocks and
+ * workgroups past *n_blocks_dev leave at once. */
 int hu_grid_eval_blocks_indirect(hu_tape t, const int32_t* blocks_dev, const uint32_t* n_blocks_dev,
                                  uint32_t max_blocks, double resolution, const double origin[3], float step,
                                  const uint32_t dims[3], int layout, void* out_dev, void* stream);
@@ -150,49 +164,21 @@ int hu_slice_rows(const void* gathered_dev, uint32_t world, uint32_t piece_rows,
 int hu_slice_rows_of(const void* piece_dev, uint32_t piece_rows, uint32_t row_bytes, uint32_t rank, uint32_t world,
                      void* out_dev, uint32_t out_capacity, uint32_t* stats_dev, void* stream);
 
-/* One level of mass_properties() for ALL parents (mass_properties.py:69-157).
- * parents_dev: double[4]*n_parents box corners; sample corner = corner + s/2 (fp64), cast
- * once.  sums_dev: uint32[10]*n_parents (caller zeroes), same order as hu_mass_properties.
- * children_dev: double[4] = (i,j,k)*s + corner (fp64), 4th component = the parent's tag,
- * appended like above. */
-int hu_mass_properties_level(hu_tape t, const double* parents_dev, uint32_t n_parents, double s,
-                             const uint32_t dims[3], float step, float threshold,
-                             uint32_t* sums_dev, uint32_t* counter_dev, double* children_dev,
-                             uint32_t capacity, void* stream);
+/* One level of mass_properties() (mass_properties.py:69-157).  parents_dev: double[4] box corners; sample corner = corner
+ * + s/2 (fp64), cast once.  sums_dev: uint32[10] per parent (the caller zeroes them for max_parents parents), same order
+ * as hu_mass_properties.  children_dev: double[4] = (i,j,k)*s + corner (fp64), 4th component = the parent's tag, appended
+ * like above (32-byte rows, and a header row of 32 bytes in the chained form). */
+int hu_mass_properties_level(const hu_level_launch* launch, double s, uint32_t* sums_dev);
 
 /* The ten integrals (1, x, y, z, xx, yy, zz, xy, xz, yz over the inside cells) of one level from
  * the per-parent index sums, with the per-block formulas of mass_properties.py:119-148 in fp64,
  * summed deterministically on the device: out_dev: double[rows][10], row g = the integrals of the g-th
  * of `rows` contiguous slices of the parents (Kahan per thread, fixed tree per workgroup); the caller adds
  * the rows in order.  rows = 1 gives the level's integrals directly; more rows spread a long level over
- * the chip (1 row per ~2048 parents is plenty). */
-int hu_mass_integrals(const double* parents_dev, const uint32_t* sums_dev, uint32_t n_parents, double s,
-                      double* out_dev, uint32_t rows, void* stream);
-
-/* The two above with the number of parents ON THE DEVICE (the launches cover max_parents, the list's capacity), so
- * that mass_properties() enqueues all its levels without a host round trip, like hu_subdivision_level_indirect:
- * counter_dev = word 0 of the children's [header row | rows...] buffer (32-byte rows), children_dev its row 1; the
- * caller zeroes sums_dev for max_parents parents and checks counter <= capacity once, at the end.  The integrals'
- * rows are cut from the actual count: the same slices as hu_mass_integrals(n_parents = the count). */
-int hu_mass_properties_level_indirect(hu_tape t, const double* parents_dev, const uint32_t* n_parents_dev,
-                                      uint32_t max_parents, double s, const uint32_t dims[3], float step,
-                                      float threshold, uint32_t* sums_dev, uint32_t* counter_dev,
-                                      double* children_dev, uint32_t capacity, void* stream);
-/* Levels that SEVERAL ranks classify in full (multi-GPU, codecad_amd/dist.py "replicated levels"; the reference has one
- * device, cl_util/opencl_manager.py:89-98): like the *_indirect forms, but of every parent's cells a rank lists -- and sums --
- * only those it OWNS: owner = mix(hash of the parent's row, the cell's linear index z + sz * (y + sy * x)) mod world.  The ranks'
- * lists then partition the level's survivors (their moment sums add up to the level's) without any exchange, whatever order
- * each rank's parents were in.  world = 1: the *_indirect forms. */
-int hu_subdivision_level_owned(hu_tape t, const int32_t* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                               int32_t int_step, const uint32_t dims[3], int dimension, double resolution,
-                               const double origin[3], float step, float threshold, uint32_t* counter_dev,
-                               int32_t* children_dev, uint32_t capacity, uint32_t world, uint32_t rank, void* stream);
-int hu_mass_properties_level_owned(hu_tape t, const double* parents_dev, const uint32_t* n_parents_dev, uint32_t max_parents,
-                                   double s, const uint32_t dims[3], float step, float threshold, uint32_t* sums_dev,
-                                   uint32_t* counter_dev, double* children_dev, uint32_t capacity, uint32_t world,
-                                   uint32_t rank, void* stream);
-int hu_mass_integrals_indirect(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev,
-                               uint32_t max_parents, double s, double* out_dev, uint32_t rows, void* stream);
+ * the chip (1 row per ~2048 parents is plenty).  n_parents_dev as in the record: NULL for exactly max_parents parents,
+ * else the rows are cut from the count on the device (at most max_parents): the same slices as with that many parents. */
+int hu_mass_integrals(const double* parents_dev, const uint32_t* sums_dev, const uint32_t* n_parents_dev,
+                      uint32_t max_parents, double s, double* out_dev, uint32_t rows, void* stream);
 
 /* ---- the launch records of the entry points over instance cells ------------------------------------
  * Every entry point from here to hu_mesh_leaf_instances (hu_instance_table apart) launches one kernel over a list of cells

@@ -66,7 +66,7 @@ def _pipeline(tape, levels, resolution, origin, n_objects, capacities, replicate
             n, cells = oracle.subdivision_step(tape, np.array(corner).astype(np.float32), np.float32(step),
                                                np.float32(step * math.sqrt(3) / 2), dims)
             for i, j, k_, _ in cells.tolist():
-                # a replicated level (hu_subdivision_level_owned): of every parent's cells a rank lists those it owns
+                # a replicated level (hu_subdivision_level with world >= 2): of every parent's cells a rank lists those it owns
                 if own is not None and dist.owner_of([ix, iy, iz, obj], k_ + dims[2] * (j + dims[1] * i), own[0]) != own[1]:
                     continue
                 rows.append([ix + i * int_step, iy + j * int_step, iz + k_ * int_step, obj])
@@ -129,7 +129,7 @@ def _integrate_pipeline(tape, box_a, levels, capacities, replicate=0, details=No
     per_level = [torch.zeros(10, dtype=torch.float64) for _ in levels]
 
     def owned_kernel(row_words, shifted, s, thr, dims, own):
-        """hu_mass_properties_level_owned restated over the oracle's distances: the kernel of mass_properties.cl:7-56 with
+        """hu_mass_properties_level with world >= 2 restated over the oracle's distances: the kernel of mass_properties.cl:7-56 with
         every cell that another rank owns left out of the sums and of the list"""
         w = oracle.grid_eval(tape, shifted.astype(np.float32), np.float32(s), dims)[..., 3]
         idx = np.indices(dims).reshape(3, -1).T

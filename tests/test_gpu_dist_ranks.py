@@ -1,5 +1,5 @@
 """Several ranks sharing ONE GPU through gloo (host-staged collectives): the real multi-rank pipelines -- the HIP kernels,
-hu_*_level_owned, hu_slice_rows -- of dist.mass_properties and dist.subdivision, compared with the single-GPU drivers.
+the level launches' world and rank, hu_slice_rows -- of dist.mass_properties and dist.subdivision, compared with the single-GPU drivers.
 
 Worlds of 2 and 3 ranks are spawned in turn, each under three replication settings (CODECAD_AMD_REPLICATE_SAMPLES = 0:
 every level exchanged; the default; a huge value: every non-leaf level replicated).  Every rank reports through a queue;

@@ -190,6 +190,7 @@ def test_object_tags_and_torch_interop(hip):
     import codecad_amd as cc
     from codecad_amd import dist
     from codecad_amd.hip_util import check
+    from codecad_amd.hip_util._lib import LevelLaunch
     shape = cc.examples.sponge(2)
     tape = cc.nodes.make_program_buffer(shape)
     res = 1 / 54
@@ -200,15 +201,15 @@ def test_object_tags_and_torch_interop(hip):
 
     def classify(level, parents):
         int_step, d = levels[level]
-        dd = (ctypes.c_uint32 * 3)(int(d[0]), int(d[1]), int(d[2]))
         cap = int(parents.shape[0]) * int(d[0]) * int(d[1]) * int(d[2])
         children = torch.empty((cap, 4), dtype=torch.int32, device="cuda")
         counter.zero_()
         torch.cuda.synchronize()
-        check(hip.lib.hu_subdivision_level(tape.device_ptr, parents.contiguous().data_ptr(), int(parents.shape[0]),
-                                           int(int_step), dd, 3, res, origin, np.float32(int_step * res),
-                                           np.float32(int_step * res * math.sqrt(3) / 2), counter.data_ptr(),
-                                           children.data_ptr(), cap, None), "hu_subdivision_level")
+        launch = LevelLaunch(tape=tape.device_ptr, parents_dev=parents.contiguous().data_ptr(), n_parents_dev=None,
+                             counter_dev=counter.data_ptr(), children_dev=children.data_ptr(), stream=None,
+                             max_parents=int(parents.shape[0]), capacity=cap, world=1, rank=0, dims=(int(d[0]), int(d[1]), int(d[2])),
+                             step=np.float32(int_step * res), thr=np.float32(int_step * res * math.sqrt(3) / 2))
+        check(hip.lib.hu_subdivision_level(launch, int(int_step), 3, res, origin), "hu_subdivision_level")
         torch.cuda.synchronize()
         return children[:int(counter.item())]
 
@@ -301,15 +302,15 @@ def test_device_integrals_match_host_formulas(hip):
             results = []
             for _ in range(2):
                 ob.enqueue_fill(0xff)           # every row must be written, also the empty ones
-                check(hip.lib.hu_mass_integrals(pb.device_ptr, sb.device_ptr, n, s, ob.device_ptr, rows, hip.queue.handle),
+                check(hip.lib.hu_mass_integrals(pb.device_ptr, sb.device_ptr, None, n, s, ob.device_ptr, rows, hip.queue.handle),
                       "integrals")
                 results.append(ob.read().copy())
             assert np.array_equal(results[0], results[1])
             for k, v in zip(_KEYS, results[0].sum(axis=0)):
                 assert v == pytest.approx(want[k], rel=1e-12, abs=1e-13 * scale * n)
             ob.release()
-        assert hip.lib.hu_mass_integrals(pb.device_ptr, sb.device_ptr, n, s, pb.device_ptr, 0, hip.queue.handle) != 0
-        # the indirect form: the count on the device, the launch sized for a larger capacity -> the same rows
+        assert hip.lib.hu_mass_integrals(pb.device_ptr, sb.device_ptr, None, n, s, pb.device_ptr, 0, hip.queue.handle) != 0
+        # the count on the device, the launch sized for a larger capacity -> the same rows
         nb = hip_util.Buffer(np.uint32, 1)
         nb.enqueue_write(np.array([n], np.uint32))
         big_p, big_s = hip_util.Buffer(np.float64, (n + 100, 4)), hip_util.Buffer(np.uint32, (n + 100, 10))
@@ -319,9 +320,9 @@ def test_device_integrals_match_host_formulas(hip):
         check(hip.lib.hu_memcpy_d2d(big_s.device_ptr, sb.device_ptr, n * 40, hip.queue.handle), "copy")
         for rows in (1, 3, 64):
             direct, indirect = hip_util.Buffer(np.float64, (rows, 10)), hip_util.Buffer(np.float64, (rows, 10))
-            check(hip.lib.hu_mass_integrals(pb.device_ptr, sb.device_ptr, n, s, direct.device_ptr, rows, hip.queue.handle), "integrals")
-            check(hip.lib.hu_mass_integrals_indirect(big_p.device_ptr, big_s.device_ptr, nb.device_ptr, n + 100, s, indirect.device_ptr, rows,
-                                                     hip.queue.handle), "integrals")
+            check(hip.lib.hu_mass_integrals(pb.device_ptr, sb.device_ptr, None, n, s, direct.device_ptr, rows, hip.queue.handle), "integrals")
+            check(hip.lib.hu_mass_integrals(big_p.device_ptr, big_s.device_ptr, nb.device_ptr, n + 100, s, indirect.device_ptr, rows,
+                                            hip.queue.handle), "integrals")
             assert np.array_equal(direct.read(), indirect.read())
 
 
@@ -510,7 +511,7 @@ def test_slice_rows_kernel_equals_the_reference_rule(hip):
 
 @pytest.mark.parametrize("name, resolution, grid", [("sponge3", 1 / 243, 9), ("sponge4", 1 / 512, 16), ("csg_example", 1.0, 8)])
 def test_pipeline_without_host_round_trips_equals_the_level_driver(hip, name, resolution, grid):
-    """dist.LevelPipeline over hu_subdivision_level_indirect (list lengths read on the device, launches sized for
+    """dist.LevelPipeline over hu_subdivision_level with n_parents_dev (list lengths read on the device, launches sized for
     the capacities) gives the leaf set of subdivision_device; the leaf blocks evaluated through
     hu_grid_eval_blocks_indirect equal the direct launch; a capacity that is too small is reported."""
     import torch
@@ -600,7 +601,7 @@ def test_library_forms_over_a_process_group(hip, forced):
 
 
 def test_replicated_levels_partition_by_ownership(hip):
-    """What replicated levels of a multi-rank traversal rest on (dist.LevelPipeline `replicate`, hu_*_level_owned): when
+    """What replicated levels of a multi-rank traversal rest on (dist.LevelPipeline `replicate`, a level's launch with world >= 2): when
     `world` ranks classify the same parents, each listing the cells it owns, the lists partition the level -- whatever the
     order of a rank's parents and of its atomics, whichever evaluator or launch shape serves it -- and a cell's owner is
     dist.owner_of(parent row, linear cell index); the owned moment sums of mass_properties add up to the level's."""
@@ -608,6 +609,7 @@ def test_replicated_levels_partition_by_ownership(hip):
     import codecad_amd as cc
     from codecad_amd import subdivision, dist, hip_util
     from codecad_amd.hip_util import check
+    from codecad_amd.hip_util._lib import LevelLaunch
     shape = cc.examples.sponge(4)
     res = 1 / 512
     box = shape.bounding_box().expanded_additive(res / 2)
@@ -619,16 +621,15 @@ def test_replicated_levels_partition_by_ownership(hip):
 
     def level(parents, lvl, own=None, capacity=40000):
         int_step, dims = levels[lvl]
-        d = (ctypes.c_uint32 * 3)(int(dims[0]), int(dims[1]), int(dims[2]))
         n = torch.tensor([parents.shape[0]], dtype=torch.int32, device=dev)
         out = torch.zeros((capacity + 1, 4), dtype=torch.int32, device=dev)
         step = np.float32(int_step * res)
-        args = (tape.device_ptr, parents.data_ptr(), n.data_ptr(), int(parents.shape[0]), int(int_step), d, 3, float(res), origin, step,
-                np.float32(float(step) * 3 ** 0.5 / 2), out.data_ptr(), out[1:].data_ptr(), capacity)
-        if own is None:
-            check(hip.lib.hu_subdivision_level_indirect(*args, stream), "level")
-        else:
-            check(hip.lib.hu_subdivision_level_owned(*args, own[0], own[1], stream), "level owned")
+        world, rank = own or (1, 0)
+        launch = LevelLaunch(tape=tape.device_ptr, parents_dev=parents.data_ptr(), n_parents_dev=n.data_ptr(), counter_dev=out.data_ptr(),
+                             children_dev=out[1:].data_ptr(), stream=stream, max_parents=int(parents.shape[0]), capacity=capacity,
+                             world=world, rank=rank, dims=(int(dims[0]), int(dims[1]), int(dims[2])), step=step,
+                             thr=np.float32(float(step) * 3 ** 0.5 / 2))
+        check(hip.lib.hu_subdivision_level(launch, int(int_step), 3, float(res), origin), "level")
         torch.cuda.synchronize()
         return out[1:1 + int(out[0, 0])].clone()
 
@@ -665,7 +666,6 @@ def test_replicated_levels_partition_by_ownership(hip):
     # mass properties: the owned sums and lists of `world` ranks add up to the level's
     mlevels = [(res * cell, tuple(int(v) for v in dims)) for cell, dims in subdivision.calculate_block_sizes(shape.bounding_box(), 3, res, 8, overlap=False)]
     s, dims = mlevels[0]
-    d = (ctypes.c_uint32 * 3)(*dims)
     parent = torch.zeros((1, 4), dtype=torch.float64, device=dev)
     parent[0, :3] = torch.tensor([shape.bounding_box().a.x, shape.bounding_box().a.y, shape.bounding_box().a.z], dtype=torch.float64)
     one = torch.tensor([1], dtype=torch.int32, device=dev)
@@ -673,12 +673,11 @@ def test_replicated_levels_partition_by_ownership(hip):
     def mass(own=None):
         sums = torch.zeros((1, 10), dtype=torch.int32, device=dev)
         out = torch.zeros((600, 4), dtype=torch.float64, device=dev)
-        args = (tape.device_ptr, parent.data_ptr(), one.data_ptr(), 1, float(s), d, np.float32(s), np.float32(s * 3 ** 0.5 / 2), sums.data_ptr(),
-                out.data_ptr(), out[1:].data_ptr(), 599)
-        if own is None:
-            check(hip.lib.hu_mass_properties_level_indirect(*args, stream), "mass level")
-        else:
-            check(hip.lib.hu_mass_properties_level_owned(*args, own[0], own[1], stream), "mass level owned")
+        world, rank = own or (1, 0)
+        launch = LevelLaunch(tape=tape.device_ptr, parents_dev=parent.data_ptr(), n_parents_dev=one.data_ptr(), counter_dev=out.data_ptr(),
+                             children_dev=out[1:].data_ptr(), stream=stream, max_parents=1, capacity=599, world=world, rank=rank, dims=dims,
+                             step=np.float32(s), thr=np.float32(s * 3 ** 0.5 / 2))
+        check(hip.lib.hu_mass_properties_level(launch, float(s), sums.data_ptr()), "mass level")
         torch.cuda.synchronize()
         n = int(out.view(torch.int32)[0, 0])
         return sums.cpu().numpy().astype(np.int64)[0], sorted(map(tuple, out[1:1 + n].cpu().tolist()))

@@ -137,6 +137,7 @@ def test_subdivision_level_across_the_limit(hip, spec, name, monkeypatch):
     on the distances' last bits; out there nothing is within a cell's diagonal of the surface.)"""
     import torch
     from codecad_amd.hip_util import check
+    from codecad_amd.hip_util._lib import LevelLaunch
     handle, tape = spec(name)
     monkeypatch.setenv("HU_CLASSIFY_BOX_MIN", "1")
     q, origin, parents = _level_parents(name)
@@ -158,9 +159,10 @@ def test_subdivision_level_across_the_limit(hip, spec, name, monkeypatch):
     children = torch.full((cap, 4), -1, dtype=torch.int32, device="cuda")
     counter = torch.zeros(1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    check(hip.lib.hu_subdivision_level(handle.device_ptr, parents_dev.data_ptr(), len(parents), int_step, (ctypes.c_uint32 * 3)(*dims), 3,
-                                       float(q), (ctypes.c_double * 3)(*origin), step, thr, counter.data_ptr(), children.data_ptr(), cap, None),
-          "hu_subdivision_level")
+    launch = LevelLaunch(tape=handle.device_ptr, parents_dev=parents_dev.data_ptr(), n_parents_dev=None, counter_dev=counter.data_ptr(),
+                         children_dev=children.data_ptr(), stream=None, max_parents=len(parents), capacity=cap, world=1, rank=0, dims=dims,
+                         step=step, thr=thr)
+    check(hip.lib.hu_subdivision_level(launch, int_step, 3, float(q), (ctypes.c_double * 3)(*origin)), "hu_subdivision_level")
     torch.cuda.synchronize()
     got_n = int(counter.item())
     assert got_n == len(want)
@@ -173,6 +175,7 @@ def test_mass_properties_level_across_the_limit(hip, spec, name, monkeypatch):
     four parents against the oracle's mass_properties per parent -- the ten sums, the count and the children."""
     import torch
     from codecad_amd.hip_util import check
+    from codecad_amd.hip_util._lib import LevelLaunch
     handle, tape = spec(name)
     monkeypatch.setenv("HU_CLASSIFY_BOX_MIN", "1")
     q, origin, parents = _level_parents(name)
@@ -196,9 +199,10 @@ def test_mass_properties_level_across_the_limit(hip, spec, name, monkeypatch):
     sums_dev = torch.zeros((len(parents), 10), dtype=torch.int32, device="cuda")
     counter = torch.zeros(1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    check(hip.lib.hu_mass_properties_level(handle.device_ptr, parents_dev.data_ptr(), len(parents), float(s), (ctypes.c_uint32 * 3)(*dims),
-                                           step, thr, sums_dev.data_ptr(), counter.data_ptr(), children.data_ptr(), cap, None),
-          "hu_mass_properties_level")
+    launch = LevelLaunch(tape=handle.device_ptr, parents_dev=parents_dev.data_ptr(), n_parents_dev=None, counter_dev=counter.data_ptr(),
+                         children_dev=children.data_ptr(), stream=None, max_parents=len(parents), capacity=cap, world=1, rank=0, dims=dims,
+                         step=step, thr=thr)
+    check(hip.lib.hu_mass_properties_level(launch, float(s), sums_dev.data_ptr()), "hu_mass_properties_level")
     torch.cuda.synchronize()
     got_n = int(counter.item())
     assert got_n == len(want)

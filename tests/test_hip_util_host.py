@@ -18,7 +18,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert sorted(_lib.PROTOTYPES) == declared      # every declared function has a typed binding
-    assert lib.hu_abi_version() == 2
+    assert lib.hu_abi_version() == 3
 
 
 CELL_LEVELS = ["hu_interference_cells_indirect", "hu_clearance_cells_indirect", "hu_section_tiles", "hu_outline_tiles", "hu_layer_tiles",
@@ -49,6 +49,82 @@ def test_the_launch_records_mirror_the_header():
         assert ctypes.sizeof(structure) == size, record
     # field by field: the C compiler's layout (instance_args.hpp asserts the sizes) is ctypes' for these types
     assert _lib.CellsLaunch.dims.offset == 64 and _lib.CellsLaunch.step.offset == 88 and _lib.CellsChildren.thr.offset == 24
+
+
+LEVELS = ["hu_subdivision_level", "hu_mass_properties_level"]
+# the entry points the record replaced (ABI 2): gone from the header and from the binding
+DELETED = [name + form for name in LEVELS for form in ("_indirect", "_owned")] + ["hu_mass_integrals" + "_indirect"]
+
+
+def test_the_level_record_mirrors_the_header():
+    """The two level entry points of a tape take hu_level_launch first and nothing else does; the ctypes Structure that fills it has
+    the header's fields, in its order, and its size; the entry points the record replaced are declared and typed nowhere."""
+    import re
+    with open(_lib.HEADER) as f:
+        header = f.read()
+    record = ctypes.POINTER(_lib.LevelLaunch)
+    for name in LEVELS:
+        assert _lib.PROTOTYPES[name][0] == record and record not in _lib.PROTOTYPES[name][1:], name
+    assert sorted(name for name, argtypes in _lib.PROTOTYPES.items() if record in argtypes) == sorted(LEVELS)
+    body = re.search(r"typedef struct hu_level_launch \{(.*?)\} hu_level_launch;", header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    declared = [re.sub(r"\[\d+\]", "", part.split()[-1]).strip("*") for line in body.split(";") if line.strip() for part in line.split(",")]
+    assert declared == [name for name, _ in _lib.LevelLaunch._fields_]
+    assert declared == ["tape", "parents_dev", "n_parents_dev", "counter_dev", "children_dev", "stream", "max_parents", "capacity", "world",
+                        "rank", "dims", "step", "thr"]
+    assert ctypes.sizeof(_lib.LevelLaunch) == int(re.search(r"#define HU_LEVEL_LAUNCH_BYTES (\d+)", header).group(1)) == 88
+    # field by field: the C compiler's layout (hip_util.hip asserts these) is ctypes' for these types
+    assert (_lib.LevelLaunch.max_parents.offset, _lib.LevelLaunch.dims.offset, _lib.LevelLaunch.thr.offset) == (48, 64, 80)
+    assert sorted(_lib.PROTOTYPES) == _lib.header_symbols()
+    assert len(DELETED) == 5 and not [name for name in DELETED if name in _lib.PROTOTYPES or name in _lib.header_symbols() or name in header]
+    assert len(_lib.PROTOTYPES["hu_mass_integrals"]) == 8 and _lib.load().hu_abi_version() == 3
+
+
+def test_the_level_entry_points_refuse_bad_arguments_without_a_device():
+    """Every argument check of hu_subdivision_level, hu_mass_properties_level and hu_mass_integrals, one broken field at a time, by
+    return code and by the exact text of hu_last_error(); all of them come before anything touches a device."""
+    import level_abi
+    lib = _lib.load()
+    FAKE = level_abi.FAKE
+    origin = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+
+    def subdivision(origin=origin, dimension=3, **broken):
+        return lib.hu_subdivision_level(level_abi.launch(**broken), 1, dimension, 0.5, origin)
+
+    def mass(sums=FAKE, **broken):
+        return lib.hu_mass_properties_level(level_abi.launch(**broken), 0.5, sums)
+
+    def integrals(parents=FAKE, sums=FAKE, n_parents=FAKE, max_parents=1, out=FAKE, rows=1):
+        return lib.hu_mass_integrals(parents, sums, n_parents, max_parents, 0.5, out, rows, None)
+
+    def refused(rc, message):
+        assert rc == -3 and lib.hu_last_error() == message, (rc, lib.hu_last_error())
+
+    # what the cases below break is accepted whole: an empty list launches nothing, and may have NULL parents and children
+    for entry in (subdivision, mass):
+        assert entry() == 0
+        assert entry(parents_dev=None, children_dev=None, n_parents_dev=None) == 0
+        assert entry(world=3, rank=2) == 0
+        refused(entry(**level_abi.NULL_RECORD), b"NULL argument")
+        refused(entry(tape=None), b"NULL argument")
+        refused(entry(counter_dev=None), b"NULL argument")
+        refused(entry(children_dev=None, capacity=1), b"NULL argument")
+        refused(entry(parents_dev=None, max_parents=1), b"NULL argument")
+        refused(entry(world=0), b"rank must be below world")
+        refused(entry(world=1, rank=1), b"rank must be below world")
+        refused(entry(world=2, rank=2), b"rank must be below world")
+        refused(entry(dims=(8, 0, 8)), b"dims must be >= 1 on every axis")
+        refused(entry(dims=(8, 8, 257)), b"grid size > 256 would overflow the uchar4 cell index (reference subdivision.py:206-208)")
+        refused(entry(dims=(512, 512, 512)), b"at most 2^24 cells (256^3) per block: cell indices are uchar4")
+    refused(subdivision(origin=None), b"NULL argument")
+    refused(subdivision(dimension=1), b"dimension must be 2 or 3")
+    refused(subdivision(dimension=4), b"dimension must be 2 or 3")
+    refused(mass(sums=None), b"NULL argument")
+    refused(integrals(out=None), b"NULL argument")
+    refused(integrals(parents=None), b"NULL argument")
+    refused(integrals(sums=None), b"NULL argument")
+    refused(integrals(rows=0), b"rows must be in 1..65535")
+    refused(integrals(rows=65536), b"rows must be in 1..65535")
 
 
 def test_no_gpu_means_loud_failure_not_fallback():

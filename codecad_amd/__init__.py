@@ -32,7 +32,10 @@ another and in what order the parts come apart by straight moves, by one scan pe
 form connected groups and which hang loose, by one pass across the faces of that volume on the device (contacts.py);
 `drainage(asm, resolution, axis, up)` says what the assembly holds when it is drained with a lattice axis pointing up -- cups,
 blind holes, U-bends, pockets between parts --, on which parts each pool stands and how high it fills, by a labelling of the
-layers and a scan with a carry along the lattice lines on the device (drainage.py).
+layers and a scan with a carry along the lattice lines on the device (drainage.py);
+`islands(asm, resolution, axis, up, of)` says what a print along a lattice axis starts in mid-air -- a peg hanging from a
+ceiling, the short leg of an arch, a captive ball --, where each island starts, where it is finally joined from above and
+which islands stay loose, by grounding the solid from the plate with the same layer labelling and scans (islands.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -63,6 +66,7 @@ from .overhangs import overhangs, OverhangReport  # noqa: F401
 from .disassembly import disassembly, DisassemblyReport  # noqa: F401
 from .contacts import contacts, ContactReport  # noqa: F401
 from .drainage import drainage, DrainageReport, Pool  # noqa: F401
+from .islands import islands, IslandReport, Island  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
@@ -71,4 +75,5 @@ __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "m
            "AssemblyMassReport", "PartMass", "assembly_meshes", "Meshes", "TRIANGLE", "assembly_voxels", "AssemblyVoxels",
            "assembly_components", "cavities", "ComponentsReport", "CavityReport", "Component", "Cavity", "EMPTY_SPACE", "SOLID",
            "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport",
-           "contacts", "ContactReport", "drainage", "DrainageReport", "Pool"]
+           "contacts", "ContactReport", "drainage", "DrainageReport", "Pool", "islands",
+           "IslandReport", "Island"]

@@ -101,6 +101,42 @@ __device__ __forceinline__ void unite(uint32_t* label, uint32_t a, uint32_t b)
     }
 }
 
+// THE FLAG OF A ROOT, for the kernels that hand a property of whole layer components on from layer to layer over a flattened
+// label volume of at most 2^31 entries: the escape of instance_drain.hip, the grounding of instance_ground.hip.
+constexpr uint32_t kFlag = 0x80000000u;     // a root's entry: index | kFlag once its component escapes
+
+// an entry as the L2 holds it: flags are set by other workgroups while a kernel runs.  A stale one would cost an atomic or a
+// pass, never a result.
+__device__ __forceinline__ uint32_t live(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Is the root of the sample q of E, whose entry reads l != kNone, flagged?  After the flatten an entry is its root's index; a
+// root's own entry is its index, with kFlag once it escapes.
+__device__ __forceinline__ bool escapes(const uint32_t* labels, uint32_t l, uint32_t q)
+{
+    if (l & kFlag) return true;
+    if (l == q) return false;
+    return (live(labels + l) & kFlag) != 0u;
+}
+
+// The lanes of `want` flag their roots r (indices, no flag in them) -> this lane's atomic found the flag unset.  DISTINCT: no two
+// lanes share a root (they lie in different layers); else one atomic per distinct root, issued by the first lane that has it.
+template <bool DISTINCT>
+__device__ __forceinline__ bool raise(uint32_t* labels, uint32_t lane, bool want, uint32_t r)
+{
+    bool fresh = false;
+    if (DISTINCT) {
+        if (want) fresh = (atomicOr(labels + r, kFlag) & kFlag) == 0u;
+    } else {
+        for (uint64_t todo = __ballot(want); todo != 0ull;) {              // wave-uniform
+            const uint32_t first = (uint32_t)__builtin_ctzll(todo);
+            const uint32_t root = (uint32_t)__builtin_amdgcn_readlane((int)r, (int)first);
+            todo &= ~__ballot(want && r == root);
+            if (lane == first) fresh = (atomicOr(labels + root, kFlag) & kFlag) == 0u;
+        }
+    }
+    return fresh;
+}
+
 // host side (`dims` is not NULL): the checks, and the fill of the lattice's fields
 inline int check_pitch(const uint32_t dims[3], uint32_t pitch)
 {

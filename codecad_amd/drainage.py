@@ -35,7 +35,7 @@ another.
 
 OUT OF SCOPE.  Directions off the lattice axes; partial fill levels; drain holes sized by a ball (the transform of `thin_walls`
 on empty space); the transitive grounded-from-the-plate closure of the SOLID, the dual problem and the next caller of the first
-three stages; whether a pool is a sealed cavity (DESIGN.md section 9.2 says what that would cost; compare `labels` with those
+three stages (`islands()`, islands.py, is that caller); whether a pool is a sealed cavity (DESIGN.md section 9.2 says what that would cost; compare `labels` with those
 of `cavities()`); more than 64 instances; several devices.
 
 ON THE DEVICE (csrc/instance_drain.hip), monotone reachability: connected within a layer, handed on from layer to layer in one

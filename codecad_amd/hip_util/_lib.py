@@ -111,6 +111,9 @@ PROTOTYPES = {
     "hu_drain_seed": [_vp, _u3, _u32, _i, _i, _vp],
     "hu_drain_rise": [_vp, _vp, _u3, _u32, _i, _i, _vp],
     "hu_drain_floor": [_vp, _vp, _vp, _vp, _u3, _u32, _i, _i, _vp],
+    "hu_ground_layers": [_vp, _vp, _u3, _u32, _i, _u32, _i, _vp],
+    "hu_ground_seed": [_vp, _vp, _u3, _u32, _i, _i, _vp],
+    "hu_ground_mark": [_vp, _vp, _vp, _vp, _vp, _vp, _u3, _u32, _i, _i, _u32, _vp],
     "hu_ray_caster": [_vp, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp],
     "hu_ray_caster_instances": [_vp, _u32, _i, _u32, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp, _vp, _vp,
                                 _u32, _vp, _vp],

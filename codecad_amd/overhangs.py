@@ -46,6 +46,8 @@ ballots of S and O and hands a carry from word to word.  The host does not wait 
 DEVICE MEMORY.  While the kernels run the ids and the three id volumes are held, 4 bytes a sample of the device buffer
 nx * ny * pz; the labelling afterwards holds `support_ids` and the labels, 5: the peak.  ValueError when
 5 * nx * ny * pz > max_bytes, and when the label volume would have more than 2^31 entries, before anything is launched.
+OUT OF SCOPE here: whether what lies below a sample is itself held, the transitive grounded-from-the-plate closure; that is
+`islands()` (islands.py), whose starts are the floating overhangs of `reach_sq=0`.
 """
 import collections
 

@@ -535,6 +535,36 @@ int hu_drain_rise(void* labels_dev, uint32_t* changed_dev, const uint32_t dims[3
 int hu_drain_floor(const void* ids_dev, const void* labels_dev, void* trapped_dev, uint64_t* counts_dev, const uint32_t dims[3],
                    uint32_t pitch, int axis, int up, void* stream);
 
+/* ---- what a print starts in mid-air: grounding from the plate (codecad_amd/islands.py) -----------
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, aligned to 16 bytes: S is its samples
+ * z < dims[2] with id != 255 (of == HU_OVERHANG_SOLID) or id == of (of <= 63); nothing outside the lattice is in S, and the
+ * padding z in [dims[2], pitch) of any volume is neither read nor written as data.  `axis`, `up`, the layers, "below" and the
+ * lateral axes are those of the drain entry points above; h0 is the least layer that holds a sample of S, and word_dev the depth
+ * word that hu_overhang_first_layer raised to dims[axis] - h0 (0: S is empty).  G, the GROUNDED samples, is the least subset
+ * of S that holds every sample of S in layer h0 and every sample of S whose sample below or one of whose in-lattice lateral
+ * neighbours is in G; F = S \ G FLOATS.  labels_dev is as for the drain entry points, over S in place of E, and bit 31 of a
+ * root's entry says that its layer component is grounded.  The calls are made in this order on one stream:
+ * hu_overhang_first_layer (above), with the caller's zeroed word and the same `of`.
+ * hu_ground_layers: labels every layer of S at once: local != 0 in tiles of HU_COMPONENTS_TILE_X x _Y x _Z samples in LDS, then
+ *   a merge across the tile faces of the two lateral axes; local == 0 from label = own index, a merge of every lateral pair.
+ * hu_components_flatten (above): every entry becomes the index of its root.
+ * hu_ground_seed: reads the word on the device; every sample of S in layer h0 sets the flag of its root, nothing else does.
+ * hu_drain_rise (above), unchanged, repeated until a pass leaves its word zero: the flagged roots are then those of G.
+ * hu_ground_mark: three volumes of the shape of ids_dev, every in-lattice byte of each written exactly once: floating_dev <- the
+ *   id on F, start_dev <- the id on the samples of F whose sample below is not in S, join_dev <- the id on the samples of F
+ *   whose sample above is in G, 255 elsewhere.  counts_dev (3 x 64 uint64, aligned to 8, the caller's zeros): [p] += the
+ *   samples of F with id p, [64 + p] += the starts, [128 + p] += the joins.  One atomic per accumulator and wavefront.
+ * All allocate nothing and synchronise nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL
+ * pointers, a pitch that is no multiple of 16 or below dims[2], dims of 0 or above 65536, an axis outside 0..2, more than 2^31
+ * entries (hu_ground_seed: exactly 2^31 with up == 0, where the flag of the last entry would read as 0xffffffff), an `of` above
+ * 63 that is not HU_OVERHANG_SOLID, ids not aligned to 16, labels or the word not to 4 or counts not to 8 bytes. */
+int hu_ground_layers(const void* ids_dev, void* labels_dev, const uint32_t dims[3], uint32_t pitch, int axis, uint32_t of,
+                     int local, void* stream);
+int hu_ground_seed(void* labels_dev, const uint32_t* word_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up,
+                   void* stream);
+int hu_ground_mark(const void* ids_dev, const void* labels_dev, void* floating_dev, void* start_dev, void* join_dev,
+                   uint64_t* counts_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, uint32_t of, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

@@ -68,7 +68,7 @@ template <class I = size_t, class A> __device__ __forceinline__ LineUnitOf<I> li
     for (uint64_t unit = (uint64_t)blockIdx.x * 4u + hu_cells::uniform(threadIdx.x >> 6); unit < (units); unit += (uint64_t)gridDim.x * 4u)
 
 // THE UNION-FIND over a uint32 label volume (instance_components.hip states THE INVARIANT: label[q] <= q, entries only ever fall,
-// labels are buffer indices), for every kernel that labels: the components, and the layers of instance_drain.hip.
+// labels are buffer indices), for every kernel that labels: the components, and the layers of instance_reach.hip.
 // The root of p: labels strictly decrease along the walk (THE INVARIANT, label[p] <= p), so it ends.  A value read here may
 // be stale (a plain load may be served by L1 while another workgroup's atomic has lowered the entry since): a stale parent
 // is still an ancestor -- whoever replaced the link p -> v took on uniting v with what it wrote --, so the walk still ends
@@ -102,7 +102,7 @@ __device__ __forceinline__ void unite(uint32_t* label, uint32_t a, uint32_t b)
 }
 
 // THE FLAG OF A ROOT, for the kernels that hand a property of whole layer components on from layer to layer over a flattened
-// label volume of at most 2^31 entries: the escape of instance_drain.hip, the grounding of instance_ground.hip.
+// label volume of at most 2^31 entries: instance_reach.hip, for the escape of drainage and the grounding of islands.
 constexpr uint32_t kFlag = 0x80000000u;     // a root's entry: index | kFlag once its component escapes
 
 // an entry as the L2 holds it: flags are set by other workgroups while a kernel runs.  A stale one would cost an atomic or a

@@ -18,7 +18,7 @@
 // whatever other wavefronts do; there is no lock, no flag and no wait for anybody's progress.
 //
 // Stages 1 and 2 are THE ONE LABELLING BODY of label_kernels.hpp, which describes it, wrapped with the predicate of `solid`
-// and every edge (edges = 7, a constant); instance_drain.hip wraps the same body for its layers.
+// and every edge (edges = 7, a constant); instance_reach.hip wraps the same body for its layers.
 //   1 k_comp_local<true>: label_tile, a tile of 8 x 8 x 16 samples labelled in LDS (4 KiB of labels, 256 B of column
 //     masks), every sample united with its three forward neighbours inside the tile; NONE outside S and in the padding.
 //     k_comp_local<false> (the comparison arm) writes label = own index.

@@ -1,6 +1,6 @@
 // codecad_amd/csrc/label_kernels.hpp -- the ONE body of the kernels that LABEL a subset S of the part-id volume by union-find:
-// instance_components.hip (the connected components of S, CompArgs) and instance_drain.hip (the components of every layer of an
-// axis at once, DrainArgs) wrap it in their kernels.  id_volume.hpp has the volume's contract, find and unite;
+// instance_components.hip (the connected components of S, CompArgs) and instance_reach.hip (the components of every layer of an
+// axis at once, ReachArgs) wrap it in their kernels.  id_volume.hpp has the volume's contract, find and unite;
 // instance_components.hip states THE INVARIANT (label[q] <= q, entries only ever fall) and what a label is: until a caller's
 // last kernel the index q = (x * ny + y) * pitch + z of a sample of its own component INTO THE LABEL BUFFER, kNone outside S
 // and in the padding.  Args has labels, nx, ny, nz, pitch and total under these names.

@@ -24,9 +24,10 @@
 //   instance_voxels.hip the part-id volume of an assembly (codecad_amd/assembly_voxels.py), likewise;
 //   instance_gap.hip    the least gap of every pair of parts (codecad_amd/separation.py), likewise; these eight share
 //                 instance_cells.hpp;
-//   instance_components.hip, instance_thickness.hip, instance_overhang.hip, instance_blocking.hip, instance_contacts.hip
+//   instance_components.hip, instance_thickness.hip, instance_overhang.hip, instance_blocking.hip, instance_contacts.hip,
+//   instance_reach.hip
 //                 the kernels that walk the part-id volume (id_volume.hpp): connected components, distance transforms,
-//                 overhangs, which part blocks which, which parts touch;
+//                 overhangs, which part blocks which, which parts touch, and the layer reachability of drainage and islands;
 //   sort.hip, exchange.hip, mesh.hip  the sort of a block list, the exchange step of the multi-GPU levels, marching cubes.
 #pragma once
 

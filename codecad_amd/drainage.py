@@ -38,8 +38,8 @@ on empty space); the transitive grounded-from-the-plate closure of the SOLID, th
 three stages (`islands()`, islands.py, is that caller); whether a pool is a sealed cavity (DESIGN.md section 9.2 says what that would cost; compare `labels` with those
 of `cavities()`); more than 64 instances; several devices.
 
-ON THE DEVICE (csrc/instance_drain.hip), monotone reachability: connected within a layer, handed on from layer to layer in one
-direction only.  `hu_drain_layers` labels the layers' components of E, all layers at once, by the union-find of
+ON THE DEVICE (csrc/instance_reach.hip, driven by _layer_reach.py, both shared with `islands()`), monotone reachability:
+connected within a layer, handed on from layer to layer in one direction only.  `hu_drain_layers` labels the layers' components of E, all layers at once, by the union-find of
 `assembly_components` with the edges of the two lateral axes alone (`local=True` labels tiles in LDS first, `local=False` is
 the comparison arm: the same bytes); `hu_components_flatten` makes every entry its root; `hu_drain_seed` sets bit 31 of a
 root's entry, its ESCAPE FLAG, for every sample in layer 0 or at a lateral border; `hu_drain_rise` is one PASS up every line
@@ -58,6 +58,7 @@ from . import hip_util
 from .assembly_voxels import _device_volume, _axis, _dims, _cropped, _LabelMask, EMPTY
 from .assembly_components import Component, NONE, _components, _label_volume, _check_entries
 from .hip_util import manager as hip_manager, check
+from ._layer_reach import flagged_layers, box_layers
 
 SAMPLE_BYTES = 6                # the ids, the labels and the trapped ids: what is held per sample at the peak
 _COUNTS = (64,)                 # uint64: the trapped samples per floor
@@ -85,7 +86,7 @@ class DrainageReport(_LabelMask, collections.namedtuple("DrainageReport", "insta
 def _pools(rows, voxels, axis, up):
     names = [i.name for i in voxels.instances]
     na = int(voxels.dims[axis])
-    return [Pool(*c, held_by=tuple(names[k] for k in c.parts), level=c.box[1][axis] if up else na - 1 - c.box[0][axis])
+    return [Pool(*c, held_by=tuple(names[k] for k in c.parts), level=box_layers(c.box, na, axis, up)[1])
             for c in _components(rows, voxels.corner, voxels.step)]
 
 
@@ -114,20 +115,14 @@ def drainage(asm, resolution, axis=2, up=True, local=True, initial_components=No
     lib, queue = hip_manager.lib, hip_manager.queue
     nx, ny, pz = volume.shape
     dims = _dims(shape)
-    acc = hip_util.Buffer(numpy.uint64, _COUNTS, queue=queue)
-    check(lib.hu_memset(acc.device_ptr, 0, acc.size, queue.handle), "hu_memset")
-    word = hip_util.Buffer(numpy.uint32, (1,), queue=queue)
-    layers = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
-    check(lib.hu_drain_layers(volume.device_ptr, layers.device_ptr, dims, pz, axis, int(bool(local)), queue.handle), "hu_drain_layers")
-    check(lib.hu_components_flatten(layers.device_ptr, dims, pz, queue.handle), "hu_components_flatten")
-    check(lib.hu_drain_seed(layers.device_ptr, dims, pz, axis, int(up), queue.handle), "hu_drain_seed")
-    passes = 0
-    while True:                                                        # at most n_a + 1 passes: a chain of handovers climbs a layer a link
-        check(lib.hu_memset(word.device_ptr, 0, word.size, queue.handle), "hu_memset")
-        check(lib.hu_drain_rise(layers.device_ptr, word.device_ptr, dims, pz, axis, int(up), queue.handle), "hu_drain_rise")
-        passes += 1
-        if int(word.read()[0]) == 0:
-            break
+
+    def label(acc, layers):
+        check(lib.hu_drain_layers(volume.device_ptr, layers.device_ptr, dims, pz, axis, int(bool(local)), queue.handle), "hu_drain_layers")
+
+    def seed(acc, layers):
+        check(lib.hu_drain_seed(layers.device_ptr, dims, pz, axis, int(up), queue.handle), "hu_drain_seed")
+
+    acc, word, layers, passes = flagged_layers(hip_manager, volume, dims, axis, up, _COUNTS, label, seed)
     trapped = hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue)
     check(lib.hu_drain_floor(volume.device_ptr, layers.device_ptr, trapped.device_ptr, acc.device_ptr, dims, pz, axis, int(up),
                              queue.handle), "hu_drain_floor")

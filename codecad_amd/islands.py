@@ -40,7 +40,7 @@ OUT OF SCOPE.  A lateral reach, so handing on across a diagonal: the 6-neighbour
 an edge do not ground each other; grounding through the supports of `overhangs()`; directions off the lattice axes; more than
 64 instances; several devices.
 
-ON THE DEVICE (csrc/instance_ground.hip, with three stages of csrc/instance_drain.hip's machinery), monotone reachability:
+ON THE DEVICE (csrc/instance_reach.hip, driven by _layer_reach.py, both shared with `drainage()`), monotone reachability:
 connected within a layer, handed on from layer to layer in one direction only.  `hu_overhang_first_layer` raises a device word
 to n_a - h0; `hu_ground_layers` labels the layers' components of S, all layers at once, by the union-find of
 `assembly_components` with the edges of the two lateral axes alone (`local=True` labels tiles in LDS first, `local=False` is
@@ -63,6 +63,7 @@ from . import hip_util
 from .assembly_voxels import _device_volume, _of_code, _axis, _dims, _cropped, _LabelMask, EMPTY
 from .assembly_components import Component, SOLID, NONE, _components, _label_volume, _check_entries
 from .hip_util import manager as hip_manager, check
+from ._layer_reach import flagged_layers, box_layers
 
 SAMPLE_BYTES = 8                # the ids, the labels and the three id volumes: what is held per sample at the peak
 _ACC = (4, 64)                  # uint64: F, A and J per part, then the depth word of hu_overhang_first_layer
@@ -96,7 +97,7 @@ def _islands(rows, voxels, axis, up, labels, start_ids, join_ids):
     order = numpy.array([c.label for c in found], dtype=numpy.uint32)             # ascending: _components sorts by label
     starts = numpy.bincount(numpy.searchsorted(order, labels[start_ids != EMPTY]), minlength=len(found))
     joined = set(numpy.unique(labels[join_ids != EMPTY]).tolist())
-    return [Island(*c, owners=tuple(names[k] for k in c.parts), first_layer=c.box[0][axis] if up else na - 1 - c.box[1][axis],
+    return [Island(*c, owners=tuple(names[k] for k in c.parts), first_layer=box_layers(c.box, na, axis, up)[0],
                    starts=int(starts[k]), loose=c.label not in joined) for k, c in enumerate(found)]
 
 
@@ -141,23 +142,17 @@ def islands(asm, resolution, axis=2, up=True, of=SOLID, local=True, initial_comp
     lib, queue = hip_manager.lib, hip_manager.queue
     nx, ny, pz = volume.shape
     dims = _dims(shape)
-    acc = hip_util.Buffer(numpy.uint64, _ACC, queue=queue)
-    check(lib.hu_memset(acc.device_ptr, 0, acc.size, queue.handle), "hu_memset")
-    depth = acc.device_ptr + _DEPTH
-    word = hip_util.Buffer(numpy.uint32, (1,), queue=queue)              # the changed word of a pass
-    layers = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
-    check(lib.hu_overhang_first_layer(volume.device_ptr, depth, dims, pz, axis, int(up), code, queue.handle), "hu_overhang_first_layer")
-    check(lib.hu_ground_layers(volume.device_ptr, layers.device_ptr, dims, pz, axis, code, int(bool(local)), queue.handle),
-          "hu_ground_layers")
-    check(lib.hu_components_flatten(layers.device_ptr, dims, pz, queue.handle), "hu_components_flatten")
-    check(lib.hu_ground_seed(layers.device_ptr, depth, dims, pz, axis, int(up), queue.handle), "hu_ground_seed")
-    passes = 0
-    while True:                                                        # at most n_a + 1 passes: a chain of handovers climbs a layer a link
-        check(lib.hu_memset(word.device_ptr, 0, word.size, queue.handle), "hu_memset")
-        check(lib.hu_drain_rise(layers.device_ptr, word.device_ptr, dims, pz, axis, int(up), queue.handle), "hu_drain_rise")
-        passes += 1
-        if int(word.read()[0]) == 0:
-            break
+
+    def label(acc, layers):                                               # the depth word lies behind the counters
+        check(lib.hu_overhang_first_layer(volume.device_ptr, acc.device_ptr + _DEPTH, dims, pz, axis, int(up), code, queue.handle),
+              "hu_overhang_first_layer")
+        check(lib.hu_ground_layers(volume.device_ptr, layers.device_ptr, dims, pz, axis, code, int(bool(local)), queue.handle),
+              "hu_ground_layers")
+
+    def seed(acc, layers):
+        check(lib.hu_ground_seed(layers.device_ptr, acc.device_ptr + _DEPTH, dims, pz, axis, int(up), queue.handle), "hu_ground_seed")
+
+    acc, word, layers, passes = flagged_layers(hip_manager, volume, dims, axis, up, _ACC, label, seed)
     floating, start, join = (hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue) for _ in range(3))
     check(lib.hu_ground_mark(volume.device_ptr, layers.device_ptr, floating.device_ptr, start.device_ptr, join.device_ptr,
                              acc.device_ptr, dims, pz, axis, int(up), code, queue.handle), "hu_ground_mark")

@@ -7,7 +7,6 @@ driver over a recording library, the C ABI, the entry points' refusals and the k
 import ctypes
 import os
 import re
-import subprocess
 import sys
 import types
 
@@ -21,6 +20,7 @@ from codecad_amd.hip_util import _lib
 import assembly_components_scenes as comp
 import disassembly_scenes as dis_scenes
 import drainage_scenes as scenes
+import reach_kernels as reach
 from drainage_scenes import SCENES, MINE, CASES, RAW_CASES, DIRECTIONS, reference, raw_reference, scene, EMPTY, NONE
 
 dr = sys.modules["codecad_amd.drainage"]               # (the package's attribute of that name is the function)
@@ -28,8 +28,8 @@ av = sys.modules["codecad_amd.assembly_voxels"]
 ac = sys.modules["codecad_amd.assembly_components"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("hu_drain_layers", "hu_drain_seed", "hu_drain_rise", "hu_drain_floor")
-KERNELS = ("k_drain_local<true>", "k_drain_local<false>", "k_drain_merge_faces", "k_drain_merge_all", "k_drain_seed",
-           "k_drain_rise<false>", "k_drain_rise<true>", "k_drain_floor<false>", "k_drain_floor<true>")
+KERNELS = ("k_reach_local<true>", "k_reach_local<false>", "k_reach_merge_faces", "k_reach_merge_all", "k_drain_seed",
+           "k_reach_rise<false>", "k_reach_rise<true>", "k_drain_floor<false>", "k_drain_floor<true>")
 EVERYTHING = [("scene",) + c for c in CASES] + [("raw",) + c for c in RAW_CASES]
 
 
@@ -396,36 +396,18 @@ def test_the_entry_points_refuse_bad_arguments_without_a_device():
     assert rise(word=None) == -3 and b"NULL" in lib.hu_last_error()
 
 
-def documented_resources():
-    """{kernel: (VGPRs, LDS bytes)} as DESIGN.md section 9.2 states them."""
-    with open(os.path.join(ROOT, "DESIGN.md")) as f:
-        text = f.read()
-    found = {}
-    for name in KERNELS:
-        m = re.search(r"`%s` (\d+) VGPRs and (\d+) B of LDS" % re.escape(name), text)
-        assert m, "DESIGN.md section 9.2 states the VGPRs and the LDS of " + name
-        found[name] = (int(m.group(1)), int(m.group(2)))
-    return found
-
-
-def test_the_kernels_use_no_scratch_and_the_resources_the_design_states(tmp_path):
+def test_the_kernels_use_no_scratch_and_the_resources_the_design_states():
     """Resources only, from the metadata of the unit compiled for gfx950: a private segment of 0 bytes, and the VGPR counts and
-    the LDS written in DESIGN.md; LDS in the tile kernel alone."""
+    the LDS written in DESIGN.md; LDS in the tile kernel alone; every kernel of the unit is held to section 9.2 or 9.3."""
     from codecad_amd.hip_util import builder
-    assert "instance_drain.hip" in builder.SOURCES and "instance_drain.hip" not in builder.FLAGGED_SOURCES
-    with open(os.path.join(builder.CSRC, "instance_drain.hip")) as f:
-        source = f.read()
+    assert reach.UNIT in builder.SOURCES and reach.UNIT not in builder.FLAGGED_SOURCES
+    everything = reach.sources()
+    for gone in ("instance_drain.hip", "instance_ground.hip"):
+        assert gone not in builder.SOURCES and gone not in everything
+    source, shared, labelling, components = (everything[name] for name in (reach.UNIT, "id_volume.hpp", "label_kernels.hpp",
+                                                                           "instance_components.hip"))
     assert '#include "id_volume.hpp"' in source and '#include "label_kernels.hpp"' in source
-    with open(os.path.join(builder.CSRC, "id_volume.hpp")) as f:
-        shared = f.read()
-    with open(os.path.join(builder.CSRC, "label_kernels.hpp")) as f:
-        labelling = f.read()
-    assert '#include "id_volume.hpp"' in labelling
-    with open(os.path.join(builder.CSRC, "instance_components.hip")) as f:
-        components = f.read()
-    assert '#include "label_kernels.hpp"' in components
-    everything = {name: open(os.path.join(builder.CSRC, name)).read() for name in sorted(os.listdir(builder.CSRC))
-                  if name.endswith((".hip", ".hpp", ".h"))}
+    assert '#include "id_volume.hpp"' in labelling and '#include "label_kernels.hpp"' in components
     # one copy of each: find, unite and the line walk in id_volume.hpp; the tile labelling, the merges, the tile's index
     # arithmetic and the grid of a lane per sample in label_kernels.hpp; nothing of them in either unit
     for home, text, functions in (("id_volume.hpp", shared, ("uint32_t find(", "void unite(", "LineUnitOf<I> line_unit(", "uint64_t line_units(")),
@@ -438,24 +420,16 @@ def test_the_kernels_use_no_scratch_and_the_resources_the_design_states(tmp_path
             assert [name for name, other in everything.items() if function in other] == [home], function
     for text in (source, components):                                              # no tile arithmetic, no face ranges
         assert "kTileX" not in text and "kTileZ" not in text and "line * a.segments" not in text and "2^31 entries\"" not in text
-    documented = documented_resources()
-    hipcc = builder.find_hipcc()
-    if hipcc is None:
+    # the unit wraps the one labelling body once: one stage-1 kernel set for every predicate
+    for wrapped in ("label_tile<", "label_merge_faces(", "label_merge_all("):
+        assert source.count(wrapped) == 1, wrapped
+    assert [name for name, other in everything.items() if "k_drain_" in other] == [reach.UNIT]
+    documented = reach.documented_resources(KERNELS)
+    found = reach.compiled_resources()
+    if found is None:
         pytest.skip("no hipcc in this environment")
-    out = tmp_path / "instance_drain.s"
-    flags = [f for f in builder.HIPCC_FLAGS if f != "-fPIC"]
-    subprocess.run([hipcc] + flags + ["-I", builder.INCLUDE, "--cuda-device-only", "-S", "-o", str(out),
-                                      os.path.join(builder.CSRC, "instance_drain.hip")], check=True, capture_output=True)
-    metadata = out.read_text().split(".amdgpu_metadata")[1]
-    found = {}
-    for block in metadata.split("\n  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        m = re.search(r"\d+(k_drain_\w+?)(?:ILb([01])EEEv|E)NS_9DrainArgsE", name)
-        assert m, name
-        kernel = m.group(1) + ("" if m.group(2) is None else "<%s>" % ("false", "true")[int(m.group(2))])
-        assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", block).group(1)) == 0, name
-        found[kernel] = (int(re.search(r"\.vgpr_count:\s*(\d+)", block).group(1)),
-                         int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", block).group(1)))
-    assert found == documented
-    assert {k for k, (_, lds) in found.items() if lds} == {"k_drain_local<true>", "k_drain_local<false>"}
-    assert found["k_drain_local<true>"][1] == 4096 + 256
+    assert set(found) == set(reach.DRAIN) | set(reach.GROUND) and len(found) == 12
+    assert all(private == 0 for _, _, private in found.values()), found
+    assert {k: v[:2] for k, v in found.items() if k in KERNELS} == documented
+    assert {k for k, (_, lds, _) in found.items() if lds} == {"k_reach_local<true>", "k_reach_local<false>"}
+    assert found["k_reach_local<true>"][1] == 4096 + 256

@@ -13,6 +13,7 @@ from codecad_amd import hip_util
 from codecad_amd.hip_util import check
 
 import disassembly_scenes as dis_scenes
+import drainage_scenes
 import islands_scenes as scenes
 from islands_scenes import CASES, RAW_CASES, RAW_PARTS, reference, raw_reference, raw_ids, raw_labels, scene, EMPTY, NONE, SOLID
 
@@ -177,3 +178,51 @@ def test_the_entry_points_alone_on_raw_volumes(hip, name, axis, up, of):
         assert len(wrong) == 0, (field, [(tuple(k), int(got[tuple(k)]), int(want[tuple(k)])) for k in wrong[:8]])
         assert (got[:, :, nz:] == SENTINEL).all(), field
     assert [[int(v) for v in totals[k, :RAW_PARTS]] for k in range(3)] == [ref.floating_counts, ref.start_counts, ref.join_counts]
+
+
+@pytest.mark.parametrize("name", ["two_ids", "19x21x70"])
+def test_stage_one_alone_serves_the_three_predicates_from_one_kernel(hip, name):
+    """hu_drain_layers (id == 255), hu_ground_layers(of=SOLID) (id != 255) and hu_ground_layers(of=k) (id == k) launch one
+    kernel set with two words of its record: the sets that come out labelled are exactly those, on every axis and both arms,
+    the padding poisoned with ids of the set that is asked for."""
+    ids = raw_ids(name)
+    nx, ny, nz = ids.shape
+    lib, queue = hip.lib, hip.queue
+    dims = (ctypes.c_uint32 * 3)(nx, ny, nz)
+    volumes = {}
+    for poison in (0, 1):                                                           # the padding alternates 255 and `poison`
+        padded, pz = padded_ids(ids, poison)
+        volumes[poison] = hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue)
+        volumes[poison].enqueue_write(padded)
+    labels = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
+    # (what to call, the volume it reads, the set by its definition, the layers' components of that set by flood fill)
+    empty = ids == EMPTY
+    predicates = {"empty": (None, 1, empty, lambda axis: drainage_scenes.layer_labels(empty, axis)),
+                  "solid": (255, 1, ids != EMPTY, lambda axis: raw_labels(name, axis, SOLID)),
+                  "of=0": (0, 0, ids == 0, lambda axis: raw_labels(name, axis, 0)),
+                  "of=1": (1, 1, ids == 1, lambda axis: raw_labels(name, axis, 1))}
+    for axis in range(3):
+        for local in (0, 1):
+            for key, (code, poison, want, layer_ref) in predicates.items():
+                volume = volumes[poison]
+                labels.enqueue_fill(SENTINEL)
+                if code is None:
+                    check(lib.hu_drain_layers(volume.device_ptr, labels.device_ptr, dims, pz, axis, local, queue.handle), "hu_drain_layers")
+                else:
+                    check(lib.hu_ground_layers(volume.device_ptr, labels.device_ptr, dims, pz, axis, code, local, queue.handle), "hu_ground_layers")
+                check(lib.hu_components_flatten(labels.device_ptr, dims, pz, queue.handle), "hu_components_flatten")
+                entries = labels.read().copy()
+                got = entries[:, :, :nz] != NONE
+                assert numpy.array_equal(got, want), (key, axis, local)
+                assert (entries[:, :, nz:] == NONE).all(), (key, axis, local)
+                assert numpy.array_equal(linear_of(entries, want, nz), layer_ref(axis)), (key, axis, local)
+    for b in (volumes[0], volumes[1], labels):
+        b.release()
+    # what the four sets are to each other, so that no predicate can stand in for another
+    e, s, zero, one = (predicates[key][2] for key in ("empty", "solid", "of=0", "of=1"))
+    assert (e ^ s).all() and e.any() and s.any()                                    # the first two partition the lattice
+    assert zero.any() and one.any() and not (zero & one).any() and not ((zero | one) & ~s).any()
+    if name == "two_ids":
+        assert numpy.array_equal(zero | one, s)                                     # the last two partition the solid
+    else:
+        assert set(numpy.unique(ids[s]).tolist()) == set(range(64)) and (s & ~(zero | one)).any()

@@ -8,7 +8,6 @@ the C ABI, the entry points' refusals and the kernels' resources."""
 import ctypes
 import os
 import re
-import subprocess
 import sys
 import types
 
@@ -22,6 +21,7 @@ from codecad_amd.hip_util import _lib
 import disassembly_scenes as dis_scenes
 import drainage_scenes
 import overhangs_scenes
+import reach_kernels as reach
 import islands_scenes as scenes
 from islands_scenes import SCENES, MINE, CASES, RAW_CASES, DIRECTIONS, reference, raw_reference, scene, shifted, EMPTY, NONE, SOLID
 
@@ -30,8 +30,7 @@ av = sys.modules["codecad_amd.assembly_voxels"]
 ac = sys.modules["codecad_amd.assembly_components"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("hu_ground_layers", "hu_ground_seed", "hu_ground_mark")
-KERNELS = ("k_ground_local<true>", "k_ground_local<false>", "k_ground_merge_faces", "k_ground_merge_all", "k_ground_seed",
-           "k_ground_mark<false>", "k_ground_mark<true>")
+KERNELS = ("k_ground_seed", "k_ground_mark<false>", "k_ground_mark<true>")
 EVERYTHING = [("scene",) + c for c in CASES] + [("raw",) + c for c in RAW_CASES]
 
 
@@ -424,52 +423,31 @@ def test_the_entry_points_refuse_bad_arguments_without_a_device():
     assert layers(of=64) == -3 and b"HU_OVERHANG_SOLID" in lib.hu_last_error()
 
 
-def documented_resources():
-    """{kernel: (VGPRs, LDS bytes)} as DESIGN.md section 9.3 states them."""
-    with open(os.path.join(ROOT, "DESIGN.md")) as f:
-        text = f.read()
-    found = {}
-    for name in KERNELS:
-        m = re.search(r"`%s` (\d+) VGPRs and (\d+) B of LDS" % re.escape(name), text)
-        assert m, "DESIGN.md section 9.3 states the VGPRs and the LDS of " + name
-        found[name] = (int(m.group(1)), int(m.group(2)))
-    return found
-
-
-def test_the_kernels_use_no_scratch_and_the_resources_the_design_states(tmp_path):
+def test_the_kernels_use_no_scratch_and_the_resources_the_design_states():
     """Resources only, from the metadata of the unit compiled for gfx950: a private segment of 0 bytes, and the VGPR counts and
-    the LDS written in DESIGN.md; LDS in the tile kernel alone; the moved helpers once, in id_volume.hpp."""
+    the LDS written in DESIGN.md; no LDS in the kernels islands() adds; the moved helpers once, in id_volume.hpp."""
     from codecad_amd.hip_util import builder
-    assert "instance_ground.hip" in builder.SOURCES and "instance_ground.hip" not in builder.FLAGGED_SOURCES
-    everything = {name: open(os.path.join(builder.CSRC, name)).read() for name in sorted(os.listdir(builder.CSRC))
-                  if name.endswith((".hip", ".hpp", ".h"))}
-    source = everything["instance_ground.hip"]
+    assert reach.UNIT in builder.SOURCES and reach.UNIT not in builder.FLAGGED_SOURCES
+    everything = reach.sources()
+    assert "instance_ground.hip" not in everything and not os.path.exists(os.path.join(builder.CSRC, "instance_ground.hip"))
+    source = everything[reach.UNIT]
     assert '#include "id_volume.hpp"' in source and '#include "label_kernels.hpp"' in source
     for function in ("constexpr uint32_t kFlag = 0x80000000u", "uint32_t live(", "bool escapes(", "bool raise("):
         assert [name for name, other in everything.items() if function in other] == ["id_volume.hpp"], function
         assert everything["id_volume.hpp"].count(function) == 1, function
     for helper in ("escapes(", "raise<", "label_tile<", "label_merge_faces(", "label_merge_all(", "gather_counts(", "line_unit<"):
         assert helper in source, helper
-    assert "k_drain" not in source.split("#include")[-1] and "hipMemset" not in source and "__shared__" not in source
-    assert [name for name, other in everything.items() if "k_ground_" in other] == ["instance_ground.hip"]
-    documented = documented_resources()
-    hipcc = builder.find_hipcc()
-    if hipcc is None:
+    for wrapped in ("label_tile<", "label_merge_faces(", "label_merge_all("):       # one stage-1 kernel set for every predicate
+        assert source.count(wrapped) == 1, wrapped
+    assert "hipMemset" not in source and "__shared__" not in source
+    assert "__shared__" not in everything["id_volume.hpp"] and "__shared__" in everything["label_kernels.hpp"]
+    for prefix in ("k_ground_", "k_drain_"):
+        assert [name for name, other in everything.items() if prefix in other] == [reach.UNIT], prefix
+    documented = reach.documented_resources(KERNELS)
+    found = reach.compiled_resources()
+    if found is None:
         pytest.skip("no hipcc in this environment")
-    out = tmp_path / "instance_ground.s"
-    flags = [f for f in builder.HIPCC_FLAGS if f != "-fPIC"]
-    subprocess.run([hipcc] + flags + ["-I", builder.INCLUDE, "--cuda-device-only", "-S", "-o", str(out),
-                                      os.path.join(builder.CSRC, "instance_ground.hip")], check=True, capture_output=True)
-    metadata = out.read_text().split(".amdgpu_metadata")[1]
-    found = {}
-    for block in metadata.split("\n  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        m = re.search(r"\d+(k_ground_\w+?)(?:ILb([01])EEEv|E)NS_10GroundArgsE", name)
-        assert m, name
-        kernel = m.group(1) + ("" if m.group(2) is None else "<%s>" % ("false", "true")[int(m.group(2))])
-        assert int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", block).group(1)) == 0, name
-        found[kernel] = (int(re.search(r"\.vgpr_count:\s*(\d+)", block).group(1)),
-                         int(re.search(r"\.group_segment_fixed_size:\s*(\d+)", block).group(1)))
-    assert found == documented
-    assert {k for k, (_, lds) in found.items() if lds} == {"k_ground_local<true>", "k_ground_local<false>"}
-    assert found["k_ground_local<true>"][1] == 4096 + 256
+    assert set(KERNELS) == set(reach.GROUND) and set(found) == set(reach.DRAIN) | set(reach.GROUND)
+    assert all(private == 0 for _, _, private in found.values()), found
+    assert {k: v[:2] for k, v in found.items() if k in KERNELS} == documented
+    assert not any(found[k][1] for k in KERNELS)

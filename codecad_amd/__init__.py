@@ -35,7 +35,11 @@ blind holes, U-bends, pockets between parts --, on which parts each pool stands 
 layers and a scan with a carry along the lattice lines on the device (drainage.py);
 `islands(asm, resolution, axis, up, of)` says what a print along a lattice axis starts in mid-air -- a peg hanging from a
 ceiling, the short leg of an arch, a captive ball --, where each island starts, where it is finally joined from above and
-which islands stay loose, by grounding the solid from the plate with the same layer labelling and scans (islands.py).
+which islands stay loose, by grounding the solid from the plate with the same layer labelling and scans (islands.py);
+`tool_access(asm, resolution, axis, up, tool, of)` says what a 3-axis cutter with its spindle along a lattice axis cannot
+remove -- undercuts, and what is in view but too narrow for the tool: inside corners, slots, the fillet of a ball nose --,
+which part holds or crowds each pocket of it, and the drop-cutter surface of the tool (`flat_tool`, `ball_tool`, `Tool`), by a
+grey-scale closing of the height field of that volume between two scans of it on the device (tool_access.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -67,6 +71,7 @@ from .disassembly import disassembly, DisassemblyReport  # noqa: F401
 from .contacts import contacts, ContactReport  # noqa: F401
 from .drainage import drainage, DrainageReport, Pool  # noqa: F401
 from .islands import islands, IslandReport, Island  # noqa: F401
+from .tool_access import tool_access, ToolAccessReport, Tool, flat_tool, ball_tool  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
@@ -76,4 +81,4 @@ __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "m
            "assembly_components", "cavities", "ComponentsReport", "CavityReport", "Component", "Cavity", "EMPTY_SPACE", "SOLID",
            "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport",
            "contacts", "ContactReport", "drainage", "DrainageReport", "Pool", "islands",
-           "IslandReport", "Island"]
+           "IslandReport", "Island", "tool_access", "ToolAccessReport", "Tool", "flat_tool", "ball_tool"]

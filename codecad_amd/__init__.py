@@ -39,7 +39,10 @@ which islands stay loose, by grounding the solid from the plate with the same la
 `tool_access(asm, resolution, axis, up, tool, of)` says what a 3-axis cutter with its spindle along a lattice axis cannot
 remove -- undercuts, and what is in view but too narrow for the tool: inside corners, slots, the fillet of a ball nose --,
 which part holds or crowds each pocket of it, and the drop-cutter surface of the tool (`flat_tool`, `ball_tool`, `Tool`), by a
-grey-scale closing of the height field of that volume between two scans of it on the device (tool_access.py).
+grey-scale closing of the height field of that volume between two scans of it on the device (tool_access.py);
+`wall_thickness(asm, resolution, max_thickness, of)` says how thick the solid is at every sample -- the greatest ball inside it
+that contains the sample, up to a cap -- and per part the thinnest spot and where it is, by the distance transform of
+`thin_walls` and one dense gather over tiles on the device (wall_thickness.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -72,6 +75,7 @@ from .contacts import contacts, ContactReport  # noqa: F401
 from .drainage import drainage, DrainageReport, Pool  # noqa: F401
 from .islands import islands, IslandReport, Island  # noqa: F401
 from .tool_access import tool_access, ToolAccessReport, Tool, flat_tool, ball_tool  # noqa: F401
+from .wall_thickness import wall_thickness, WallThicknessReport  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
@@ -81,4 +85,5 @@ __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "m
            "assembly_components", "cavities", "ComponentsReport", "CavityReport", "Component", "Cavity", "EMPTY_SPACE", "SOLID",
            "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport",
            "contacts", "ContactReport", "drainage", "DrainageReport", "Pool", "islands",
-           "IslandReport", "Island", "tool_access", "ToolAccessReport", "Tool", "flat_tool", "ball_tool"]
+           "IslandReport", "Island", "tool_access", "ToolAccessReport", "Tool", "flat_tool", "ball_tool",
+           "wall_thickness", "WallThicknessReport"]

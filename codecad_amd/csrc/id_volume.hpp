@@ -5,7 +5,8 @@
 // PADDING z in [nz, pitch) is never read as data.  Every dimension is at most 65536, so the volume may hold 2^48 bytes: BYTE
 // OFFSETS ARE 64-BIT.  Nothing outside the lattice is inside any part.  A kernel takes the lattice in its argument struct as
 // uint32 nx, ny, nz, pitch and, where it walks units, segments and na, under these names: the structs keep their own layout (the
-// order of a kernel's arguments decides how its scalar loads pair up).  Lanes lie along z; workgroups are four wavefronts.
+// order of a kernel's arguments decides how its scalar loads pair up).  Lanes lie along z; workgroups are four wavefronts
+// (but for instance_local.hip's kernels over wide windows, which take 8 and 16 to keep a compute unit's wavefronts up).
 #pragma once
 
 #include "instance_cells.hpp"

@@ -102,6 +102,7 @@ PROTOTYPES = {
     "hu_components_finish": [_vp, _u3, _u32, _vp],
     "hu_thickness_pass_z": [_vp, _vp, _vp, _u3, _u32, _u32, _u32, _u32, _u32, _i, _vp],
     "hu_thickness_pass_axis": [_vp, _vp, _vp, _vp, _vp, _u3, _u32, _i, _u32, _u32, _u32, _u32, _i, _u32, _i, _vp],
+    "hu_thickness_local": [_vp, _vp, _vp, _vp, _vp, _u3, _u32, _u32, _u32, _i, _vp],
     "hu_overhang_first_layer": [_vp, _vp, _u3, _u32, _i, _i, _u32, _vp],
     "hu_overhang_mark": [_vp, _vp, _vp, _vp, _u3, _u32, _i, _i, _u32, _u32, _vp],
     "hu_overhang_columns": [_vp, _vp, _vp, _vp, _vp, _vp, _u3, _u32, _i, _i, _u32, _vp],

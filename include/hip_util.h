@@ -432,6 +432,28 @@ int hu_thickness_pass_axis(const void* in_dev, void* out_dev, const void* ids_de
                            const uint32_t dims[3], uint32_t pitch, int axis, uint32_t of, uint32_t K, uint32_t cap,
                            uint32_t outside, int finish, uint32_t tile, int lds, void* stream);
 
+/* ---- the local thickness of a field on the part-id volume (codecad_amd/wall_thickness.py) --------
+ * hu_thickness_local: over depth_dev and out_dev, uint16[dims[0]][dims[1]][pitch], and the id volume ids_dev of that shape, all
+ *   still on the device; S as above.  in(q) = depth_dev[q] for q in S inside the lattice, 0 for every other point, whatever is
+ *   stored there, and at most radius_sq + 1 (the caller's to ensure).  For a sample p of S with in(p) > 0
+ *       out(p) = the greatest in(q) over the q with |p - q|^2 < in(q)          (q = p qualifies: out >= in),
+ *   and out(p) = 0 on every other sample of the lattice; the padding z in [dims[2], pitch) is neither read nor written.  On
+ *   the capped squared distance to the background (the x pass of transform 1, finish == 1) this is the greatest capped
+ *   inscribed ball over every sample.  keys_dev (64 uint64, the caller's all ones): [p] is lowered to the least
+ *   out << 48 | x << 32 | y << 16 | z over the samples of id p with out > 0.  counts_dev (64 uint64, the caller's zeros): [p] +=
+ *   the samples of id p with out == radius_sq + 1.  One atomic per accumulator, wavefront and part.  A workgroup takes a tile
+ *   of HU_COMPONENTS_TILE_X x _Y x _Z samples; lds != 0 stages the tile and a halo of K = isqrt(radius_sq), or of the reach of
+ *   the greatest value around the tile where that is less, in LDS while that halo is at most HU_LOCAL_LDS_K (at most
+ *   HU_LOCAL_LDS_BYTES a workgroup); beyond that, and with lds == 0, every tap comes from global memory: the same bytes.
+ *   Asynchronous; allocates nothing.  Checked before a device is touched (HU_ERR_BAD_ARG): NULL pointers, the pitch, the dims
+ *   and `of` as above, radius_sq above HU_LOCAL_MAX_RADIUS_SQ, volumes not aligned to 2 bytes, keys or counts not to 8,
+ *   depth_dev == out_dev. */
+#define HU_LOCAL_MAX_RADIUS_SQ 1024
+#define HU_LOCAL_LDS_K 16
+#define HU_LOCAL_LDS_BYTES 153664
+int hu_thickness_local(const void* depth_dev, const void* ids_dev, void* out_dev, uint64_t* keys_dev, uint64_t* counts_dev,
+                       const uint32_t dims[3], uint32_t pitch, uint32_t of, uint32_t radius_sq, int lds, void* stream);
+
 /* ---- what a print direction leaves in the air (codecad_amd/overhangs.py) -----------------------
  * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device.  S is the samples with id != 255
  * (of == HU_OVERHANG_SOLID) or id == of (of <= 63); nothing outside the lattice is in S, and the padding z in [dims[2], pitch)

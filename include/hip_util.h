@@ -527,8 +527,8 @@ int hu_contact_faces(const void* ids_dev, void* contact_ids_dev /* may be NULL *
                      const uint32_t dims[3], uint32_t pitch, uint32_t n, void* stream);
 
 /* ---- what an assembly holds when drained along a lattice axis (codecad_amd/drainage.py) ----------
- * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, aligned to 16 bytes: E is its samples
- * z < dims[2] with id == 255, S those with another id; nothing outside the lattice is in S, and the padding z in [dims[2], pitch)
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, aligned to 16 bytes for hu_drain_layers: E is
+ * its samples z < dims[2] with id == 255, S those with another id; nothing outside the lattice is in S, and the padding z in [dims[2], pitch)
  * of any volume is neither read nor written as data.  Up runs along `axis` (up != 0: the layer of a sample is its index on that
  * axis; else dims[axis] - 1 - index), "below" is one layer less, the other two axes are the lateral ones.  labels_dev is
  * uint32[dims[0]][dims[1]][pitch], aligned to 4 bytes, dims[0] * dims[1] * pitch at most 2^31, under the invariant of the
@@ -549,7 +549,8 @@ int hu_contact_faces(const void* ids_dev, void* contact_ids_dev /* may be NULL *
  *   255).  One atomic per accumulator and wavefront.
  * All allocate nothing and synchronise nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL
  * pointers, a pitch that is no multiple of 16 or below dims[2], dims of 0 or above 65536, an axis outside 0..2, more than 2^31
- * entries, ids not aligned to 16, labels or the word not to 4 or counts not to 8 bytes. */
+ * entries, ids not aligned to 16 (hu_drain_layers alone: hu_drain_floor reads bytes and takes ids_dev at any address), labels or
+ * the word not to 4 or counts not to 8 bytes. */
 int hu_drain_layers(const void* ids_dev, void* labels_dev, const uint32_t dims[3], uint32_t pitch, int axis, int local,
                     void* stream);
 int hu_drain_seed(void* labels_dev, const uint32_t dims[3], uint32_t pitch, int axis, int up, void* stream);

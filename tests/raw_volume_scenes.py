@@ -4,7 +4,8 @@ test_gpu_overhang_raw.py, test_gpu_components_raw.py).  test_raw_volumes_host.py
 edge it is named for.  Everything is seeded; the references are those of thin_walls_scenes, disassembly_scenes,
 overhangs_scenes and assembly_components_scenes, which take raw ids.
 
-A device buffer is uint8 (or uint16) [nx][ny][ceil16(nz)]; the PADDING z in [nz, pz) belongs to nobody.  `padded` and
+A device buffer is uint8 (or uint16) [nx][ny][pz], pz = ceil16(nz) unless a caller asks for a wider pitch (pitched_buffers.py);
+the PADDING z in [nz, pz) belongs to nobody.  `padded` and
 `padded16` fill it with a POISON chosen per consumer: values that would change the consumer's answer if a kernel read them as
 data."""
 import collections
@@ -29,9 +30,10 @@ def code(of):
     return SOLID_CODE if of == SOLID else int(of)
 
 
-def _fill(dtype, values, poison):
+def _fill(dtype, values, poison, pitch=None):
     nx, ny, nz = values.shape
-    pz = ceil16(nz)
+    pz = ceil16(nz) if pitch is None else int(pitch)
+    assert pz % 16 == 0 and nz <= pz <= 65536
     out = numpy.empty((nx, ny, pz), dtype=dtype)
     out[:, :, :nz] = values
     if pz > nz:
@@ -40,14 +42,15 @@ def _fill(dtype, values, poison):
     return out, pz
 
 
-def padded(ids, poison):
-    """(uint8[nx][ny][ceil16(nz)], pz): `ids`, and poison(x, y, z) (index arrays -> values) in the padding."""
-    return _fill(numpy.uint8, ids, poison)
+def padded(ids, poison, pitch=None):
+    """(uint8[nx][ny][pz], pz): `ids`, and poison(x, y, z) (index arrays -> values) over the whole padding [nz, pz); pz is
+    `pitch`, any multiple of 16 from nz on, or ceil16(nz) without one."""
+    return _fill(numpy.uint8, ids, poison, pitch)
 
 
-def padded16(values, fill):
+def padded16(values, fill, pitch=None):
     """The same for a uint16 volume."""
-    return _fill(numpy.uint16, values, fill)
+    return _fill(numpy.uint16, values, fill, pitch)
 
 
 def alternating(a, b):
@@ -209,6 +212,7 @@ def planted_far_tap(n, K, cap, outside):
     return False
 
 
+AXIS_COUNTED_POISON = constant(65535)           # under a finishing pass: as data it reaches every cap and is counted
 FINISH_PARAMS = ((10, 200, 236, 1), (96, 12000, 64, 1), (97, 12000, 64, 0))          # (K, cap, tile, lds) on x300
 FINISH_OFS = (SOLID, 63)
 
@@ -364,6 +368,17 @@ def over_ids(name):
 @functools.lru_cache(maxsize=None)
 def over_reference(name, axis, up, reach_sq, of):
     return over.reference_overhangs(over_ids(name), axis, up, reach_sq, of, 64)
+
+
+# ---- the reach kernels and hu_contact_faces ---------------------------------------------------------------------------------
+
+DRAIN_POISON = alternating(63, EMPTY)           # read as data, it would open ways out and lay floors
+CONTACT_POISON = alternating(0, 1)              # ... it would make contacts
+
+
+def ground_poison(of):
+    """Empty and an id of S: read as data, it would ground, join and close starts."""
+    return alternating(63 if of == SOLID else of, EMPTY)
 
 
 # ---- the component kernels ---------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ from codecad_amd.hip_util import check
 
 import contacts_scenes as scenes
 import disassembly_scenes as dis_scenes
+import raw_volume_scenes as raw
 from contacts_scenes import SCENES, NAMES, RAW_NAMES, RAW_PARTS, reference, raw_reference, raw_ids, scene, EMPTY, NONE
 
 pytestmark = pytest.mark.gpu
@@ -113,15 +114,12 @@ def test_a_face_is_a_distance_of_one_on_the_device(hip, name):
         assert other.contacts(axis) == [(int(i), int(j)) for i, j in numpy.argwhere(touching[axis])]
 
 
-def raw_call(hip, name, with_contact_ids):
-    """hu_contact_faces alone over a raw volume in a buffer of pitch ceil16(nz) whose padding alternates 0 and 1 -> the tables
-    as contacts() decodes them, and the output buffer, which was filled with SENTINEL."""
+def raw_call(hip, name, with_contact_ids, pitch=None):
+    """hu_contact_faces alone over a raw volume in a buffer of pitch `pitch`, ceil16(nz) without one, whose padding alternates 0
+    and 1 -> the tables as contacts() decodes them, and the output buffer, which was filled with SENTINEL."""
     ids = raw_ids(name)
     nx, ny, nz = ids.shape
-    pz = -(-nz // 16) * 16
-    padded = numpy.empty((nx, ny, pz), dtype=numpy.uint8)
-    padded[:, :, :nz] = ids
-    padded[:, :, nz:] = (numpy.arange(nz, pz) + numpy.arange(nx)[:, None, None] + numpy.arange(ny)[None, :, None]) % 2     # would make contacts
+    padded, pz = raw.padded(ids, raw.CONTACT_POISON, pitch)                        # would make contacts
     lib, queue = hip.lib, hip.queue
     volume, out = (hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue) for _ in range(2))
     volume.enqueue_write(padded)

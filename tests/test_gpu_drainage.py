@@ -13,6 +13,7 @@ from codecad_amd.hip_util import check
 
 import disassembly_scenes as dis_scenes
 import drainage_scenes as scenes
+import raw_volume_scenes as raw
 from drainage_scenes import CASES, RAW_CASES, RAW_PARTS, reference, raw_reference, raw_ids, raw_labels, scene, EMPTY, NONE
 
 pytestmark = pytest.mark.gpu
@@ -84,15 +85,10 @@ def test_the_empty_assembly_launches_nothing(hip):
 
 # ---- the entry points alone ---------------------------------------------------------------------------------------------
 
-def padded_ids(ids):
-    """The volume in a buffer of pitch ceil16(nz) whose padding alternates empty and solid: read as data, it would open ways out
-    and lay floors."""
-    nx, ny, nz = ids.shape
-    pz = -(-nz // 16) * 16
-    out = numpy.empty((nx, ny, pz), dtype=numpy.uint8)
-    out[:, :, :nz] = ids
-    out[:, :, nz:] = numpy.where((numpy.arange(nz, pz) + numpy.arange(nx)[:, None, None] + numpy.arange(ny)[None, :, None]) % 2, EMPTY, 63)
-    return out, pz
+def padded_ids(ids, pitch=None):
+    """The volume in a buffer of pitch `pitch`, ceil16(nz) without one, whose padding alternates empty and solid: read as data,
+    it would open ways out and lay floors."""
+    return raw.padded(ids, raw.DRAIN_POISON, pitch)
 
 
 def flagged_of(entries, empty, nz):

@@ -15,6 +15,7 @@ from codecad_amd.hip_util import check
 import disassembly_scenes as dis_scenes
 import drainage_scenes
 import islands_scenes as scenes
+import raw_volume_scenes as raw
 from islands_scenes import CASES, RAW_CASES, RAW_PARTS, reference, raw_reference, raw_ids, raw_labels, scene, EMPTY, NONE, SOLID
 
 pytestmark = pytest.mark.gpu
@@ -87,16 +88,10 @@ def test_the_empty_assembly_launches_nothing(hip):
 
 # ---- the entry points alone ---------------------------------------------------------------------------------------------
 
-def padded_ids(ids, of):
-    """The volume in a buffer of pitch ceil16(nz) whose padding alternates empty and an id of S: read as data, it would ground,
-    join and close starts."""
-    nx, ny, nz = ids.shape
-    pz = -(-nz // 16) * 16
-    out = numpy.empty((nx, ny, pz), dtype=numpy.uint8)
-    out[:, :, :nz] = ids
-    out[:, :, nz:] = numpy.where((numpy.arange(nz, pz) + numpy.arange(nx)[:, None, None] + numpy.arange(ny)[None, :, None]) % 2, EMPTY,
-                                 63 if of == SOLID else of)
-    return out, pz
+def padded_ids(ids, of, pitch=None):
+    """The volume in a buffer of pitch `pitch`, ceil16(nz) without one, whose padding alternates empty and an id of S: read as
+    data, it would ground, join and close starts."""
+    return raw.padded(ids, raw.ground_poison(of), pitch)
 
 
 def flagged_of(entries, s, nz):

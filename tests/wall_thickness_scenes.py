@@ -295,13 +295,14 @@ RAW_NAMES = [c.name for c in RAW_CASES]
 LOW_NAMES = [n for n in RAW_NAMES if n.startswith("low_")]
 
 
-def raw_buffers(case):
+def raw_buffers(case, pitch=None):
     """(ids uint8[nx][ny][pz], field uint16[nx][ny][pz], pz) as the device takes them, POISONED: the padding of the ids lies in
-    S, the padding of the field and its entries outside S hold the cap -- read as data, each would raise a neighbour's answer."""
+    S, the padding of the field and its entries outside S hold the cap -- read as data, each would raise a neighbour's answer.
+    pz is `pitch`, or ceil16(nz) without one."""
     cap = case.r2 + 1
     s = in_set_of(case.ids, case.of)
-    ids, pz = raw.padded(case.ids, raw.constant(0 if case.of == SOLID else case.of))
-    field, _ = raw.padded16(numpy.where(s, case.field, cap), raw.constant(cap))
+    ids, pz = raw.padded(case.ids, raw.constant(0 if case.of == SOLID else case.of), pitch)
+    field, _ = raw.padded16(numpy.where(s, case.field, cap), raw.constant(cap), pitch)
     return ids, field, pz
 
 

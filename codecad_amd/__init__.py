@@ -42,7 +42,11 @@ which part holds or crowds each pocket of it, and the drop-cutter surface of the
 grey-scale closing of the height field of that volume between two scans of it on the device (tool_access.py);
 `wall_thickness(asm, resolution, max_thickness, of)` says how thick the solid is at every sample -- the greatest ball inside it
 that contains the sample, up to a cap -- and per part the thinnest spot and where it is, by the distance transform of
-`thin_walls` and one dense gather over tiles on the device (wall_thickness.py).
+`thin_walls` and one dense gather over tiles on the device (wall_thickness.py);
+`flow_length(asm, resolution, source, of)` says how far it is through the material from gates, from the plate or from the
+lattice's rim (`Gates`, `Samples`, `Plate`, `BORDER`) -- the flow length of a moulding, the way out of a channel -- and per
+part the sample that is reached last, by a min-plus relaxation along the lattice lines that is repeated on the device until it
+changes nothing (flow_length.py).
 The CLI is out of scope.  Importing the package does not touch the GPU; the first kernel launch does,
 and raises if the HIP library or a device is missing -- there is no CPU fallback.
 """
@@ -76,6 +80,7 @@ from .drainage import drainage, DrainageReport, Pool  # noqa: F401
 from .islands import islands, IslandReport, Island  # noqa: F401
 from .tool_access import tool_access, ToolAccessReport, Tool, flat_tool, ball_tool  # noqa: F401
 from .wall_thickness import wall_thickness, WallThicknessReport  # noqa: F401
+from .flow_length import flow_length, FlowLengthReport, Gates, Samples, Plate, BORDER  # noqa: F401
 
 __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "mass_properties",
            "MassProperties", "examples", "assembly", "interference", "InterferenceReport", "clearance",
@@ -86,4 +91,4 @@ __all__ = ["util", "nodes", "shapes", "hip_util", "grid_eval", "subdivision", "m
            "thin_walls", "ThinWallReport", "overhangs", "OverhangReport", "disassembly", "DisassemblyReport",
            "contacts", "ContactReport", "drainage", "DrainageReport", "Pool", "islands",
            "IslandReport", "Island", "tool_access", "ToolAccessReport", "Tool", "flat_tool", "ball_tool",
-           "wall_thickness", "WallThicknessReport"]
+           "wall_thickness", "WallThicknessReport", "flow_length", "FlowLengthReport", "Gates", "Samples", "Plate", "BORDER"]

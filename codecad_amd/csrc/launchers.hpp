@@ -25,11 +25,12 @@
 //   instance_gap.hip    the least gap of every pair of parts (codecad_amd/separation.py), likewise; these eight share
 //                 instance_cells.hpp;
 //   instance_components.hip, instance_thickness.hip, instance_overhang.hip, instance_blocking.hip, instance_contacts.hip,
-//   instance_reach.hip, instance_tool.hip, instance_local.hip
+//   instance_reach.hip, instance_tool.hip, instance_local.hip, instance_geodesic.hip
 //                 the kernels that walk the part-id volume (id_volume.hpp): connected components, distance transforms,
 //                 overhangs, which part blocks which, which parts touch, the layer reachability of drainage and islands,
-//                 what a cutter along an axis cannot reach (with a 2D morphology stage between its two scans), and the local
-//                 thickness (the greatest inscribed ball over every sample, a 3D gather over tiles);
+//                 what a cutter along an axis cannot reach (with a 2D morphology stage between its two scans), the local
+//                 thickness (the greatest inscribed ball over every sample, a 3D gather over tiles), and the shortest paths
+//                 inside a set (a min-plus relaxation along the lines of the axes, repeated until it changes nothing);
 //   sort.hip, exchange.hip, mesh.hip  the sort of a block list, the exchange step of the multi-GPU levels, marching cubes.
 #pragma once
 

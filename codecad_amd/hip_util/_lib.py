@@ -119,6 +119,9 @@ PROTOTYPES = {
     "hu_tool_dilate": [_vp, _vp, _vp, _u32, _u32, _u32, _vp],
     "hu_tool_erode": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp],
     "hu_tool_rest": [_vp, _vp, _vp, _vp, _vp, _u3, _u32, _i, _i, _u32, _vp],
+    "hu_geodesic_seed": [_vp, _vp, _u3, _u32, _u32, _i, _i, _u32, _vp, _u32, _vp],
+    "hu_geodesic_sweep": [_vp, _vp, _vp, _u3, _u32, _i, _u32, _vp],
+    "hu_geodesic_stats": [_vp, _vp, _vp, _vp, _u3, _u32, _u32, _vp],
     "hu_ray_caster": [_vp, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp],
     "hu_ray_caster_instances": [_vp, _u32, _i, _u32, _f4, _f4, _f4, _f4, _f, _f, _f, _f, _f, _u32, _u32, _u32, _vp, _vp, _vp, _vp,
                                 _u32, _vp, _vp],

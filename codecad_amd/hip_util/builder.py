@@ -15,7 +15,7 @@ SOURCES = ["hip_util.hip", "tape_build.hip", "render.hip", "sort.hip", "exchange
            "instance_rays.hip", "instance_section.hip", "instance_outline.hip", "instance_layers.hip", "instance_mass.hip",
            "instance_mesh.hip", "instance_voxels.hip", "instance_gap.hip", "instance_components.hip",
            "instance_thickness.hip", "instance_overhang.hip", "instance_blocking.hip", "instance_contacts.hip",
-           "instance_reach.hip", "instance_tool.hip", "instance_local.hip"]
+           "instance_reach.hip", "instance_tool.hip", "instance_local.hip", "instance_geodesic.hip"]
 
 
 def headers():
@@ -44,7 +44,8 @@ HIPCC_FLAGS = [
 # part-id volume (instance_voxels.hip), the least gap of its pairs (instance_gap.hip), the connected components of the
 # volume (instance_components.hip), its distance transforms (instance_thickness.hip), its overhangs along a print direction
 # (instance_overhang.hip), which part blocks which along the axes (instance_blocking.hip) which parts touch (instance_contacts.hip), what the assembly holds when drained
-# and what a print of it starts in mid-air (both instance_reach.hip), what a cutter along an axis cannot reach (instance_tool.hip), the local thickness of its walls (instance_local.hip) -- is built without it, each unit with the entry points of its kernels; so is tape_build.hip, the host-only build of a tape's
+# and what a print of it starts in mid-air (both instance_reach.hip), what a cutter along an axis cannot reach (instance_tool.hip), the local thickness of its walls (instance_local.hip), the
+# shortest paths inside it (instance_geodesic.hip) -- is built without it, each unit with the entry points of its kernels; so is tape_build.hip, the host-only build of a tape's
 # own kernels (hipRTC, the on-disk cache, the precompiled header), which holds no kernel at all.
 # tests/test_hip_util_host.py checks both halves of that from the ISA: which kernels the flagged object holds, and that
 # its loops have the shape described here.

@@ -624,6 +624,50 @@ int hu_tool_erode(const uint32_t* tips_dev, const uint32_t* tops_dev, const uint
 int hu_tool_rest(const void* ids_dev, const uint32_t* tops_dev, const uint32_t* cut_dev, void* rest_dev, uint64_t* counts_dev,
                  const uint32_t dims[3], uint32_t pitch, int axis, int up, uint32_t of, void* stream);
 
+/* ---- shortest paths inside a set of the part-id volume (codecad_amd/flow_length.py) --------------
+ * Over the id volume ids_dev, uint8[dims[0]][dims[1]][pitch], still on the device, at any address: S is its samples z < dims[2]
+ * with id != 255 (of == HU_GEODESIC_SOLID), id == of (of <= 63) or id == 255 (of == HU_GEODESIC_EMPTY, this section's own code);
+ * nothing outside the lattice is in S, and the padding z in [dims[2], pitch) of any volume is neither read nor written.  A STEP
+ * joins two 6-neighbours that are both in S.  dist_dev is uint32[dims[0]][dims[1]][pitch], aligned to 4 bytes, dims[0] * dims[1]
+ * * pitch at most 2^31: d of a sample, HU_GEODESIC_NONE where no seed reaches it and outside S.  The calls are made in this order
+ * on one stream:
+ * hu_geodesic_seed: writes EVERY in-lattice entry of dist_dev: 0 on a seed that is in S, HU_GEODESIC_NONE elsewhere.  The seeds
+ *   are, by `mode`: HU_GEODESIC_BORDER the samples with an index of 0 or dims - 1 on some axis; HU_GEODESIC_LAYER those whose
+ *   index on `axis` is `layer`; HU_GEODESIC_LIST the n_samples samples {x, y, z} of samples_dev, uint32[n_samples][3] on the
+ *   device, aligned to 4 bytes (one outside the lattice or not in S seeds nothing: the caller's to refuse).  `axis` and `layer`
+ *   are read under HU_GEODESIC_LAYER only, samples_dev and n_samples under HU_GEODESIC_LIST only.
+ * hu_geodesic_sweep: one SWEEP: along every line of `axis` a forward walk and then a backward walk of the whole line.  The carry
+ *   c is HU_GEODESIC_NONE at the start of a walk and after a sample outside S; on a sample of S v = min(dist, c + 1), the sum
+ *   saturating at HU_GEODESIC_NONE, is stored where it is lower than dist, and c = v.  Entries outside S are neither read as data
+ *   nor written.  The lines of an axis share no entry: the bytes after a call are those of the plain walks, whatever ran when.
+ *   *word_dev (aligned to 4 bytes; the caller zeroes it) becomes nonzero when any entry was lowered, by at most one store per
+ *   wavefront.  The caller repeats ROUNDS of three sweeps (axis 2, 1, 0 on one word) until a round leaves its word zero: dist is
+ *   then the least number of steps from a seed, on every sample of S that a seed reaches.
+ * hu_geodesic_stats: counts_dev, uint64[3][HU_GEODESIC_SLOTS], the caller's zeros: [0][p] += the samples of S with id p and
+ *   d != HU_GEODESIC_NONE, [1][p] += those with d == HU_GEODESIC_NONE, [2][p] += the sum of d over the former; keys_dev,
+ *   uint64[HU_GEODESIC_SLOTS], the caller's zeros: [p] is raised by a 64-bit atomic maximum to the greatest
+ *   (d + 1) << 32 | (0xffffffff - q) over the former, q = (x * dims[1] + y) * pitch + z: the greatest d and the
+ *   lexicographically first sample that has it; 0 while there is none.  Under HU_GEODESIC_EMPTY p is 64 for every sample.  One
+ *   atomic per accumulator, wavefront and part.
+ * All allocate nothing and synchronise nothing.  Every argument is checked before a device is touched (HU_ERR_BAD_ARG): NULL
+ * pointers, a pitch that is no multiple of 16 or below dims[2], dims of 0 or above 65536, more than 2^31 entries, an `of` above
+ * 63 that is neither HU_GEODESIC_SOLID nor HU_GEODESIC_EMPTY, an unknown mode, an axis outside 0..2, a layer from dims[axis] up,
+ * n_samples outside 1..HU_GEODESIC_MAX_SAMPLES, distances, samples or the word not aligned to 4, keys or counts not to 8 bytes. */
+#define HU_GEODESIC_SOLID 255
+#define HU_GEODESIC_EMPTY 254
+#define HU_GEODESIC_NONE 0xffffffffu
+#define HU_GEODESIC_BORDER 0
+#define HU_GEODESIC_LAYER 1
+#define HU_GEODESIC_LIST 2
+#define HU_GEODESIC_MAX_SAMPLES 65536
+#define HU_GEODESIC_SLOTS 65
+int hu_geodesic_seed(const void* ids_dev, void* dist_dev, const uint32_t dims[3], uint32_t pitch, uint32_t of, int mode, int axis,
+                     uint32_t layer, const uint32_t* samples_dev, uint32_t n_samples, void* stream);
+int hu_geodesic_sweep(const void* ids_dev, void* dist_dev, uint32_t* word_dev, const uint32_t dims[3], uint32_t pitch, int axis,
+                      uint32_t of, void* stream);
+int hu_geodesic_stats(const void* ids_dev, const void* dist_dev, uint64_t* keys_dev, uint64_t* counts_dev, const uint32_t dims[3],
+                      uint32_t pitch, uint32_t of, void* stream);
+
 /* ---- the surface meshes of an assembly's parts (codecad_amd/assembly_meshes.py) ----------------
  * The lattice of interference() with a ring of samples around it: samples carry the shifted index s = index + 1, 0 .. dims
  * per axis, and sit at corner + step * ((float)s - 1.0f) per axis in float32 (corner: the position of the sample (0, 0, 0) of

@@ -1,0 +1,247 @@
+"""hu_geodesic_seed, hu_geodesic_sweep and hu_geodesic_stats alone on raw volumes, at the tight pitch and at a wider one, against
+the references of flow_length_scenes.py: every seed mode, single sweeps of every axis on fields that are NO distance fields
+(random values, NONE, values near 2^31 next to NONE, arbitrary values outside S that must survive), words of a column that
+end and start runs at 63 | 64, a seed three words away, gaps inside a word, one line and one sample, one layer more than a
+batch, the serpentine round by round, and the statistics with ties -- every output EQUAL to the reference, byte for byte.
+The padding of the ids is POISONED with ids of S and the padding of the distances holds 0, a value that would seed: a kernel
+that reads either as data fails, and the padding of the distances is still 0 afterwards.
+(test_flow_length_host.py proves the references on the CPU.)"""
+import ctypes
+
+import numpy
+import pytest
+
+from codecad_amd import hip_util
+from codecad_amd.hip_util import check
+
+import raw_volume_scenes as raw
+import flow_length_scenes as scenes
+from flow_length_scenes import NONE, SOLID, EMPTY_SPACE, EMPTY
+
+pytestmark = pytest.mark.gpu
+OFS = (SOLID, 3, EMPTY_SPACE)
+PITCHES = (0, 32)                                                                     # beyond ceil16(nz)
+
+
+def ids_poison(of):
+    """Ids that are in S: read as data they would carry a way through the padding."""
+    return raw.alternating(0, 63) if of == SOLID else raw.constant(EMPTY if of == EMPTY_SPACE else of)
+
+
+def some_ids(rng, shape, empty=0.3):
+    """Ids from 0..63, about a third of them 3 (so that of = 3 has runs) and `empty` of the samples empty."""
+    ids = rng.integers(0, 64, size=shape).astype(numpy.uint8)
+    ids[rng.random(shape) < 0.35] = 3
+    ids[rng.random(shape) < empty] = EMPTY
+    return ids
+
+
+def some_field(rng, shape, s):
+    """No distance field: small values, NONE, and values near 2^31 and near NONE; outside S arbitrary values of their own."""
+    field = rng.integers(0, 40, size=shape).astype(numpy.uint32)
+    pick = rng.random(shape)
+    field[pick < 0.45] = NONE
+    field[(pick >= 0.45) & (pick < 0.5)] = rng.integers(2 ** 31 - 2, 2 ** 31 + 2, size=int(((pick >= 0.45) & (pick < 0.5)).sum()))
+    field[(pick >= 0.5) & (pick < 0.53)] = NONE - 1
+    outside = rng.integers(0, 2 ** 32, size=shape, dtype=numpy.uint64).astype(numpy.uint32)
+    outside[rng.random(shape) < 0.3] = 0                                              # zeros outside S: they would seed
+    return numpy.where(s, field, outside)
+
+
+class Device:
+    """The ids and a distance field on the device, both with their padding poisoned."""
+
+    def __init__(self, hip, ids, of, extra=0, field=None):
+        self.hip, self.of, self.shape = hip, of, ids.shape
+        self.pz = raw.ceil16(ids.shape[2]) + extra
+        host_ids, _ = raw.padded(ids, ids_poison(of), self.pz)
+        start = numpy.full(ids.shape, 7, dtype=numpy.uint32) if field is None else field
+        host_dist, _ = scenes.padded32(start, raw.constant(0), self.pz)
+        self.ids, self.dist = self.upload(host_ids), self.upload(host_dist)
+        self.word = hip_util.Buffer(numpy.uint32, (1,), queue=hip.queue)
+        self.dims = (ctypes.c_uint32 * 3)(*ids.shape)
+        self.buffers = [self.ids, self.dist, self.word]
+
+    def upload(self, host):
+        b = hip_util.Buffer(host.dtype, host.shape, queue=self.hip.queue)
+        b.enqueue_write(host)
+        return b
+
+    def seed(self, mode, axis=0, layer=0, samples=None):
+        rows = None
+        if samples is not None:
+            rows = self.upload(numpy.ascontiguousarray(samples, dtype=numpy.uint32))
+            self.buffers.append(rows)
+        check(self.hip.lib.hu_geodesic_seed(self.ids.device_ptr, self.dist.device_ptr, self.dims, self.pz, scenes.code(self.of), mode, axis, layer,
+                                            None if rows is None else rows.device_ptr, 0 if samples is None else len(samples),
+                                            self.hip.queue.handle), "hu_geodesic_seed")
+
+    def sweep(self, axis):
+        """-> whether the word came back nonzero"""
+        self.word.enqueue_fill(0)
+        check(self.hip.lib.hu_geodesic_sweep(self.ids.device_ptr, self.dist.device_ptr, self.word.device_ptr, self.dims, self.pz, axis,
+                                             scenes.code(self.of), self.hip.queue.handle), "hu_geodesic_sweep")
+        return int(self.word.read()[0]) != 0
+
+    def stats(self):
+        keys, counts = hip_util.Buffer(numpy.uint64, (65,), queue=self.hip.queue), hip_util.Buffer(numpy.uint64, (3, 65), queue=self.hip.queue)
+        self.buffers += [keys, counts]
+        keys.enqueue_fill(0), counts.enqueue_fill(0)
+        check(self.hip.lib.hu_geodesic_stats(self.ids.device_ptr, self.dist.device_ptr, keys.device_ptr, counts.device_ptr, self.dims, self.pz,
+                                             scenes.code(self.of), self.hip.queue.handle), "hu_geodesic_stats")
+        return keys.read().copy(), counts.read().copy()
+
+    def field(self):
+        """The in-lattice distances; the padding still holds its zeros."""
+        got = self.dist.read()
+        assert (got[:, :, self.shape[2]:] == 0).all()
+        return got[:, :, :self.shape[2]].copy()
+
+    def release(self):
+        for b in self.buffers:
+            b.release()
+
+
+def same(got, want):
+    wrong = numpy.argwhere(got != want)
+    assert len(wrong) == 0, [(tuple(k), int(got[tuple(k)]), int(want[tuple(k)])) for k in wrong[:8]]
+
+
+# ---- the seeds ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("extra", PITCHES)
+@pytest.mark.parametrize("of", OFS)
+@pytest.mark.parametrize("shape", [(5, 7, 130), (1, 1, 1), (3, 1, 17), (2, 3, 64)])
+def test_every_seed_mode_writes_every_entry(hip, shape, of, extra):
+    rng = numpy.random.default_rng(31 + sum(shape))
+    ids = some_ids(rng, shape)
+    s = scenes.in_set_of(ids, of)
+    device = Device(hip, ids, of, extra)
+    device.seed(scenes.MODE_BORDER)
+    same(device.field(), scenes.seeded(s, scenes.border_of(shape)))
+    for axis in range(3):
+        for layer in sorted({0, shape[axis] // 2, shape[axis] - 1}):
+            device.seed(scenes.MODE_LAYER, axis, layer)
+            same(device.field(), scenes.seeded(s, scenes.layer_of(shape, axis, layer)))
+    corners = [(x, y, z) for x in {0, shape[0] - 1} for y in {0, shape[1] - 1} for z in {0, shape[2] - 1}]
+    inside, outside = numpy.argwhere(s), numpy.argwhere(~s)
+    for samples in ([tuple(p) for p in inside[:1]], corners + [tuple(p) for p in outside[:2]] + [tuple(p) for p in inside[-3:]] + corners[:1]):
+        if samples:
+            device.seed(scenes.MODE_LIST, samples=samples)
+            same(device.field(), scenes.seeded(s, scenes.listed(shape, samples)))     # a listed sample not in S stays NONE
+    device.release()
+
+
+# ---- the sweeps, each axis alone ----------------------------------------------------------------------------------------
+
+def check_sweeps(hip, ids, of, field, extra):
+    s = scenes.in_set_of(ids, of)
+    for axis in range(3):
+        device = Device(hip, ids, of, extra, field)
+        want, lowered = scenes.swept(field, s, axis)
+        assert device.sweep(axis) == lowered
+        got = device.field()
+        same(got, want)
+        assert numpy.array_equal(got[~s], field[~s])                                  # entries outside S survive
+        assert not device.sweep(axis)                                                 # a line is final after one sweep: the word stays zero
+        same(device.field(), want)
+        device.release()
+
+
+@pytest.mark.parametrize("extra", PITCHES)
+@pytest.mark.parametrize("of", OFS)
+@pytest.mark.parametrize("nz", [1, 15, 16, 17, 63, 64, 65, 130])
+def test_a_sweep_equals_the_plain_walks_on_fields_that_are_no_distance_fields(hip, nz, of, extra):
+    shape = (5, 6, nz)                                                                # one layer more than a batch along x
+    rng = numpy.random.default_rng(900 + nz)
+    ids = some_ids(rng, shape)
+    check_sweeps(hip, ids, of, some_field(rng, shape, scenes.in_set_of(ids, of)), extra)
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 70), (1, 9, 1), (9, 1, 1), (1, 5, 3), (5, 1, 3), (1, 1, 1), (4, 4, 3), (8, 9, 5)])
+def test_single_lines_and_lattices_of_one_sample_a_side(hip, shape):
+    rng = numpy.random.default_rng(77 + sum(shape))
+    ids = some_ids(rng, shape, 0.15)
+    for of in (SOLID, EMPTY_SPACE):
+        check_sweeps(hip, ids, of, some_field(rng, shape, scenes.in_set_of(ids, of)), 16)
+    none = numpy.full(shape, NONE, dtype=numpy.uint32)                                # nothing is seeded: nothing falls
+    check_sweeps(hip, ids, SOLID, none, 0)
+
+
+def test_the_words_of_a_column(hip):
+    """Planted columns of 192 samples: a run that ends at 63 | 64, one that starts at 64, a seed in the last word that reaches the
+    first through three words, a gap inside a word that resets the carry, and a carry that saturates."""
+    ids = numpy.full((2, 3, 192), 3, dtype=numpy.uint8)
+    field = numpy.full(ids.shape, NONE, dtype=numpy.uint32)
+    ids[0, 0, 64:] = EMPTY                                                            # the run ends at 63
+    field[0, 0, 0] = 0
+    ids[0, 1, :64] = EMPTY                                                            # the run starts at 64
+    field[0, 1, 191] = 5
+    field[0, 2, 191] = 0                                                              # all of S: 191 steps down through three words
+    ids[1, 0, 100] = EMPTY                                                            # a gap inside the second word
+    field[1, 0, 70], field[1, 0, 100] = 0, 0                                          # (the zero in the gap is no seed)
+    field[1, 1, 10] = NONE - 3                                                        # saturates after three steps, both ways
+    field[1, 2, 63], field[1, 2, 64], field[1, 2, 128] = 9, 2, 2 ** 31
+    for of in (SOLID, 3):
+        s = scenes.in_set_of(ids, of)
+        want, lowered = scenes.swept(field, s, 2)
+        assert want[0, 2, 0] == 191 and want[0, 0, 63] == 63 and want[0, 1, 64] == 132 and want[1, 0, 99] == 29 and want[1, 0, 101] == NONE
+        assert want[1, 1, 12] == NONE - 1 and want[1, 1, 13] == NONE and want[1, 1, 8] == NONE - 1 and want[1, 1, 0] == NONE and want[1, 2, 63] == 3 and lowered
+        for extra in PITCHES:
+            device = Device(hip, ids, of, extra, field)
+            assert device.sweep(2)
+            same(device.field(), want)
+            assert not device.sweep(2)
+            device.release()
+
+
+def test_the_serpentine_round_by_round(hip):
+    ids, seeds = scenes.serpentine()
+    s = scenes.in_set_of(ids, SOLID)
+    fields, rounds = scenes.reference_rounds(s, seeds)
+    device = Device(hip, ids, SOLID, 0)
+    device.seed(scenes.MODE_LIST, samples=[tuple(p) for p in numpy.argwhere(seeds)])
+    same(device.field(), scenes.seeded(s, seeds))
+    ran = 0
+    while True:
+        changed = [device.sweep(axis) for axis in (2, 1, 0)]
+        same(device.field(), fields[ran])
+        ran += 1
+        if not any(changed):
+            break
+        assert ran < rounds
+    print("rounds", ran, "reference", rounds, "greatest d", int(fields[-1][s].max()))
+    assert ran == rounds == 12
+    keys, counts = device.stats()
+    want_keys, want_counts = scenes.raw_stats(ids, SOLID, fields[-1], device.pz)
+    assert keys.tolist() == want_keys.tolist() and counts.tolist() == want_counts.tolist() and int(keys[0]) >> 32 == 780
+    device.release()
+
+
+# ---- the statistics -----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("extra", PITCHES)
+@pytest.mark.parametrize("of", OFS)
+@pytest.mark.parametrize("kind", ["random", "none", "ties", "large"])
+def test_the_statistics(hip, kind, of, extra):
+    shape = (5, 7, 130)
+    rng = numpy.random.default_rng(4100 + len(kind))
+    ids = some_ids(rng, shape)
+    s = scenes.in_set_of(ids, of)
+    if kind == "none":
+        field = numpy.where(s, NONE, 0).astype(numpy.uint32)                          # (zeros outside S are not counted)
+    elif kind == "ties":
+        field = numpy.where(rng.random(shape) < 0.5, 6, NONE).astype(numpy.uint32)    # every reached sample is the farthest: the first wins
+    elif kind == "large":
+        field = some_field(rng, shape, s)
+        field[s & (rng.random(shape) < 0.1)] = NONE - 1                               # d + 1 fills the key's upper word
+    else:
+        field = some_field(rng, shape, s)
+    device = Device(hip, ids, of, extra, field)
+    keys, counts = device.stats()
+    want_keys, want_counts = scenes.raw_stats(ids, of, field, device.pz)
+    assert [hex(int(k)) for k in keys] == [hex(int(k)) for k in want_keys]
+    assert counts.tolist() == want_counts.tolist()
+    same(device.field(), field)                                                       # the statistics write no distance
+    assert (want_counts[0].sum() > 0) == (kind != "none") and want_counts[1].sum() > 0
+    device.release()

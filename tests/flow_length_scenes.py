@@ -196,6 +196,26 @@ def padded32(values, fill, pitch=None):
 
 # ---- raw volumes ------------------------------------------------------------------------------------------------------
 
+def some_ids(rng, shape, empty=0.3):
+    """Ids from 0..63, about a third of them 3 (so that of = 3 has runs) and `empty` of the samples empty."""
+    ids = rng.integers(0, 64, size=shape).astype(numpy.uint8)
+    ids[rng.random(shape) < 0.35] = 3
+    ids[rng.random(shape) < empty] = EMPTY
+    return ids
+
+
+def some_field(rng, shape, s):
+    """No distance field: small values, NONE, and values near 2^31 and near NONE; outside S arbitrary values of their own."""
+    field = rng.integers(0, 40, size=shape).astype(numpy.uint32)
+    pick = rng.random(shape)
+    field[pick < 0.45] = NONE
+    field[(pick >= 0.45) & (pick < 0.5)] = rng.integers(2 ** 31 - 2, 2 ** 31 + 2, size=int(((pick >= 0.45) & (pick < 0.5)).sum()))
+    field[(pick >= 0.5) & (pick < 0.53)] = NONE - 1
+    outside = rng.integers(0, 2 ** 32, size=shape, dtype=numpy.uint64).astype(numpy.uint32)
+    outside[rng.random(shape) < 0.3] = 0                                              # zeros outside S: they would seed
+    return numpy.where(s, field, outside)
+
+
 SERPENTINE = (21, 3, 70)
 
 

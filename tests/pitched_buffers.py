@@ -18,7 +18,9 @@ with their references, which take raw ids and know nothing of a pitch.  A family
 directions, the `local` arms, the transforms.  reference(family, case, arm) is an ordered dict name -> (kind, value):
   "volume"  [..][nz] last, compared on the lattice;  "table"  counts, keys, rows, words: compared whole;
   "labels"  linear indices, which depend on the lattice's nz (the device's are buffer indices until they are converted);
-  "field"   a 2D field of the tool kernels whose extent follows nz along the walks over x and y.
+  "field"   a 2D field of the tool kernels whose extent follows nz along the walks over x and y;
+  "far"     the farthest samples of hu_geodesic_stats as (d + 1, x, y, z): the device's key holds a buffer index, which the test
+            converts with the placed pitch.
 reference(..., widen=pitch) is the same reference over the volume AS IF ITS PADDING WERE DATA, the lattice nz' = pitch: the host
 test asserts that it differs, so a kernel that read the padding would not pass.  BLIND arms are those whose padding columns are
 independent of the lattice's and feed no count (the thickness passes along x and y with finish == 0): there the widened reference
@@ -39,6 +41,7 @@ import drainage_scenes as drain
 import islands_scenes as isl
 import tool_access_scenes as tool
 import wall_thickness_scenes as wall
+import flow_length_scenes as flow
 from raw_volume_scenes import SOLID, EMPTY, NONE, ceil16
 
 GUARD = 256                     # bytes of sentinel on either side of a placed array, at the least
@@ -148,7 +151,7 @@ def linear_index(entries, nz, pitch):
 
 # ---- the cases ----------------------------------------------------------------------------------------------------------------
 
-FAMILIES = ("components", "thickness", "overhang", "blocking", "contacts", "reach", "tool")
+FAMILIES = ("components", "thickness", "overhang", "blocking", "contacts", "reach", "tool", "geodesic")
 LOCAL_CASES = {"local:K2": "random_r5_ofsolid", "local:K9": "random_r81_ofsolid", "local:K12": "random_r144_ofsolid",
                "local:2x3x64": "long_z64", "local:2x3x65": "long_z65"}       # k_thick_local<4>, <10>, <16>; the words' edge
 TOOLS = {"2x3x64": tool.FLAT1, "2x3x65": tool.FLAT1, "3x5x130": tool.BALL3, "6x5x70": tool.STEEP}
@@ -160,6 +163,7 @@ CASES = collections.OrderedDict([
     ("contacts", ["random", "one_line_65", "1x3x17", "2x3x64"]),
     ("reach", ["drain:9x8x130", "drain:9x8x64", "ground:two_ids", "ground:9x8x130", "ground:9x8x64"]),
     ("tool", list(TOOLS)),
+    ("geodesic", ["5x7x130", "2x3x64", "1x1x70"]),
 ])
 # the thickness passes: (K, cap) along z; (K, cap, tile) along x and y, tile + 2 K <= 256 so that both arms run
 Z_PARAMS = ((8, 70), (65, 4226))
@@ -229,7 +233,47 @@ def ids_of(family, case):
         return _cropped(kind, "9x8x130", 64) if name == "9x8x64" else scenes.raw_ids(name)
     if family == "tool":
         return tool.noise((6, 5, 70), 0.3) if case == "6x5x70" else tool.noise(tuple(int(v) for v in case.split("x")), 0.3)
+    if family == "geodesic":
+        return geodesic_ids(case)
     raise KeyError(family)
+
+
+@functools.lru_cache(maxsize=None)
+def geodesic_ids(case):
+    """flow_length_scenes.some_ids; every column ends with an empty sample, with part 3 or with another part in turn, so that
+    under every `of` some column's top is in S and some is not."""
+    shape = tuple(int(v) for v in case.split("x"))
+    ids = flow.some_ids(numpy.random.default_rng(2700 + sum(shape)), shape)
+    tops = numpy.array([3, EMPTY, 7], dtype=numpy.uint8)[numpy.arange(shape[0] * shape[1]) % 3].reshape(shape[:2])
+    ids[:, :, -1] = tops if shape[0] * shape[1] > 1 else 3
+    ids.setflags(write=False)
+    return ids
+
+
+@functools.lru_cache(maxsize=None)
+def geodesic_field(case, of):
+    """flow_length_scenes.some_field, no distance field, for the sweeps and the statistics; NONE on every top that is in S, which
+    the zeros of the padding would lower."""
+    ids = geodesic_ids(case)
+    s = flow.in_set_of(ids, of)
+    field = flow.some_field(numpy.random.default_rng(2800 + sum(ids.shape)), ids.shape, s)
+    field[:, :, -1] = numpy.where(s[:, :, -1], NONE, field[:, :, -1])
+    field.setflags(write=False)
+    return field
+
+
+def geodesic_poison(of):
+    """Ids that are in S: read as data they would carry a way through the padding and be counted."""
+    return raw.alternating(0, 63) if of == SOLID else raw.constant(EMPTY if of == flow.EMPTY_SPACE else of)
+
+
+def geodesic_samples(case, of):
+    """The listed seeds: the first and the last samples of S, two outside it, a corner twice."""
+    ids = geodesic_ids(case)
+    s = flow.in_set_of(ids, of)
+    inside, outside = numpy.argwhere(s), numpy.argwhere(~s)
+    corner = tuple(n - 1 for n in ids.shape)
+    return [tuple(int(v) for v in p) for p in list(inside[:1]) + list(outside[:2]) + list(inside[-2:])] + [corner, corner]
 
 
 def ground_of(case):
@@ -260,6 +304,9 @@ def arms(family, case):
     if family == "tool":
         # (along x and y the padding adds columns: under SOLID they change nothing the lattice's columns see in some cases)
         return [(axis, up, 63) for axis, up in dis.DIRECTIONS] + [(2, True, SOLID), (2, False, SOLID)]
+    if family == "geodesic":
+        # (the one line holds one part at its top: in S for SOLID and for 3)
+        return [(of,) for of in ((SOLID, 3) if case == "1x1x70" else (SOLID, 3, flow.EMPTY_SPACE))]
     raise KeyError(family)
 
 
@@ -296,6 +343,9 @@ def inputs(family, case, arm, pitch=None):
         out["ids"] = raw.padded(ids, raw.DRAIN_POISON if case.startswith("drain:") else raw.ground_poison(ground_of(case)), pitch)[0]
     elif family == "tool":
         out["ids"] = raw.padded(ids, tool.RAW_POISON, pitch)[0]
+    elif family == "geodesic":
+        out["ids"] = raw.padded(ids, geodesic_poison(arm[0]), pitch)[0]
+        out["dist"] = flow.padded32(geodesic_field(case, arm[0]), raw.constant(0), pitch)[0]      # 0 in the padding: it would seed
     return out
 
 
@@ -395,6 +445,28 @@ def _reference(family, case, arm, given, labels=True):
         ref["cut"], ref["crowd"] = (along, r.cut), (along, r.crowd)
         ref["rest"] = ("volume", r.rest_ids)
         ref["undercut_counts"], ref["tight_counts"] = ("table", list(r.undercut_counts)), ("table", list(r.tight_counts))
+    elif family == "geodesic":
+        of, = arm
+        s = flow.in_set_of(ids, of)
+        shape = ids.shape
+        last = tuple(n - 1 for n in ids_of(family, case).shape)                    # the layers and the samples are the LATTICE's
+        ref["seed_border"] = ("volume", flow.seeded(s, flow.border_of(shape)))
+        for axis in range(3):
+            ref["seed_layer%d" % axis] = ("volume", flow.seeded(s, flow.layer_of(shape, axis, last[axis])))
+        ref["seed_list"] = ("volume", flow.seeded(s, flow.listed(shape, geodesic_samples(case, of))))
+        lowered = []
+        for axis in range(3):
+            out, low = flow.swept(given["dist"], s, axis)
+            ref["swept%d" % axis] = ("volume", out)
+            lowered.append(int(low))
+        ref["lowered"] = ("table", lowered)
+        keys, counts = flow.raw_stats(ids, of, given["dist"], shape[2])
+        ref["counts"] = ("table", counts.tolist())
+        far = []
+        for key in keys.tolist():
+            q = 0xffffffff - (key & 0xffffffff)
+            far.append((key >> 32,) + tuple(int(v) for v in numpy.unravel_index(q, shape)) if key else (0, 0, 0, 0))
+        ref["far"] = ("far", far)
     return ref
 
 
@@ -423,7 +495,7 @@ def widened_differs(family, case, arm, pitch):
         other = wide[name][1]
         if kind in ("volume", "field"):
             other = other[..., :nz]
-        elif kind in ("labels", "tips"):
+        elif kind in ("labels", "tips", "far"):
             continue
         if mismatches(other, want, 1):
             return True

@@ -1,7 +1,8 @@
 """drainage() on the device against the reference of drainage_scenes.py, which is written from the definitions: the part ids, the
 trapped ids and their counts, the labels and every field of every pool are EQUAL to the reference, entry for entry, on every
 scene and in all six directions, whatever the labelling's arm and the pool table's first capacity were; and the four entry
-points alone on raw id volumes whose padding holds ids that would change the answer, the rise driven pass by pass."""
+points alone on raw id volumes whose padding holds ids that would change the answer, the rise driven pass by pass; and the
+rise and the floors along z over more columns than the grid has wavefronts, where a wavefront takes a second column."""
 import ctypes
 
 import numpy
@@ -14,6 +15,7 @@ from codecad_amd.hip_util import check
 import disassembly_scenes as dis_scenes
 import drainage_scenes as scenes
 import raw_volume_scenes as raw
+import wide_volume_scenes as wide
 from drainage_scenes import CASES, RAW_CASES, RAW_PARTS, reference, raw_reference, raw_ids, raw_labels, scene, EMPTY, NONE
 
 pytestmark = pytest.mark.gpu
@@ -163,3 +165,54 @@ def test_the_entry_points_alone_on_raw_volumes(hip, name, axis, up):
     assert len(wrong) == 0, [(tuple(k), int(written[tuple(k)]), int(ref.trapped_ids[tuple(k)])) for k in wrong[:8]]
     assert (written[:, :, nz:] == SENTINEL).all()
     assert [int(v) for v in totals[:RAW_PARTS]] == ref.trapped_counts
+
+
+# ---- past the grid's cap: a wavefront takes a second column (wide_volume_scenes.py) ---------------------------------------------
+
+def same_bytes(got, want, what):
+    wrong = numpy.argwhere(got != want)
+    assert len(wrong) == 0, (what, [(tuple(k), int(got[tuple(k)]), int(want[tuple(k)])) for k in wrong[:8]])
+
+
+@pytest.mark.parametrize("up", [True, False])
+@pytest.mark.parametrize("name", list(wide.REACH_SHAPES))
+def test_a_wavefront_walks_a_second_column(hip, name, up):
+    """hu_drain_floor and hu_drain_rise along z over more than GRID_WAVEFRONTS columns, on labels whose flags are crafted: every
+    layer component is one sample, so the label buffer is written here and ONE pass of the rise is the fixed point.  The first
+    columns end flagged and with a floor, the second begin unflagged or outside E: a carry or a floor taken along would show."""
+    shape = wide.REACH_SHAPES[name]
+    c = wide.reach_case(shape, "empty")
+    nx, ny, nz = shape
+    padded, pz = padded_ids(c.ids)
+    lib, queue = hip.lib, hip.queue
+    dims = (ctypes.c_uint32 * 3)(nx, ny, nz)
+    volume, trapped = (hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue) for _ in range(2))
+    labels = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
+    acc = hip_util.Buffer(numpy.uint64, (64,), queue=queue)
+    word = hip_util.Buffer(numpy.uint32, (1,), queue=queue)
+    buffers = (volume, trapped, labels, acc, word)
+
+    def floors(flagged, what):
+        trapped.enqueue_fill(SENTINEL)
+        acc.enqueue_fill(0)
+        check(lib.hu_drain_floor(volume.device_ptr, labels.device_ptr, trapped.device_ptr, acc.device_ptr, dims, pz, 2, int(up),
+                                 queue.handle), "hu_drain_floor")
+        written, totals = trapped.read().copy(), acc.read().copy()
+        want, counts = wide.trapped_of(c.ids, flagged, 2, up)
+        same_bytes(written[:, :, :nz], want, what)
+        assert (written[:, :, nz:] == SENTINEL).all() and [int(v) for v in totals] == counts and sum(counts) > 0, what
+
+    try:
+        volume.enqueue_write(padded)
+        labels.enqueue_write(wide.own_labels(c.r, pz, c.flags))
+        floors(c.flags, "the floors under the crafted flags")
+        want = wide.risen(c.r, c.flags, 2, up)
+        for changed in (1, 0):                                                          # the pass, and a pass that finds nothing to do
+            word.enqueue_fill(0)
+            check(lib.hu_drain_rise(labels.device_ptr, word.device_ptr, dims, pz, 2, int(up), queue.handle), "hu_drain_rise")
+            assert int(word.read()[0]) == changed
+            same_bytes(labels.read().copy(), wide.own_labels(c.r, pz, want), "the labels after the rise")
+        floors(want, "the floors after the rise")
+    finally:
+        for b in buffers:
+            b.release()

@@ -2,7 +2,8 @@
 the references of flow_length_scenes.py: every seed mode, single sweeps of every axis on fields that are NO distance fields
 (random values, NONE, values near 2^31 next to NONE, arbitrary values outside S that must survive), words of a column that
 end and start runs at 63 | 64, a seed three words away, gaps inside a word, one line and one sample, one layer more than a
-batch, the serpentine round by round, and the statistics with ties -- every output EQUAL to the reference, byte for byte.
+batch, the serpentine round by round, the statistics with ties, and lattices of more columns than the grid has wavefronts,
+where a wavefront takes a second unit -- every output EQUAL to the reference, byte for byte.
 The padding of the ids is POISONED with ids of S and the padding of the distances holds 0, a value that would seed: a kernel
 that reads either as data fails, and the padding of the distances is still 0 afterwards.
 (test_flow_length_host.py proves the references on the CPU.)"""
@@ -16,7 +17,8 @@ from codecad_amd.hip_util import check
 
 import raw_volume_scenes as raw
 import flow_length_scenes as scenes
-from flow_length_scenes import NONE, SOLID, EMPTY_SPACE, EMPTY
+import wide_volume_scenes as wide
+from flow_length_scenes import NONE, SOLID, EMPTY_SPACE, EMPTY, some_ids, some_field
 
 pytestmark = pytest.mark.gpu
 OFS = (SOLID, 3, EMPTY_SPACE)
@@ -26,26 +28,6 @@ PITCHES = (0, 32)                                                               
 def ids_poison(of):
     """Ids that are in S: read as data they would carry a way through the padding."""
     return raw.alternating(0, 63) if of == SOLID else raw.constant(EMPTY if of == EMPTY_SPACE else of)
-
-
-def some_ids(rng, shape, empty=0.3):
-    """Ids from 0..63, about a third of them 3 (so that of = 3 has runs) and `empty` of the samples empty."""
-    ids = rng.integers(0, 64, size=shape).astype(numpy.uint8)
-    ids[rng.random(shape) < 0.35] = 3
-    ids[rng.random(shape) < empty] = EMPTY
-    return ids
-
-
-def some_field(rng, shape, s):
-    """No distance field: small values, NONE, and values near 2^31 and near NONE; outside S arbitrary values of their own."""
-    field = rng.integers(0, 40, size=shape).astype(numpy.uint32)
-    pick = rng.random(shape)
-    field[pick < 0.45] = NONE
-    field[(pick >= 0.45) & (pick < 0.5)] = rng.integers(2 ** 31 - 2, 2 ** 31 + 2, size=int(((pick >= 0.45) & (pick < 0.5)).sum()))
-    field[(pick >= 0.5) & (pick < 0.53)] = NONE - 1
-    outside = rng.integers(0, 2 ** 32, size=shape, dtype=numpy.uint64).astype(numpy.uint32)
-    outside[rng.random(shape) < 0.3] = 0                                              # zeros outside S: they would seed
-    return numpy.where(s, field, outside)
 
 
 class Device:
@@ -244,4 +226,52 @@ def test_the_statistics(hip, kind, of, extra):
     assert counts.tolist() == want_counts.tolist()
     same(device.field(), field)                                                       # the statistics write no distance
     assert (want_counts[0].sum() > 0) == (kind != "none") and want_counts[1].sum() > 0
+    device.release()
+
+
+# ---- past the grid's cap: a wavefront takes a second unit (wide_volume_scenes.py) -----------------------------------------------
+
+@pytest.mark.parametrize("of", OFS)
+@pytest.mark.parametrize("name", list(wide.COLUMN_SHAPES))
+def test_a_wavefront_sweeps_a_second_column(hip, name, of):
+    """More than GRID_WAVEFRONTS columns: k_geo_sweep_columns walks the units w and w + G; the carry that the walk down of the
+    first leaves at z = 0 would lower the second (test_wide_volumes_host.py)."""
+    shape = wide.COLUMN_SHAPES[name]
+    ids, field = wide.geo_ids(shape), wide.geo_field(shape, of)
+    s = scenes.in_set_of(ids, of)
+    want, lowered = scenes.swept(field, s, 2)
+    device = Device(hip, ids, of, 0, field)
+    assert lowered and device.sweep(2)
+    got = device.field()
+    same(got, want)
+    assert numpy.array_equal(got[~s], field[~s])
+    assert not device.sweep(2)                                                        # a second sweep leaves the word zero
+    same(device.field(), want)
+    device.release()
+
+
+@pytest.mark.parametrize("of", OFS)
+@pytest.mark.parametrize("name", list(wide.COLUMN_SHAPES))
+def test_the_seeds_and_the_statistics_past_the_cap(hip, name, of):
+    """129 x 128 x 70 has 33024 segment units: k_geo_seed and k_geo_stats, four units a wavefront at the least, loop there too."""
+    shape = wide.COLUMN_SHAPES[name]
+    ids, field = wide.geo_ids(shape), wide.geo_field(shape, of)
+    s = scenes.in_set_of(ids, of)
+    device = Device(hip, ids, of, 0, field)
+    keys, counts = device.stats()
+    want_keys, want_counts = scenes.raw_stats(ids, of, field, device.pz)
+    assert [hex(int(k)) for k in keys] == [hex(int(k)) for k in want_keys] and counts.tolist() == want_counts.tolist()
+    same(device.field(), field)
+    device.seed(scenes.MODE_BORDER)
+    same(device.field(), scenes.seeded(s, scenes.border_of(shape)))
+    for axis, layer in ((0, shape[0] - 1), (1, 0), (2, shape[2] - 1)):
+        device.seed(scenes.MODE_LAYER, axis, layer)
+        same(device.field(), scenes.seeded(s, scenes.layer_of(shape, axis, layer)))
+    inside = numpy.argwhere(s)
+    samples = [tuple(p) for p in inside[:2]] + [tuple(p) for p in inside[-3:]] + [tuple(p) for p in numpy.argwhere(~s)[-2:]]
+    device.seed(scenes.MODE_LIST, samples=samples)
+    same(device.field(), scenes.seeded(s, scenes.listed(shape, samples)))
+    keys, counts = device.stats()                                                     # ... and of a field of zeros and NONE
+    want_keys, want_counts = scenes.raw_stats(ids, of, scenes.seeded(s, scenes.listed(shape, samples)), device.pz)
+    assert keys.tolist() == want_keys.tolist() and counts.tolist() == want_counts.tolist()
     device.release()

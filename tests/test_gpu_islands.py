@@ -16,6 +16,7 @@ import disassembly_scenes as dis_scenes
 import drainage_scenes
 import islands_scenes as scenes
 import raw_volume_scenes as raw
+import wide_volume_scenes as wide
 from islands_scenes import CASES, RAW_CASES, RAW_PARTS, reference, raw_reference, raw_ids, raw_labels, scene, EMPTY, NONE, SOLID
 
 pytestmark = pytest.mark.gpu
@@ -221,3 +222,91 @@ def test_stage_one_alone_serves_the_three_predicates_from_one_kernel(hip, name):
         assert numpy.array_equal(zero | one, s)                                     # the last two partition the solid
     else:
         assert set(numpy.unique(ids[s]).tolist()) == set(range(64)) and (s & ~(zero | one)).any()
+
+
+# ---- past the grid's cap: a wavefront takes a second unit (wide_volume_scenes.py) -----------------------------------------------
+
+def same_bytes(got, want, what):
+    wrong = numpy.argwhere(got != want)
+    assert len(wrong) == 0, (what, [(tuple(k), int(got[tuple(k)]), int(want[tuple(k)])) for k in wrong[:8]])
+
+
+@pytest.mark.parametrize("of", [SOLID, 63])
+@pytest.mark.parametrize("up", [True, False])
+@pytest.mark.parametrize("name", list(wide.REACH_SHAPES))
+def test_a_wavefront_walks_a_second_column(hip, name, up, of):
+    """hu_ground_mark, hu_ground_seed and hu_drain_rise along z over more than GRID_WAVEFRONTS columns, on labels written here
+    (every layer component is one sample) with crafted flags: the first columns end in a grounded sample of S, the second begin
+    with a floating one or outside S."""
+    shape = wide.REACH_SHAPES[name]
+    c = wide.reach_case(shape, "solid")
+    nx, ny, nz = shape
+    s = scenes.in_set_of(c.ids, of)
+    flags = c.flags & s
+    code = 255 if of == SOLID else of
+    padded, pz = padded_ids(c.ids, of)
+    lib, queue = hip.lib, hip.queue
+    dims = (ctypes.c_uint32 * 3)(nx, ny, nz)
+    volume, floating, start, join = (hip_util.Buffer(numpy.uint8, (nx, ny, pz), queue=queue) for _ in range(4))
+    labels = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
+    acc = hip_util.Buffer(numpy.uint64, (3, 64), queue=queue)
+    depth, word = (hip_util.Buffer(numpy.uint32, (1,), queue=queue) for _ in range(2))
+
+    def marks(grounded, what):
+        for b in (floating, start, join):
+            b.enqueue_fill(SENTINEL)
+        acc.enqueue_fill(0)
+        check(lib.hu_ground_mark(volume.device_ptr, labels.device_ptr, floating.device_ptr, start.device_ptr, join.device_ptr, acc.device_ptr,
+                                 dims, pz, 2, int(up), code, queue.handle), "hu_ground_mark")
+        totals = acc.read().copy()
+        for k, (b, (want, counts)) in enumerate(zip((floating, start, join), wide.marks_of(c.ids, s, grounded, 2, up))):
+            got = b.read().copy()
+            same_bytes(got[:, :, :nz], want, (what, k))
+            assert (got[:, :, nz:] == SENTINEL).all() and [int(v) for v in totals[k]] == counts and sum(counts) > 0, (what, k)
+
+    try:
+        volume.enqueue_write(padded)
+        labels.enqueue_write(wide.own_labels(s, pz, flags))
+        marks(flags, "the marks under the crafted flags")
+        want = wide.risen(s, flags, 2, up)
+        for changed in (1, 0):
+            word.enqueue_fill(0)
+            check(lib.hu_drain_rise(labels.device_ptr, word.device_ptr, dims, pz, 2, int(up), queue.handle), "hu_drain_rise")
+            assert int(word.read()[0]) == changed
+            same_bytes(labels.read().copy(), wide.own_labels(s, pz, want), "the labels after the rise")
+        marks(want, "the marks after the rise")
+        # the seeds: the true first layer, and layers that the word only claims, in the second word and in the last lane of the first
+        for h0 in (scenes.first_layer(s, 2, up), 65, 63):
+            labels.enqueue_write(wide.own_labels(s, pz))
+            depth.enqueue_write(numpy.array([nz - h0], dtype=numpy.uint32))
+            check(lib.hu_ground_seed(labels.device_ptr, depth.device_ptr, dims, pz, 2, int(up), queue.handle), "hu_ground_seed")
+            seeds = s & (drainage_scenes.layers(shape, 2, up) == h0)
+            assert seeds.any() and int(depth.read()[0]) == nz - h0
+            same_bytes(labels.read().copy(), wide.own_labels(s, pz, seeds), ("the seeds of layer", h0))
+        assert numpy.array_equal(s & (drainage_scenes.layers(shape, 2, up) == scenes.first_layer(s, 2, up)), scenes.seeds(s, 2, up))
+    finally:
+        for b in (volume, floating, start, join, labels, acc, depth, word):
+            b.release()
+
+
+@pytest.mark.parametrize("up", [True, False])
+@pytest.mark.parametrize("na", raw.WIDE_NA)
+@pytest.mark.parametrize("axis", [0, 1])
+def test_a_wavefront_seeds_a_second_line(hip, axis, na, up):
+    """hu_ground_seed along x and y over 10000 line units: a layer component is a whole z line, its root the sample at z = 0, and
+    the lanes of a unit share it.  Every layer in turn is claimed by the depth word."""
+    ids, r = wide.seed_lines(axis, na)
+    nx, ny, nz = ids.shape
+    pz = raw.ceil16(nz) + 16
+    lib, queue = hip.lib, hip.queue
+    dims = (ctypes.c_uint32 * 3)(nx, ny, nz)
+    labels = hip_util.Buffer(numpy.uint32, (nx, ny, pz), queue=queue)
+    depth = hip_util.Buffer(numpy.uint32, (1,), queue=queue)
+    try:
+        for layer in sorted({0, na // 2, na - 1}):
+            labels.enqueue_write(wide.line_labels(r, pz))
+            depth.enqueue_write(numpy.array([na - (layer if up else na - 1 - layer)], dtype=numpy.uint32))
+            check(lib.hu_ground_seed(labels.device_ptr, depth.device_ptr, dims, pz, axis, int(up), queue.handle), "hu_ground_seed")
+            same_bytes(labels.read().copy(), wide.line_labels(r, pz, wide.seeded_lines(r, axis, layer, False)), ("layer", layer))
+    finally:
+        labels.release(), depth.release()

@@ -1,7 +1,7 @@
-"""The id-volume entry points of include/hip_util.h at every pitch and alignment their contract allows: the 24 entry points of
+"""The id-volume entry points of include/hip_util.h at every pitch and alignment their contract allows: the 27 entry points of
 instance_components.hip, instance_thickness.hip, instance_local.hip, instance_overhang.hip, instance_blocking.hip,
-instance_contacts.hip, instance_reach.hip and instance_tool.hip over the buffers of pitched_buffers.py -- a pitch one word and
-more than one 64-sample segment beyond ceil16(nz), every pointer aligned to what its entry point asks for and to no more, the
+instance_contacts.hip, instance_reach.hip, instance_tool.hip and instance_geodesic.hip over the buffers of pitched_buffers.py
+-- a pitch one word and more than one 64-sample segment beyond ceil16(nz), every pointer aligned to what its entry point asks for and to no more, the
 whole padding poisoned, sentinels in every output's padding and in guard zones around every buffer -- against the NumPy
 references of the raw cases, which know nothing of a pitch.  Every output is EQUAL to its reference, entry for entry; every byte
 of an output's padding still holds the sentinel (the labels' padding: NONE, which hu_components_local, hu_drain_layers and
@@ -330,8 +330,64 @@ def run_tool(hip, case, arm, placement):
             "undercut_counts": totals[:64], "tight_counts": totals[64:]}
 
 
+def run_geodesic(hip, case, arm, placement):
+    """hu_geodesic_seed in its three modes, hu_geodesic_sweep on each axis and hu_geodesic_stats: the distances, the changed word
+    and the samples aligned to 4 bytes and no more, the keys and the counts to 8, the ids at an odd address (they have no check);
+    the padding of the distances holds 0, which would seed, and still holds it afterwards."""
+    of, = arm
+    ids = pb.ids_of("geodesic", case)
+    flow = pb.flow
+    r = Run(hip, placement, ids.shape)
+    lib, s, pitch, dims = hip.lib, hip.queue.handle, r.pitch, r.dims
+    given = pb.inputs("geodesic", case, arm, pitch)
+    volume = r.volume("ids", given["ids"], 1)
+    host = pb.sentinel(numpy.uint32, ids.shape[:2] + (pitch,))                       # every in-lattice entry is written by a seed
+    host[:, :, r.nz:] = 0
+    r.placed["dist"] = (Placed(hip.queue, host, 4, placement, r.nz), 0)
+    dist = r.placed["dist"][0].ptr
+    rows = numpy.array(pb.geodesic_samples(case, of), dtype=numpy.uint32)
+    samples = r.array("samples", rows, 4)
+    word = r.array("word", numpy.zeros(1, dtype=numpy.uint32), 4)
+    keys, counts = r.array("keys", zeros(65), 8), r.array("counts", zeros(3 * 65).reshape(3, 65), 8)
+    code = flow.code(of)
+    got = {}
+
+    def field():
+        lattice, padding, _ = r.placed["dist"][0].read()
+        assert (padding == 0).all()
+        return lattice
+
+    last = [n - 1 for n in ids.shape]
+    check(lib.hu_geodesic_seed(volume, dist, dims, pitch, code, flow.MODE_BORDER, 0, 0, None, 0, s), "hu_geodesic_seed")
+    got["seed_border"] = field()
+    for axis in range(3):
+        check(lib.hu_geodesic_seed(volume, dist, dims, pitch, code, flow.MODE_LAYER, axis, last[axis], None, 0, s), "hu_geodesic_seed")
+        got["seed_layer%d" % axis] = field()
+    check(lib.hu_geodesic_seed(volume, dist, dims, pitch, code, flow.MODE_LIST, 0, 0, samples, len(rows), s), "hu_geodesic_seed")
+    got["seed_list"] = field()
+    lowered = []
+    for axis in range(3):
+        r.placed["dist"][0].refill(given["dist"])
+        r.placed["word"][0].refill(numpy.zeros(1, dtype=numpy.uint32))
+        check(lib.hu_geodesic_sweep(volume, dist, word, dims, pitch, axis, code, s), "hu_geodesic_sweep")
+        got["swept%d" % axis] = field()
+        lowered.append(int(r.placed["word"][0].read()[0][0] != 0))
+    got["lowered"] = lowered
+    r.placed["dist"][0].refill(given["dist"])
+    check(lib.hu_geodesic_stats(volume, dist, keys, counts, dims, pitch, code, s), "hu_geodesic_stats")
+    back = r.read()
+    assert numpy.array_equal(back["dist"], given["dist"][:, :, :r.nz]) and numpy.array_equal(back["samples"], rows)   # the statistics write no distance
+    got["counts"] = back["counts"].tolist()
+    far = []
+    for key in back["keys"].tolist():                                               # the key's buffer index, by the PLACED pitch
+        q = 0xffffffff - (key & 0xffffffff)
+        far.append((key >> 32, q // pitch // ids.shape[1], q // pitch % ids.shape[1], q % pitch) if key else (0, 0, 0, 0))
+    got["far"] = far
+    return got
+
+
 RUNNERS = {"components": run_components, "thickness": run_thickness, "overhang": run_overhang, "blocking": run_blocking,
-           "contacts": run_contacts, "reach": run_reach, "tool": run_tool}
+           "contacts": run_contacts, "reach": run_reach, "tool": run_tool, "geodesic": run_geodesic}
 
 
 @pytest.mark.parametrize("family,case,placement", pb.combinations(), ids=lambda v: str(v).replace(":", "_"))

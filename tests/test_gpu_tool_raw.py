@@ -14,6 +14,7 @@ from codecad_amd.hip_util import check
 
 import raw_volume_scenes as raw
 import tool_access_scenes as scenes
+import wide_volume_scenes as wide
 from tool_access_scenes import RAW_NAMES, RAW_BY_NAME, EMPTY
 
 pytestmark = pytest.mark.gpu
@@ -88,3 +89,20 @@ def test_an_empty_volume_leaves_zeros(hip, axis, up):
     got = tool_kernels(hip, c)
     check_against_reference(got, scenes.reference_tool_access(ids, axis, up, scenes.BALL3, scenes.SOLID, 64, pockets=False), ids.shape)
     assert not got[0].any() and not got[1].any() and (got[2] == EMPTY).all() and (got[3][:, :, :130] == EMPTY).all() and not got[4].any()
+
+
+# ---- past the grid's cap: a wavefront takes a second line unit (wide_volume_scenes.py) --------------------------------------------
+
+@pytest.mark.parametrize("na", raw.WIDE_NA)
+@pytest.mark.parametrize("axis", [0, 1])
+def test_a_wavefront_walks_a_second_line(hip, axis, na):
+    """hu_tool_tops and hu_tool_rest along x and y over 10000 line units: the lines a wavefront walks second hold other parts than
+    the first, and half of them no sample of S at all -- their key is 0, whatever key the lane held before."""
+    ids = wide.tool_ids(axis, na)
+    for up in (True, False):
+        for of in wide.TOOL_OFS:
+            ref = wide.tool_reference(axis, na, up, of)
+            got = tool_kernels(hip, scenes.RawCase("wide", ids, axis, up, wide.TOOL, of))
+            check_against_reference(got, ref, ids.shape)
+            second = ref.tops[wide.line_kinds() == 1]                                # the lines a wavefront walks second
+            assert (second == 0).any() and (second > 0).any()

@@ -125,6 +125,16 @@ def test_the_helpers_called_without_a_pitch_give_the_bytes_they_gave_before():
     import test_gpu_contacts
     import test_gpu_drainage
     import test_gpu_islands
+    import test_gpu_geodesic_raw
+    for case in pb.CASES["geodesic"]:                                               # the geodesic family pads as the geodesic raw test does
+        for of, in pb.arms("geodesic", case):
+            ids, field = pb.geodesic_ids(case), pb.geodesic_field(case, of)
+            assert same(raw.padded(ids, pb.geodesic_poison(of)), _old_fill(numpy.uint8, ids, test_gpu_geodesic_raw.ids_poison(of)))
+            assert same(pb.flow.padded32(field, raw.constant(0)), _old_fill(numpy.uint32, field, raw.constant(0)))
+            given = pb.inputs("geodesic", case, (of,))
+            assert same((given["ids"], 0), (raw.padded(ids, pb.geodesic_poison(of))[0], 0)) and not given["dist"][:, :, ids.shape[2]:].any()
+            s = pb.flow.in_set_of(ids, of)
+            assert s[:, :, -1].any() and (field[:, :, -1][s[:, :, -1]] == NONE).all()     # a top in S that the padding's zeros would lower
     for name in raw.Z_LATTICES:
         for of in raw.Z_OFS:
             assert same(raw.padded(raw.z_ids(name), raw.z_ids_poison(of)), _old_fill(numpy.uint8, raw.z_ids(name), raw.z_ids_poison(of)))
